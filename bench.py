@@ -5,6 +5,8 @@
                                                              torch.distributed.run, one rank per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --full                                 (the headline plus every extra measurement listed below)
+    python bench.py --dump-outputs DIR                     (also writes the last timed step's outputs as DIR/<name>.npy)
 
 A "step" is one Track4D.backbone() pass (PointNet++ MSG encoder over both frames, kNN cost volume,
 decoder PNHead, GRU, scene-flow + motion-segmentation heads) over one synthetic batch of B frame-pairs
@@ -12,12 +14,16 @@ already resident in HBM.  One process per GPU; frame-pairs are independent, so r
 batches with no data-path collective (weak scaling); the timed region is bracketed by a barrier +
 synchronize on both sides and the maximum over ranks is reported.
 
-The timed region is EXACTLY `steps` steps with steps = max(K asked for, the steps HEADLINE_SECONDS = 11 s take) -- a K = 20 window is
-15 ms, which nothing outside this process can check (round 4's 1.5 s window was invisible to a 10 s utilisation sampler too); the
-K-step window itself is reported as `k_step_window`.  NBATCH distinct resident batches rotate
-through the steps (no step re-reads its predecessor's inputs).
+The timed region is EXACTLY K steps, after W warm-up steps (and, in the forward, as many more untimed steps as 0.5 s takes).
+NBATCH distinct resident batches rotate through the steps (no step re-reads its predecessor's inputs); the rotation starts afresh in
+every timed region, so the inputs of its i-th step, and with them the outputs --dump-outputs writes, depend on i alone.
+--dump-outputs DIR writes what the timed path returned in its last step as float32 .npy files (forward: flow, h, cls, cor,
+pc1_features, pc2_features, prop; --mode train: h and the loss items as loss_<name>), at most DUMP_BYTES in all: above that every
+array is cut to a fixed, seeded sample of its elements.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+A plain run measures the headline and nothing else.  With --full, rank 0's ONE JSON line also carries
+  long_window         the same timed region over max(K, the steps HEADLINE_SECONDS = 11 s take) -- a K = 20 window is 15 ms, which
+                      nothing outside this process can check (round 4's 1.5 s window was invisible to a 10 s utilisation sampler too);
   configs             BASELINE.json's other single-GPU forward configurations with the same method: config 2 (B=32, N=256) and
                       config 5 (B=32, N=1024): ms/step, pairs/s, the dominant kernel alone against the split matrix peak;
   roofline            the dominant kernel (cost_volume_split_kernel) against its matrix peak (dense fp16 / 3 products per fp32
@@ -37,7 +43,8 @@ Round 6: roofline.profile_frac (the same FLOPs / the kernel's average in the new
 to the in-situ frac), kernels_alone as the median of 7 eager passes, train.allreduce_us_1rank (the gradient bucket through a 1-rank
 RCCL group), roofline_irregular with the product path's two geometry launches.
 
-`--mode train` makes the train step the headline line instead (same fields).
+`--mode train` makes the train step the headline line instead (same fields; with --full its roofline, kernel count, all-reduce
+timings and CPU baseline).
 """
 import argparse
 import json
@@ -62,10 +69,12 @@ BF16_PEAK_TFLOPS = 2500.0     # dense bf16 = fp16 MFMA peak (MI355X_MICROARCH.md
 SPLIT_PRODUCTS = 3
 SPLIT_PEAK_TFLOPS = BF16_PEAK_TFLOPS / SPLIT_PRODUCTS
 DTYPE = "f32 (2xfp16 split MFMA: three fp16 products per fp32 product, fp32 accumulate, power-of-two scales per matrix and position)"
-HEADLINE_SECONDS = 11.0       # the headline timed region (a utilisation sampler outside the process must see it)
+HEADLINE_SECONDS = 11.0       # --full: the long window (a utilisation sampler outside the process must see it)
 CONFIG_SECONDS = 3.0          # configs 2 and 5
 HBM_PEAK_GBS = 8000.0
 NBATCH = 8                    # distinct synthetic batches resident in HBM, rotated through the timed steps
+DUMP_BYTES = 60 << 20         # --dump-outputs: bytes of array data in all (B=64, N=256 forward: 56.4 MiB, written whole)
+FORWARD_OUTPUTS = ("flow", "h", "cls", "cor", "pc1_features", "pc2_features", "prop")      # Track4D.backbone's return, in order
 PMC = {"forward": "pmc_cost_volume.json", "train": "pmc_cost_volume_bwd.json", "irregular": "irregular_hbm.json"}      # profiles/rNN_<name>
 ROUNDS = ["r%02d" % r for r in range(6, 0, -1)]                                                                       # newest first
 
@@ -415,10 +424,12 @@ def time_cost_volume_bwd(batch, n, dev, iters=10):
     return train_ops.time_cost_volume_bwd(batch, n, dev, iters)
 
 
-def run_train(a, net, d, dev, dist, world, rank, steps, warmup, live_traffic=None):
+def run_train(a, net, d, dev, dist, world, rank, steps, warmup, live_traffic=None, full=True, dump=None):
     """Train step per rank on B frame-pairs: train-mode forward (training path: fused HIP operators under autograd),
     multi-task loss, backward, ONE flat gradient all-reduce over RCCL, Adam.  Weak scaling (B per GPU fixed).
-    world 1: one hipGraph; world > 1: graph (forward..gradient pack) -> eager RCCL all-reduce -> graph (Adam)."""
+    world 1: one hipGraph; world > 1: graph (forward..gradient pack) -> eager RCCL all-reduce -> graph (Adam).
+    full: also the all-reduce timings, the dominant kernel's roofline and the kernel count.  dump: rank 0 writes the last timed
+    step's return (h and the loss items) there."""
     from ratrack_amd.ddp import broadcast_parameters
     from ratrack_amd.train import Trainer
     broadcast_parameters(net)
@@ -442,12 +453,27 @@ def run_train(a, net, d, dev, dist, world, rank, steps, warmup, live_traffic=Non
     for _ in range(max(warmup, 5 if use_graph else 1)):      # >= 3 eager warm-ups + the capture + one replay
         step()
     barrier()
+    rot["i"] = 0
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        out = step()
     barrier()
     mine = time.perf_counter() - t0
     el, per_rank = reduce_times(mine, dist, dev, world)
+    if dump and rank == 0:
+        items, h_out = out
+        dump_outputs(dump, [("h", h_out)] + [("loss_" + k, v) for k, v in items.items()])
+    res = None
+    if rank == 0:
+        res = {"ms_per_step": round(el / steps * 1e3, 3), "pairs_per_s": round(a.batch * world * steps / el, 1), "steps": steps,
+               "hipGraph": ("one graph" if world == 1 or not tr.split else "graph | RCCL all-reduce | graph") if use_graph else False,
+               "deterministic": bool(a.deterministic),
+               "workload": "Track4D.backbone train step (fwd + multi-task loss + bwd + grad all-reduce + Adam), B=%d x N=%d per GPU, %d distinct "
+                           "resident batches in rotation" % (a.batch, a.npoints, len(ts)),
+               "allreduce_bytes": tr.reducer.bucket_bytes or 4 * sum(p.numel() for p in net.parameters() if p.requires_grad),
+               "per_rank_ms_per_step": {"min": round(min(per_rank) / steps * 1e3, 3), "max": round(max(per_rank) / steps * 1e3, 3)}}
+    if not full:
+        return res
     # the gradient all-reduce alone (the bucket as the step leaves it), back to back between two HIP events
     ar_us = None
     if world > 1:
@@ -467,7 +493,6 @@ def run_train(a, net, d, dev, dist, world, rank, steps, warmup, live_traffic=Non
             ar1_us = allreduce_1rank_us(sum(p.numel() for p in net.parameters() if p.requires_grad) + 5, dev)
         except Exception:
             ar1_us = None
-    res = None
     if rank == 0:
         ms_step = el / steps * 1e3
         kms, kflops = time_cost_volume_bwd(a.batch, a.npoints, dev)
@@ -492,23 +517,30 @@ def run_train(a, net, d, dev, dist, world, rank, steps, warmup, live_traffic=Non
             kernels = max(counts)
         except Exception:
             pass
-        res = {"ms_per_step": round(ms_step, 3), "pairs_per_s": round(a.batch * world * steps / el, 1), "steps": steps,
-               "hipGraph": ("one graph" if world == 1 or not tr.split else "graph | RCCL all-reduce | graph") if use_graph else False,
-               "deterministic": bool(a.deterministic),
-               "kernels_per_step": kernels,
-               "workload": "Track4D.backbone train step (fwd + multi-task loss + bwd + grad all-reduce + Adam), B=%d x N=%d per GPU, %d distinct "
-                           "resident batches in rotation" % (a.batch, a.npoints, len(ts)),
-               "allreduce_bytes": tr.reducer.bucket_bytes or 4 * sum(p.numel() for p in net.parameters() if p.requires_grad),
-               "allreduce_gradient_bytes": tr.reducer.payload_bytes or 4 * sum(p.numel() for p in net.parameters() if p.grad is not None),
-               "allreduce_us": None if ar_us is None else round(ar_us, 1),
-               "allreduce_us_1rank": None if ar1_us is None else round(ar1_us, 1),
-               "per_rank_ms_per_step": {"min": round(min(per_rank) / steps * 1e3, 3), "max": round(max(per_rank) / steps * 1e3, 3)},
-               "roofline": train_roofline(a, kms, kflops, ach, pm, ms_step),
-               "whole_step": {**_train_total_traffic(a),"hbm_frac_algorithmic_3x": round(3 * ALG_BYTES_PER_PAIR.get(a.npoints, 0) * a.batch / (ms_step * 1e-3)
-                                                               / (HBM_PEAK_GBS * 1e9), 5),
-                              "fp32_frac_algorithmic_3x": round(3 * ALG_FLOPS_PER_PAIR.get(a.npoints, 0) * a.batch / (ms_step * 1e-3)
-                                                                / (FP32_PEAK_TFLOPS * 1e12), 5)}}
+        res.update({"kernels_per_step": kernels,
+                    "allreduce_gradient_bytes": tr.reducer.payload_bytes or 4 * sum(p.numel() for p in net.parameters() if p.grad is not None),
+                    "allreduce_us": None if ar_us is None else round(ar_us, 1),
+                    "allreduce_us_1rank": None if ar1_us is None else round(ar1_us, 1),
+                    "roofline": train_roofline(a, kms, kflops, ach, pm, ms_step),
+                    "whole_step": {**_train_total_traffic(a),"hbm_frac_algorithmic_3x": round(3 * ALG_BYTES_PER_PAIR.get(a.npoints, 0) * a.batch / (ms_step * 1e-3)
+                                                                    / (HBM_PEAK_GBS * 1e9), 5),
+                                   "fp32_frac_algorithmic_3x": round(3 * ALG_FLOPS_PER_PAIR.get(a.npoints, 0) * a.batch / (ms_step * 1e-3)
+                                                                     / (FP32_PEAK_TFLOPS * 1e12), 5)}})
     return res
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: [(name, tensor)] -> PATH/<name>.npy, float32.  Above DUMP_BYTES in all, every array keeps the same fraction of its
+    flattened elements, at positions drawn by a generator seeded with the array's index (the same positions from run to run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = [(k, v.detach().float().cpu().numpy()) for k, v in arrays]
+    total = sum(x.nbytes for _, x in host)
+    for i, (k, x) in enumerate(host):
+        if total > DUMP_BYTES:
+            keep = max(1, x.size * DUMP_BYTES // total)
+            x = x.reshape(-1)[np.sort(np.random.default_rng(i).choice(x.size, keep, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(x, dtype=np.float32))
 
 
 def reduce_times(mine, dist, dev, world):
@@ -520,6 +552,25 @@ def reduce_times(mine, dist, dev, world):
     dist.all_gather(allt, t)
     per_rank = [float(x.item()) for x in allt]
     return max(per_rank), per_rank
+
+
+def headline(a, world, elapsed, spread, depth):
+    """The forward's result line as a plain run prints it: the contract fields of the K timed steps and the configuration."""
+    return {
+        "metric": "radar frame-pairs/sec (backbone forward, eval) at B=%d,N=%d per GPU" % (a.batch, a.npoints),
+        "value": round(a.batch * world * a.steps / elapsed, 1),
+        "unit": "frame-pairs/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(elapsed / a.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": DTYPE, "data": "synthetic",
+        "per_rank_ms_per_step": spread.get("headline"),
+        "timed_region": "EXACTLY `steps` steps between barrier + synchronize, max over ranks, after `warmup` steps and >= 0.5 s of untimed "
+                        "steps; %d distinct resident batches rotate through the steps" % NBATCH,
+        "config": {"workload": "Track4D.backbone forward, B=%d frame-pairs x N=%d points per GPU, S=512 centroids, "
+                               "eval-mode BN, random-init weights, hipGraph=%s, batches in flight=%d"
+                               % (a.batch, a.npoints, not a.no_graph, 1 if a.no_graph else depth),
+                   "global_batch": a.batch * world, "parallelism": "replicas x%d (no collective on the forward path)" % world}}
 
 
 def dry_run(a, world, rank):
@@ -622,27 +673,34 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=64, help="frame-pairs per GPU per step")
     ap.add_argument("--npoints", type=int, default=256, help="radar points per frame")
+    ap.add_argument("--full", action="store_true", help="measure everything besides the headline as well: long window, in-situ and per-kernel "
+                    "rooflines, BASELINE's other configs, the train step, the irregular ops, the CPU baseline (the --no-* options below skip legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the train-step leg of the default (forward) run")
+    ap.add_argument("--no-train", action="store_true", help="skip the train-step leg of the --full forward run")
     ap.add_argument("--no-irregular", action="store_true", help="skip the irregular-op roofline leg")
     ap.add_argument("--no-configs", action="store_true", help="skip the forward legs of BASELINE's other single-GPU configs (B=32 at N=256 / 1024)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured hipGraph")
     ap.add_argument("--pipeline", type=int, default=4, help="captured graphs in flight (batch-level pipelining on streams)")
     ap.add_argument("--train-steps", type=int, default=20)
-    ap.add_argument("--seconds", type=float, default=HEADLINE_SECONDS, help="length of the headline timed region (never fewer than --steps steps)")
-    ap.add_argument("--evidence", default=None, help="rank 0 writes the in-situ event timings of the dominant kernel behind roofline.kernel_ms to "
+    ap.add_argument("--seconds", type=float, default=HEADLINE_SECONDS, help="--full: length of the long window (never fewer than --steps steps)")
+    ap.add_argument("--evidence", default=None, help="--full: rank 0 writes the in-situ event timings of the dominant kernel behind roofline.kernel_ms to "
                     "profiles/<NAME>_insitu_cost_volume.txt")
     ap.add_argument("--graph-collective", action="store_true", help="world > 1: capture the RCCL all-reduce inside the train graph (one graph) "
                                                                      "instead of graph | eager all-reduce | graph")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo run of the distributed control flow with a stand-in step (tests)")
     ap.add_argument("--traffic", choices=["auto", "profiles", "off"], default="auto",
-                    help="roofline.traffic: auto = measure now with two rocprofv3 --pmc child passes when rocprofv3 is present, else take the "
+                    help="--full: roofline.traffic: auto = measure now with two rocprofv3 --pmc child passes when rocprofv3 is present, else take the "
                          "committed profiles/ value (and say so); profiles = always the committed value")
     ap.add_argument("--deterministic", action="store_true", help="train legs: Trainer(deterministic=True) -- order-independent sums, bit-reproducible steps")
     ap.add_argument("--mode", choices=["forward", "train"], default="forward",
-                    help="forward = the headline metric (eval backbone, fused kernels) with the train step embedded as `train`; "
+                    help="forward = the headline metric (eval backbone, fused kernels; --full embeds the train step as `train`); "
                          "train = the train step (BASELINE config 3/4) as the headline line")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.evidence and not a.full:
+        ap.error("--evidence writes a measurement of --full")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         _self_spawn(a)
@@ -691,7 +749,7 @@ def main():
             dist.destroy_process_group()
 
     if a.mode == "train":
-        tr = run_train(a, net, hosts[:4], dev, dist, world, rank, a.steps, a.warmup)
+        tr = run_train(a, net, hosts[:4], dev, dist, world, rank, a.steps, a.warmup, full=a.full, dump=a.dump_outputs)
         res = None
         if rank == 0:
             res = {"metric": "radar frame-pairs/sec (train step) at B=%d,N=%d per GPU" % (a.batch, a.npoints), "value": tr["pairs_per_s"],
@@ -699,12 +757,11 @@ def main():
                    "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
                    "config": {"workload": tr["workload"] + ", hipGraph=%s" % tr["hipGraph"], "global_batch": a.batch * world,
                               "parallelism": "dp%d, one flat RCCL all-reduce of %d bytes per step" % (world, tr["allreduce_bytes"])},
-                   "roofline": tr["roofline"], "whole_step": tr["whole_step"],
-                   "train": {"hipGraph": tr["hipGraph"], "deterministic": tr["deterministic"], "kernels_per_step": tr["kernels_per_step"],
-                             "allreduce_bytes": tr["allreduce_bytes"],
-                             "allreduce_gradient_bytes": tr["allreduce_gradient_bytes"], "allreduce_us": tr["allreduce_us"],
-                             "allreduce_us_1rank": tr["allreduce_us_1rank"]},
+                   "train": {"hipGraph": tr["hipGraph"], "deterministic": tr["deterministic"], "allreduce_bytes": tr["allreduce_bytes"]},
                    "per_rank_ms_per_step": tr["per_rank_ms_per_step"]}
+        if rank == 0 and a.full:
+            res.update(roofline=tr["roofline"], whole_step=tr["whole_step"])
+            res["train"].update({k: tr[k] for k in ("kernels_per_step", "allreduce_gradient_bytes", "allreduce_us", "allreduce_us_1rank")})
             if world == 1 and not a.no_cpu_baseline:
                 try:
                     res["cpu_baseline"] = cpu_train_baseline(min(a.batch, 4), a.npoints)
@@ -718,40 +775,42 @@ def main():
         net.backbone(pc1, pc2, f1, f2, h)
         eng = net._fused
         assert eng, "fused engine not active"
-        # multiply-adds this design executes per step, from the launch shapes of one eager pass (data dependent through the
-        # exhausted-cloud counters, hence measured, not hard-coded)
-        with fused.trace_work() as tw:
+        if a.full:
+            # multiply-adds this design executes per step, from the launch shapes of one eager pass (data dependent through the
+            # exhausted-cloud counters, hence measured, not hard-coded)
+            with fused.trace_work() as tw:
+                net.backbone(pc1, pc2, f1, f2, h)
+            exec_macs, exec_by_kernel = tw.executed_macs()
+            # every launch of one eager pass between two HIP events, one stream, nothing else on the GPU: per kernel family the time
+            # and -- for the FLOP-carrying ones -- the executed rate against the split-path matrix peak
+            from ratrack_amd import _lib as rtk_lib
+            eng.use_side_stream, side_saved = False, eng.use_side_stream
             net.backbone(pc1, pc2, f1, f2, h)
-        exec_macs, exec_by_kernel = tw.executed_macs()
-        # every launch of one eager pass between two HIP events, one stream, nothing else on the GPU: per kernel family the time
-        # and -- for the FLOP-carrying ones -- the executed rate against the split-path matrix peak
-        from ratrack_amd import _lib as rtk_lib
-        eng.use_side_stream, side_saved = False, eng.use_side_stream
-        net.backbone(pc1, pc2, f1, f2, h)
-        torch.cuda.synchronize()
-        fam_of = {"rtk_pointwise_mlp": "pointwise", "rtk_sa_scale": "sa_scale", "rtk_sa_scale_split": "sa_scale", "rtk_cost_volume_split": "cost_volume",
-                  "rtk_cost_volume": "cost_volume", "rtk_patch_cost": "patch_cost", "rtk_gru_step": "gru"}
-        ALONE_PASSES = 7
-        passes = []
-        for _ in range(ALONE_PASSES):      # the MEDIAN over the passes, family by family (round 5 committed one pass: a 155 us outlier in it)
-            rtk_lib.TIMING = timing = []
-            net.backbone(pc1, pc2, f1, f2, h)
-            rtk_lib.TIMING = None
             torch.cuda.synchronize()
-            fam = {}
-            for nm, e0, e1 in timing:
-                f = fam.setdefault(fam_of.get(nm, nm.replace("rtk_", "")), [0, 0.0])
-                f[0] += 1
-                f[1] += e0.elapsed_time(e1) * 1e3
-            passes.append(fam)
-        eng.use_side_stream = side_saved
-        by_family = {k: [passes[0][k][0], statistics.median(p_[k][1] for p_ in passes if k in p_)] for k in passes[0]}
+            fam_of = {"rtk_pointwise_mlp": "pointwise", "rtk_sa_scale": "sa_scale", "rtk_sa_scale_split": "sa_scale", "rtk_cost_volume_split": "cost_volume",
+                      "rtk_cost_volume": "cost_volume", "rtk_patch_cost": "patch_cost", "rtk_gru_step": "gru"}
+            ALONE_PASSES = 7
+            passes = []
+            for _ in range(ALONE_PASSES):      # the MEDIAN over the passes, family by family (round 5 committed one pass: a 155 us outlier in it)
+                rtk_lib.TIMING = timing = []
+                net.backbone(pc1, pc2, f1, f2, h)
+                rtk_lib.TIMING = None
+                torch.cuda.synchronize()
+                fam = {}
+                for nm, e0, e1 in timing:
+                    f = fam.setdefault(fam_of.get(nm, nm.replace("rtk_", "")), [0, 0.0])
+                    f[0] += 1
+                    f[1] += e0.elapsed_time(e1) * 1e3
+                passes.append(fam)
+            eng.use_side_stream = side_saved
+            by_family = {k: [passes[0][k][0], statistics.median(p_[k][1] for p_ in passes if k in p_)] for k in passes[0]}
 
-        spread = {}
+        spread, last = {}, {}
 
         def timed(step, drain, steps, warmup, warm_seconds=0.0, tag=None):
             """`warmup` untimed steps (and, with warm_seconds, as many more as that takes: clocks and caches of a fresh box settle
-            in ~0.5 s, not in the 5-10 steps = 5-10 ms a caller asks for), then EXACTLY `steps` steps between barrier + synchronize."""
+            in ~0.5 s, not in the 5-10 steps = 5-10 ms a caller asks for), then EXACTLY `steps` steps between barrier + synchronize;
+            the return of the last one is kept as last["out"]."""
             def barrier():
                 drain()                                            # every submitted batch finishes inside the timed region
                 if dist is not None:
@@ -766,10 +825,12 @@ def main():
                     drain()
                     torch.cuda.synchronize()
             barrier()
+            rot["i"] = 0                                           # every timed region starts the batch rotation afresh
             t0 = time.perf_counter()
             for _ in range(steps):
-                step()
+                out = step()
             barrier()
+            last["out"] = out
             el, per_rank = reduce_times(time.perf_counter() - t0, dist, dev, world)
             if tag:
                 spread[tag] = {"min": round(min(per_rank) / steps * 1e3, 4), "max": round(max(per_rank) / steps * 1e3, 4), "untimed_warmup_steps": n_w}
@@ -778,20 +839,25 @@ def main():
         depth = max(1, a.pipeline)
         if a.no_graph:
             step_fn, drain_fn = (lambda: net.backbone(*next_batch(), h)), (lambda: None)
-            kstep = timed(step_fn, drain_fn, a.steps, a.warmup, 0.5, "k_steps")
-            # the headline window: the same region over >= HEADLINE_SECONDS (never fewer than the K steps asked for) -- with the driver's
-            # --steps 20 the K-step window is 15 ms, which no clock outside this process resolves
-            timed_steps = max(a.steps, int(a.seconds / max(kstep / a.steps, 1e-6)))
-            elapsed = timed(step_fn, drain_fn, timed_steps, 0, 0.0, "headline")
+        else:
+            pipe = fused.GraphPipeline(eng, (pc1, pc2, f1, f2, h), depth=depth)
+            step_fn, drain_fn = (lambda: pipe.submit(*next_batch(), h)), pipe.drain      # inputs are copied into the slot's static buffers
+        elapsed = timed(step_fn, drain_fn, a.steps, a.warmup, 0.5, "headline")
+        if a.dump_outputs and rank == 0:                # to the host before a later step reuses the output buffers
+            dump_outputs(a.dump_outputs, zip(FORWARD_OUTPUTS, last["out"]))
+    if not a.full:
+        return finish(headline(a, world, elapsed, spread, depth) if rank == 0 else None)
+
+    with torch.no_grad():
+        # the long window: the same region over >= a.seconds (never fewer than the K steps asked for) -- a K = 20 window is 15 ms,
+        # which no clock outside this process resolves
+        long_steps = max(a.steps, int(a.seconds / max(elapsed / a.steps, 1e-6)))
+        long_elapsed = timed(step_fn, drain_fn, long_steps, 0, 0.0, "long_window")
+        if a.no_graph:
             eng.kernel_events = events = []
             insitu = timed(step_fn, drain_fn, a.steps, 2)
             eng.kernel_events = None
         else:
-            pipe = fused.GraphPipeline(eng, (pc1, pc2, f1, f2, h), depth=depth)
-            step_fn = lambda: pipe.submit(*next_batch(), h)      # inputs are copied into the slot's static buffers
-            kstep = timed(step_fn, pipe.drain, a.steps, a.warmup, 0.5, "k_steps")
-            timed_steps = max(a.steps, int(a.seconds / max(kstep / a.steps, 1e-6)))
-            elapsed = timed(step_fn, pipe.drain, timed_steps, 0, 0.0, "headline")
             # second timed region, same workload and concurrency, graphs split around the dominant kernel: its duration in situ
             pipe2 = fused.GraphPipeline(eng, (pc1, pc2, f1, f2, h), depth=depth, split_cost_volume=True)
             events = []
@@ -827,13 +893,13 @@ def main():
                 f.write("%3d  %.4f ms\n" % (k, v))
             f.write("# mean %.4f ms  median %.4f  min %.4f  max %.4f  (n = %d);  alone (nothing else in flight): %.4f ms\n"
                     % (kern_ms, statistics.median(kern_each), min(kern_each), max(kern_each), len(kern_each), alone_ms))
+    live = None
     if rank == 0:
-        pairs_per_s = a.batch * world * timed_steps / elapsed
+        pairs_per_s = a.batch * world * long_steps / long_elapsed
         cv_flops = cost_volume_flops_per_pair(a.npoints) * a.batch
         achieved = cv_flops / (kern_ms * 1e-3) / 1e12
         pm = _pmc("forward", a.batch, a.npoints)
         traffic = {"bytes": pm["traffic_bytes_per_launch"] if pm else None, "source": (pm or {}).get("source")}
-        live = None
         if a.traffic == "auto" and world == 1:
             live = measure_traffic(a.batch, a.npoints)
             if live and live.get("forward"):
@@ -843,24 +909,11 @@ def main():
         prof_us, prof_file = profile_kernel_avg_us("cost_volume_split_kernel<false>" if split else "cost_volume_kernel<") if (a.batch, a.npoints) == (64, 256) else (None, None)
         cv_peak = SPLIT_PEAK_TFLOPS if split else FP32_PEAK_TFLOPS
         exec_flops_per_pair = 2.0 * exec_macs / a.batch
-        res = {
-            "metric": "radar frame-pairs/sec (backbone forward, eval) at B=%d,N=%d per GPU" % (a.batch, a.npoints),
-            "value": round(pairs_per_s, 1),
-            "unit": "frame-pairs/s",
-            "n_gpus": world, "steps": timed_steps, "steps_requested": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(elapsed / timed_steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": DTYPE, "data": "synthetic",
-            "per_rank_ms_per_step": spread.get("headline"),
-            "timed_region": "EXACTLY `steps` steps between barrier + synchronize, max over ranks; steps = max(K asked for, what %g s take): " % a.seconds +
-                            "the K-step window alone is `k_step_window`; %d distinct resident batches rotate through the steps" % NBATCH,
-            "k_step_window": {"steps": a.steps, "ms_per_step": round(kstep / a.steps * 1e3, 4),
-                              "value": round(a.batch * world * a.steps / kstep, 1), "per_rank_ms_per_step": spread.get("k_steps"),
-                              "what": "the first K steps after the warm-up (>= 0.5 s of untimed steps)"},
-            "config": {"workload": "Track4D.backbone forward, B=%d frame-pairs x N=%d points per GPU, S=512 centroids, "
-                                   "eval-mode BN, random-init weights, hipGraph=%s, batches in flight=%d"
-                                   % (a.batch, a.npoints, not a.no_graph, 1 if a.no_graph else depth),
-                       "global_batch": a.batch * world, "parallelism": "replicas x%d (no collective on the forward path)" % world},
+        res = headline(a, world, elapsed, spread, depth)
+        res.update({
+            "long_window": {"steps": long_steps, "ms_per_step": round(long_elapsed / long_steps * 1e3, 4), "value": round(pairs_per_s, 1),
+                            "per_rank_ms_per_step": spread.get("long_window"),
+                            "what": "the headline's timed region again, right after it, over max(K, what %g s take) steps" % a.seconds},
             "roofline": {"kernel": "cost_volume_split_kernel" if split else "cost_volume_kernel", "bound": "mfma",
                          "achieved": round(achieved, 2), "peak": round(cv_peak, 1),
                          "unit": "TFLOP/s", "frac": round(achieved / cv_peak, 4),
@@ -910,13 +963,14 @@ def main():
                                           "frac_of_split_peak": round(2.0 * exec_by_kernel[k] / (v[1] * 1e-6) / 1e12 / SPLIT_PEAK_TFLOPS, 3)}
                                          if k in exec_by_kernel and v[1] > 0 else {}))
                               for k, v in sorted(by_family.items(), key=lambda kv: -kv[1][1])},
-        }
+        })
     # ---- BASELINE.json's other single-GPU forward configurations (config 2: B=32, N=256; config 5: B=32, N=1024) -----------
     if rank == 0 and world == 1 and not a.no_configs and (a.batch, a.npoints) == (64, 256):
         res["configs"] = {}
         for name, (b_, n_) in (("config2_B32_N256", (32, 256)), ("config5_B32_N1024", (32, 1024))):
             try:
-                pipe = pipe2 = None
+                pipe = pipe2 = step_fn = drain_fn = None
+                last.clear()
                 res["configs"][name] = forward_config(net, b_, n_, depth, dev)
             except Exception as e:
                 res["configs"][name] = {"error": repr(e)[:300]}
@@ -925,7 +979,8 @@ def main():
         try:
             # the forward leg's pipelines (eight captured graphs with their private pools, events, streams) are released first: the
             # train leg starts from the allocator state a fresh `--mode train` process has
-            pipe = pipe2 = eng = events = alone = None
+            pipe = pipe2 = step_fn = drain_fn = eng = events = alone = None
+            last.clear()
             net._fused = None
             import gc
             gc.collect()

@@ -81,3 +81,27 @@ def test_round6_evidence_helpers():
                           "print('{\"ok\": 1}')" % ROOT],
                          capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.strip() == '{"ok": 1}', (out.stdout, out.stderr[-500:])
+
+
+def test_dump_outputs_whole_or_seeded_sample(tmp_path):
+    """`--dump-outputs`: one float32 .npy per output, whole below bench.DUMP_BYTES; above it every array is cut to a seeded sample of
+    its elements -- the same positions in every run -- and the files stay within the budget."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    small =[("flow", torch.randn(2, 3, 8, dtype=torch.float64)), ("cls", torch.randn(2, 8))]
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    for k, v in small:
+        a = np.load(tmp_path / "small" / (k + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, v.float().numpy()), k
+    n = bench.DUMP_BYTES // 8 + 1000        # two float32 arrays of n elements: over the budget
+    big = [("a", torch.arange(n, dtype=torch.float32)), ("b", -torch.arange(n, dtype=torch.float32))]
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    total = 0
+    for k, _ in big:
+        x, y = np.load(tmp_path / "x" / (k + ".npy")), np.load(tmp_path / "y" / (k + ".npy"))
+        assert np.array_equal(x, y) and 0 < x.size < n, k
+        total += x.nbytes
+    assert total <= bench.DUMP_BYTES

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round 5: board power and shader clock while the pipelined forward runs (is the launch power-limited?).
 # usage (GPU box): bash tools/experiments/smi_during_bench.sh > gpurun_out/r05/smi_during_bench.txt
-python bench.py --no-cpu-baseline --no-train --no-configs --traffic off --seconds 15 > /tmp/smi_bench.json 2>/tmp/smi_bench.err &
+python bench.py --full --no-cpu-baseline --no-train --no-configs --traffic off --seconds 15 > /tmp/smi_bench.json 2>/tmp/smi_bench.err &
 BP=$!
 sleep 2
 for i in $(seq 1 80); do
