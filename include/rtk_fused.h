@@ -287,6 +287,66 @@ RTK_EXPORT int rtk_log_sinkhorn(int m, int n, const float *scores, float alpha, 
 RTK_EXPORT int rtk_dbscan(int n, const float *feat, int pitch, const int *channels, const float *score, float threshold, double eps,
                           int min_samples, int *labels, rtk_stream_t stream);
 
+/* ---- Batched tracking (ratrack_amd/tracker.py): B independent sequences, one launch per stage per frame -------------------------
+ * Detection and association of the post-backbone half of Track4D.forward for every stream of a batch at once, without a host round
+ * trip.  Per stream b: K = max_objects object slots; objects are numbered in the reference's order (by their first member point).
+ * Descriptors are the 141-d vectors of association.object_descriptor:
+ *   [centre(3) | var xyz(3) | max prop(128) | mean flow(3) | mean (RCS, v_r)(2) | var (RCS, v_r)(2)]. */
+#define RTK_DESC 141
+
+/* Element (b, c, p) of a (B, C, N) tensor at ptr[b * sb + c * sc + p * sp] (strides in floats): the backbone's outputs are
+ * permuted views of point-major buffers and are read in place. */
+typedef struct {
+    const float *ptr;
+    long long sb, sc, sp;
+} rtk_bcn_view_t;
+
+/* One frame of the batch: pc1 (B,3,N), flow (B,3,N), feature1 (B,2,N) = (RCS, v_r), prop (B,128,N), cls (B,1,N) (sc unused). */
+typedef struct {
+    int B, N;
+    rtk_bcn_view_t pc1, flow, feature1, prop, cls;
+    const int *n_valid;            /* (B) DEVICE: frame-1 point counts (row 0 of a padded batch's n_valid), or NULL: N points */
+    const unsigned char *active;   /* (B) DEVICE: 0 = the stream sits this frame out, or NULL: every stream is active */
+} rtk_track_frame_t;
+
+/* rtk_dbscan_batched: mover selection (cls > threshold over the stream's n_valid columns) + DBSCAN on the channels
+ * (xyz, flow, v_r, prop[0]), per stream, labels identical to rtk_dbscan.  Outputs: labels (B,N) cluster ids (-1: noise, non-mover,
+ * padding or inactive), obj (B,N) object index in reference order (-1: none), num_objects (B) = min(objects, K), flags (B):
+ * bit 0 = more than K objects (objects K.. are not reported), bit 1 = n_valid outside [0, N] (clamped).  Tables of a stream live
+ * in LDS when they fit 128 KiB, else in its slice of `work` (B * N * RTK_DBSCAN_POINT_BYTES bytes; may be NULL when every table
+ * fits).  One workgroup per stream. */
+#define RTK_DBSCAN_POINT_BYTES 48
+RTK_EXPORT int rtk_dbscan_batched(const rtk_track_frame_t *frame, float threshold, double eps, int min_samples, int K, int *labels,
+                                  int *obj, int *num_objects, int *flags, void *work, long long work_bytes, rtk_stream_t stream);
+
+/* rtk_object_descriptors: desc (B,K,141) of every object of every active stream (points in index order; two-pass population
+ * variance).  Inactive streams carry their previous descriptors over: desc[b][:prev_count[b]] = desc_prev[b][:prev_count[b]]. */
+RTK_EXPORT int rtk_object_descriptors(const rtk_track_frame_t *frame, int K, const int *obj, const int *num_objects,
+                                      const int *prev_count, const float *desc_prev, float *desc, rtk_stream_t stream);
+
+/* rtk_affinity_pairs: the Affinity MLP 141 -> 564 -> 282 -> 70 -> 35 -> 1 (ReLU, then sigmoid) on desc[b][j] - desc_prev[b][i]
+ * for the live pairs i < m_b (previous objects; 0 on a reset stream), j < num_objects[b] only: aff[b][i][j] (B,K,K).
+ * weights: packed by RTK_AFFINITY_WEIGHTS floats = for each layer its transposed weight (Cin, Cout) then its bias (Cout). */
+#define RTK_AFFINITY_WEIGHTS (141 * 564 + 564 + 564 * 282 + 282 + 282 * 70 + 70 + 70 * 35 + 35 + 35 + 1)
+RTK_EXPORT int rtk_affinity_pairs(int B, int K, const float *weights, const float *desc_prev, const int *prev_count,
+                                  const unsigned char *reset, const float *desc, const int *num_objects, float *aff,
+                                  rtk_stream_t stream);
+
+/* rtk_associate_batched: per stream, the log-Sinkhorn of rtk_log_sinkhorn (same arithmetic; `iters` iterations, dustbin `alpha`)
+ * on its live (m_b, n_b) block of aff, the mutual-best assignment (exact ties: the LOWEST index wins), the track IDs
+ * (fresh from counter[b] in current-object order when unmatched or aff < 0.01, else the previous object's ID with conf = aff) and
+ * point_track_id (B,N).  Writes object_ids / object_conf / indices1 (B,K) (-1 / 0 / -1 past num_objects), num_prev (B) = m_b,
+ * counter (B) in place, and the next state ids (B,K), count (B).  Inactive streams: ids = prev_ids, count = prev_count, no objects.
+ * scores: NULL, or (B, K+1, K+1): each stream's whole (m_b+1, n_b+1) Sinkhorn output (rtk_log_sinkhorn's `out`, row stride K+1).
+ * One workgroup per stream; its LDS holds the (K+1) x (K+1) table (about 66 KiB at K = 128). */
+RTK_EXPORT int rtk_associate_batched(int B, int N, int K, const unsigned char *active, const unsigned char *reset, const float *aff,
+                                     const int *num_objects, const int *obj, const int *prev_ids, const int *prev_count, float alpha,
+                                     int iters, int *counter, int *ids, int *count, int *object_ids, float *object_conf, int *indices1,
+                                     int *num_prev, int *point_track_id, float *scores, rtk_stream_t stream);
+
+/* The largest K (max_objects) the batched association accepts: its per-stream table must fit one workgroup's LDS. */
+RTK_EXPORT int rtk_track_max_objects(void);
+
 #ifdef __cplusplus
 }
 #endif

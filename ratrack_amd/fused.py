@@ -63,6 +63,12 @@ _lib.SIGNATURES.update({
     "rtk_to_channel_major_multi": [_ci] * 3 + [_vp, _vp],
     "rtk_log_sinkhorn": [_ci, _ci, _vp, ctypes.c_float, _ci, _vp, _vp],
     "rtk_dbscan": [_ci, _vp, _ci, _vp, _vp, ctypes.c_float, ctypes.c_double, _ci, _vp, _vp],
+    # batched tracking (ratrack_amd/tracker.py); the frame struct is rtk_track_frame_t (tracker.TrackFrame)
+    "rtk_dbscan_batched": [_vp, ctypes.c_float, ctypes.c_double, _ci, _ci, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp],
+    "rtk_object_descriptors": [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rtk_affinity_pairs": [_ci, _ci] + [_vp] * 7 + [_vp],
+    "rtk_associate_batched": [_ci] * 3 + [_vp] * 7 + [ctypes.c_float, _ci] + [_vp] * 9 + [_vp],
+    "rtk_track_max_objects": [],
 })
 
 

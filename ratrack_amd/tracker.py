@@ -1,0 +1,289 @@
+"""Many sequences at once: B independent radar sequences tracked in lockstep, one batched step per frame.
+
+    trk = BatchedTracker(net, streams=B, max_objects=128)      # net: an eval-mode Track4D; the Affinity weights are read here
+    out = trk.step(pc1, pc2, feature1, feature2, n_valid=None, reset=None, active=None)
+
+Per stream, `step()` computes what `Track4D.forward` computes for that stream run alone (models/track4d.py:49-65): the backbone on
+the fused engine for the whole batch, then detection and association as four HIP launches for the whole batch
+(csrc/track_batched.hip) -- no host synchronisation between the backbone and the track IDs.  State between steps (h, the previous
+objects' descriptors, IDs and count, the next-ID counter) lives on the device; this frame's descriptors and IDs become the previous
+ones by a buffer swap.
+
+  * reset (B,) bool: the reference's is_new_seq (main_utils.py:70-74): the stream's h goes to zero and its previous objects are
+    dropped; its ID counter keeps counting (the reference's max_id across clips).
+  * active (B,) bool: a stream that sits the frame out keeps h, previous objects and counter exactly as they were and reports no
+    objects (clips of different lengths).  reset only acts on an active stream.
+
+Outputs stay on the device; `StepResult.objects(b)`, `aff_mat(b)`, `indices1(b)` and `BatchedTracker.write_results` synchronise
+when they are called.  More than `max_objects` objects in a stream is an error, never a truncation: the kernels flag it on the
+device and `objects`, `write_results` and `check()` raise.
+"""
+import ctypes
+import os
+
+import torch
+
+from . import _lib
+from . import fused  # noqa: F401  (registers the signatures of include/rtk_fused.h)
+
+DESC = 141
+DBSCAN_POINT_BYTES = 48          # RTK_DBSCAN_POINT_BYTES
+DBSCAN_LDS_BYTES = 128 * 1024
+_FLAG_OVERFLOW, _FLAG_NVALID = 1, 2
+
+
+class _View(ctypes.Structure):
+    _fields_ = [("ptr", ctypes.c_void_p), ("sb", ctypes.c_longlong), ("sc", ctypes.c_longlong), ("sp", ctypes.c_longlong)]
+
+
+class TrackFrame(ctypes.Structure):
+    """rtk_track_frame_t."""
+    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("pc1", _View), ("flow", _View), ("feature1", _View), ("prop", _View),
+                ("cls", _View), ("n_valid", ctypes.c_void_p), ("active", ctypes.c_void_p)]
+
+
+def _view(t):
+    """(B,C,N) or (B,N) fp32 CUDA tensor, any strides -> rtk_bcn_view_t (read in place: no copy)."""
+    assert t.is_cuda and t.dtype == torch.float32, (t.device, t.dtype)
+    if t.dim() == 2:
+        return _View(t.data_ptr(), t.stride(0), 0, t.stride(1))
+    return _View(t.data_ptr(), t.stride(0), t.stride(1), t.stride(2))
+
+
+def max_objects_limit():
+    """The largest max_objects the batched association accepts (its per-stream table in one workgroup's LDS)."""
+    return _lib.load().rtk_track_max_objects()
+
+
+def pack_affinity(affinity):
+    """Affinity.affinity (Linear 141-564-282-70-35-1) -> the packed fp32 image of rtk_affinity_pairs: per layer W^T (Cin, Cout), b."""
+    lins = [m for m in affinity.affinity if isinstance(m, torch.nn.Linear)]
+    dims = [(l.in_features, l.out_features) for l in lins]
+    if dims != [(141, 564), (564, 282), (282, 70), (70, 35), (35, 1)]:
+        raise ValueError("rtk_affinity_pairs is built for the 141-564-282-70-35-1 Affinity MLP, got %s" % (dims,))
+    parts = []
+    for l in lins:
+        parts += [l.weight.detach().float().t().reshape(-1), l.bias.detach().float().reshape(-1)]
+    return torch.cat(parts).contiguous()
+
+
+def _mask(x, B, default, dev):
+    if x is None:
+        return torch.full((B,), int(default), dtype=torch.uint8, device=dev)
+    t = torch.as_tensor(x).to(device=dev).reshape(-1)
+    if t.numel() != B:
+        raise ValueError("a per-stream mask needs %d entries, got %d" % (B, t.numel()))
+    return (t != 0).to(torch.uint8)
+
+
+def check_n_valid(n_valid, N):
+    """Host-side sizes check of a (2,B) n_valid (a device tensor is checked by the kernels: flag -> check() raises)."""
+    if n_valid is not None and not (torch.is_tensor(n_valid) and n_valid.is_cuda):
+        nv = torch.as_tensor(n_valid)
+        if nv.dim() != 2 or nv.shape[0] != 2:
+            raise ValueError("n_valid must be (2, B), got %s" % (tuple(nv.shape),))
+        if bool((nv > N).any()) or bool((nv < 0).any()):
+            raise ValueError("n_valid %s outside [0, N=%d]" % (nv.tolist(), N))
+
+
+class StepResult:
+    """One step's outputs (device tensors): flow (B,3,N), cls (B,N), h (5,B,128), point_track_id (B,N) int32, num_objects (B,),
+    object_ids / object_conf (B,K), aff (B,K,K) (only [:m_b, :n_b] meaningful), indices1() (B,K) int32 (-1: no match)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def indices1(self, b=None):
+        """b None: the (B,K) int32 device tensor.  b: the reference's indices1 of stream b, (1,n_b) int64, or None when there was
+        nothing to associate (no previous or no current objects), as Track4D.forward returns it."""
+        if b is None:
+            return self._indices1
+        m, n = self._sizes(b)
+        if m == 0 or n == 0:
+            return None
+        return self._indices1[b, :n].long().unsqueeze(0)
+
+    def _host(self):
+        if self._cache is None:
+            self._cache = dict(num=self.num_objects.cpu().tolist(), prev=self.num_prev.cpu().tolist(), flags=self.flags.cpu().tolist(),
+                               active=self.active.cpu().tolist())
+        return self._cache
+
+    def _sizes(self, b):
+        h = self._host()
+        return h["prev"][b], h["num"][b]
+
+    def check(self):
+        raise_on_flags(self._host()["flags"], self.max_objects)
+
+    def aff_mat(self, b):
+        """(1, m_b, n_b) affinities of stream b (previous x current), as Track4D.forward returns them."""
+        m, n = self._sizes(b)
+        if m == 0 or n == 0:
+            return torch.zeros(1, m, n, device=self.aff.device)
+        return self.aff[b, :m, :n].unsqueeze(0)
+
+    def objects(self, b):
+        """(objects, confs) of stream b in the structure of Track4D.forward: {track id: (1,139,n_i) tensor} in association order,
+        confs aligned with it (0 for a fresh track, the 0-dim affinity tensor for an inherited one)."""
+        raise_on_flags(self._host()["flags"], self.max_objects, only=b)
+        m, n = self._sizes(b)
+        if n == 0:
+            return dict(), []
+        ids = self.object_ids[b, :n].cpu().tolist()
+        idx = self._indices1[b, :n].cpu().tolist()
+        conf = self.object_conf[b, :n].cpu().tolist()
+        N = self.pc1.shape[2]
+        pf = torch.cat((self.pc1[b] + self.flow[b], self.pc1[b], self.flow[b], self.feature1[b], self.prop[b]), dim=0)   # (139, N)
+        obj = self.obj[b].long()
+        order = torch.argsort(obj * N + torch.arange(N, device=obj.device))       # objects in order, points in column order inside
+        sizes = torch.bincount(obj[obj >= 0], minlength=n).cpu().tolist()
+        npts = sum(sizes)
+        order = order[N - npts:]                                                   # (the -1 keys sort first)
+        parts = torch.split(pf.index_select(1, order).unsqueeze(0), sizes, dim=2)
+        objects, confs = dict(), []
+        for j in range(n):
+            objects[ids[j]] = parts[j]
+            confs.append(0 if conf[j] == 0.0 else self.aff[b, idx[j], j])      # an inherited ID has conf >= 0.01
+        return objects, confs
+
+
+def raise_on_flags(flags, K, only=None):
+    for b, f in enumerate(flags):
+        if only is not None and b != only:
+            continue
+        if f & _FLAG_OVERFLOW:
+            raise RuntimeError("BatchedTracker: stream %d has more than max_objects=%d objects (raise max_objects)" % (b, K))
+        if f & _FLAG_NVALID:
+            raise RuntimeError("BatchedTracker: stream %d has an n_valid outside [0, N]" % b)
+
+
+class BatchedTracker:
+    """Tracks `streams` independent sequences in lockstep (see the module docstring)."""
+
+    def __init__(self, net, streams, max_objects=128, iters=500, alpha=0.9, eps=1.5, threshold=0.5):
+        if net.training:
+            raise ValueError("BatchedTracker runs the eval-mode (fused) backbone: call net.eval() first")
+        kmax = max_objects_limit()
+        if not 1 <= max_objects <= kmax:
+            raise ValueError("max_objects=%d outside [1, %d] (the per-stream association table must fit one workgroup's LDS)"
+                             % (max_objects, kmax))
+        self.net, self.B, self.K = net, int(streams), int(max_objects)
+        self.iters, self.alpha, self.eps, self.threshold = int(iters), float(alpha), float(eps), float(threshold)
+        self.min_samples = int(net.min_obj_points)
+        dev = next(net.parameters()).device
+        self.dev = dev
+        self.weights = pack_affinity(net.affinity).to(dev)
+        B, K = self.B, self.K
+        self.h = torch.zeros(5, B, 128, device=dev)
+        self.desc = torch.zeros(2, B, K, DESC, device=dev)          # double-buffered: [cur] written, [1 - cur] = previous objects
+        self.ids = torch.full((2, B, K), -1, dtype=torch.int32, device=dev)
+        self.count = torch.zeros(2, B, dtype=torch.int32, device=dev)
+        self.counter = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.cur = 0
+        self._work = None
+        self.last = None
+
+    # ---- one frame --------------------------------------------------------------------------------
+    def step(self, pc1, pc2, feature1, feature2, n_valid=None, reset=None, active=None):
+        B, _, N = pc1.shape
+        if B != self.B or pc2.shape[2] != N:
+            raise ValueError("step(): expected (%d,3,N) clouds of one padded size, got %s and %s" % (self.B, tuple(pc1.shape), tuple(pc2.shape)))
+        check_n_valid(n_valid, N)
+        dev = self.dev
+        reset_d, active_d = _mask(reset, B, False, dev), _mask(active, B, True, dev)
+        nv = None if n_valid is None else torch.as_tensor(n_valid).to(device=dev, dtype=torch.int32).reshape(2, B).contiguous()
+        keep = (active_d != 0).view(1, B, 1)
+        h_in = torch.where((reset_d != 0).view(1, B, 1), 0.0, self.h)
+        with torch.no_grad():
+            flow, h_out, cls, _, _, _, prop = self.net._fused_engine().backbone(pc1, pc2, feature1, feature2, h_in, n_valid=nv)
+        self.h = torch.where(keep, h_out, self.h)
+        return self.associate(pc1, feature1, flow, cls, prop, nv, reset_d, active_d)
+
+    def associate(self, pc1, feature1, flow, cls, prop, n_valid, reset, active):
+        """The post-backbone half of step(): four launches, the state swap; no host synchronisation.  reset / active (B,) uint8 and
+        n_valid (2,B) int32 (or None) are device tensors."""
+        B, K = self.B, self.K
+        N = pc1.shape[2]
+        dev = self.dev
+        st = torch.cuda.current_stream().cuda_stream
+        cur, prev = self.cur, 1 - self.cur
+        i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
+        labels, obj, num, flags = i32(B, N), i32(B, N), i32(B), i32(B)
+        fr = TrackFrame(B, N, _view(pc1), _view(flow), _view(feature1), _view(prop), _view(cls),
+                        None if n_valid is None else n_valid.data_ptr(), active.data_ptr())
+        need = N * DBSCAN_POINT_BYTES
+        work, work_bytes = None, 0
+        if need > DBSCAN_LDS_BYTES:        # a stream whose tables exceed the LDS clusters in its slice of this workspace
+            if self._work is None or self._work.numel() < B * need:
+                self._work = torch.empty(B * need, dtype=torch.uint8, device=dev)
+            work, work_bytes = self._work.data_ptr(), self._work.numel()
+        _lib.call("rtk_dbscan_batched", ctypes.addressof(fr), self.threshold, self.eps, self.min_samples, K, labels.data_ptr(),
+                  obj.data_ptr(), num.data_ptr(), flags.data_ptr(), work, work_bytes, st)
+        desc_prev, desc = self.desc[prev], self.desc[cur]
+        _lib.call("rtk_object_descriptors", ctypes.addressof(fr), K, obj.data_ptr(), num.data_ptr(), self.count[prev].data_ptr(),
+                  desc_prev.data_ptr(), desc.data_ptr(), st)
+        aff = torch.empty(B, K, K, device=dev)
+        _lib.call("rtk_affinity_pairs", B, K, self.weights.data_ptr(), desc_prev.data_ptr(), self.count[prev].data_ptr(), reset.data_ptr(),
+                  desc.data_ptr(), num.data_ptr(), aff.data_ptr(), st)
+        object_ids, object_conf, indices1, num_prev, point_track_id = i32(B, K), torch.empty(B, K, device=dev), i32(B, K), i32(B), i32(B, N)
+        _lib.call("rtk_associate_batched", B, N, K, active.data_ptr(), reset.data_ptr(), aff.data_ptr(), num.data_ptr(), obj.data_ptr(),
+                  self.ids[prev].data_ptr(), self.count[prev].data_ptr(), self.alpha, self.iters, self.counter.data_ptr(),
+                  self.ids[cur].data_ptr(), self.count[cur].data_ptr(), object_ids.data_ptr(), object_conf.data_ptr(), indices1.data_ptr(),
+                  num_prev.data_ptr(), point_track_id.data_ptr(), None, st)
+        self.cur = prev                    # this frame's objects are the next frame's previous objects: a swap, not a copy
+        out = StepResult(flow=flow, cls=cls, h=self.h, point_track_id=point_track_id, num_objects=num, object_ids=object_ids,
+                         object_conf=object_conf, _indices1=indices1, aff=aff, num_prev=num_prev, flags=flags, labels=labels, obj=obj,
+                         descriptors=desc, active=active, pc1=pc1, feature1=feature1, prop=prop, max_objects=K, _cache=None)
+        self.last = out
+        return out
+
+    def check(self, out=None):
+        """Raises RuntimeError naming the stream if the last step (or `out`) overflowed max_objects or had a bad n_valid."""
+        out = out if out is not None else self.last
+        if out is not None:
+            out.check()
+
+    # ---- result files ------------------------------------------------------------------------------
+    def write_results(self, root, seqs, indices, out):
+        """One result file per active stream, <root>/<seqs[b]>/<indices[b]:05d>.txt, byte-identical to
+        vod_io.write_track_results(root, seqs[b], indices[b], *out.objects(b)); one device->host copy for the whole batch.
+        Returns the paths written."""
+        B, K = self.B, self.K
+        N = out.pc1.shape[2]
+        pc1 = out.pc1.float()
+        flat = [out.num_objects, out.flags, out.active.to(torch.int32), out.object_ids.reshape(-1), out.object_conf.reshape(-1).view(torch.int32),
+                out.obj.reshape(-1), pc1.contiguous().reshape(-1).view(torch.int32)]
+        host = torch.cat([t.reshape(-1) for t in flat]).cpu()
+        o = 0
+
+        def take(count):
+            nonlocal o
+            r = host[o:o + count]
+            o += count
+            return r
+        num, flags, act = take(B).tolist(), take(B).tolist(), take(B).tolist()
+        ids, conf = take(B * K).view(B, K), take(B * K).view(torch.float32).view(B, K)
+        obj, xyz = take(B * N).view(B, N), take(B * 3 * N).view(torch.float32).view(B, 3, N)
+        raise_on_flags([f if a else 0 for f, a in zip(flags, act)], K)
+        paths = []
+        for b in range(B):
+            if not act[b]:
+                continue
+            d = os.path.join(root, str(seqs[b]))
+            os.makedirs(d, exist_ok=True)
+            path = os.path.join(d, str(int(indices[b])).zfill(5) + ".txt")
+            ob = obj[b].tolist()
+            members = [[] for _ in range(num[b])]
+            for p, k in enumerate(ob):
+                if k >= 0:
+                    members[k].append(p)
+            xb = xyz[b].numpy()
+            with open(path, "w+") as f:
+                for j in range(num[b]):
+                    parts = ["NA", "1", "-1", "-1", str(float(conf[b, j])), str(int(ids[b, j]))]
+                    for p in members[j]:
+                        parts += [str(float(xb[0, p])), str(float(xb[1, p])), str(float(xb[2, p]))]
+                    f.write(" ".join(parts) + "\n")
+            paths.append(path)
+        return paths
