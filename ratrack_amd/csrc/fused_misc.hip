@@ -375,31 +375,16 @@ extern "C" int rtk_gru_step_bwd(int b, int layers, int hidden, const float *x, c
 // (log_optimal_transport / log_sinkhorn_iterations, models/utils/track4d_utils.py:405-434) in ONE launch.
 // The reference issues ~8 framework kernels per iteration on an (m+1) x (n+1) matrix of a few hundred entries: 4000
 // launches, 40-90 ms per radar frame -- of a 100 ms frame period.  Here one workgroup keeps the score matrix with its
-// dustbin row / column in LDS and alternates row and column log-sum-exp passes (thread = row, then thread = column).
-//   couplings = [[scores, alpha], [alpha, alpha]],  norm = -log(m + n),
-//   log_mu = (norm, ..., norm, log n + norm),  log_nu = (norm, ..., norm, log m + norm),  u = v = 0
-//   iters x { u = log_mu - lse_j(Z + v);  v = log_nu - lse_i(Z + u) };   out = Z + u + v - norm
-// logsumexp is evaluated as torch does: max + log(sum(exp(x - max))) (tree-summed across the lanes of a wave).
+// dustbin row / column in LDS and alternates row and column log-sum-exp passes (log_ot_lds, assoc_common.h); out = the whole
+// (m+1) x (n+1) plan.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void log_sinkhorn_kernel(int m, int n, const float *__restrict__ scores, float alpha, int iters,
                                                            float *__restrict__ out) {
     extern __shared__ float s_mem[];
     const int R = m + 1, C = n + 1, ld = C | 1;           // odd row stride: the column pass walks down a column conflict-free
     float *Z = s_mem, *u = Z + R * ld, *v = u + R;
-    const int t = threadIdx.x;
-    for (int e = t; e < R * C; e += 256) {
-        const int i = e / C, j = e % C;
-        Z[i * ld + j] = (i < m && j < n) ? scores[i * n + j] : alpha;
-    }
-    for (int e = t; e < R; e += 256) u[e] = 0.f;
-    for (int e = t; e < C; e += 256) v[e] = 0.f;
-    const float norm = -logf((float)m + (float)n);
-    __syncthreads();
-    log_sinkhorn_lds(m, n, Z, ld, u, v, norm, iters);
-    for (int e = t; e < R * C; e += 256) {
-        const int i = e / C, j = e % C;
-        out[e] = Z[i * ld + j] + u[i] + v[j] - norm;
-    }
+    const float norm = log_ot_lds(m, n, scores, n, alpha, iters, Z, ld, u, v);
+    for (int e = threadIdx.x; e < R * C; e += 256) out[e] = log_ot_plan(Z, ld, u, v, norm, e / C, e % C);
 }
 
 extern "C" int rtk_log_sinkhorn(int m, int n, const float *scores, float alpha, int iters, float *out, rtk_stream_t stream) {
@@ -412,16 +397,8 @@ extern "C" int rtk_log_sinkhorn(int m, int n, const float *scores, float alpha, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// rtk_dbscan: clustering of the moving points (models/track4d.py:108-126: sklearn.cluster.DBSCAN(eps, min_samples) on the
-// host, behind a device->host copy of the features and a boolean-mask gather).  One workgroup:
-//   1. ordered compaction of the movers (score > threshold) and their D feature channels into LDS;
-//   2. core points: closed eps-ball (itself included) holds >= min_samples movers.  Distances in float64 with numpy's
-//      pairwise summation order, sqrt(d2) <= eps -- the arithmetic of ratrack_amd/association.dbscan;
-//   3. connected components of the core points under the eps-graph by min-label propagation with pointer jumping;
-//   4. sklearn numbers clusters in order of their first core point and fully expands one cluster before starting the next,
-//      so: cluster id = rank of the component's smallest core index; a border point (non-core, within eps of a core
-//      point; only possible for min_samples > 2) joins the lowest-numbered cluster among its core neighbours; the rest is
-//      noise (-1).
+// rtk_dbscan: clustering of the moving points (score > threshold) in one workgroup: dbscan_workgroup (assoc_common.h) on the
+// channels feat[channels[c] * pitch + i].  Tables: f (n,8) | src | lab | aux, 44 B per point.
 // labels (n) int32: cluster id of every INPUT point, -1 for noise and for non-movers.
 // ------------------------------------------------------------------------------------------------
 // WORK = false: the tables live in LDS (clouds up to ~2900 points: every real frame).  WORK = true: the same single workgroup on a
@@ -432,83 +409,16 @@ __global__ __launch_bounds__(256) void dbscan_kernel(int n, const float *__restr
                                                      const float *__restrict__ score, float thr, double eps, int min_samples,
                                                      int *__restrict__ labels, unsigned char *__restrict__ work) {
     extern __shared__ __attribute__((aligned(16))) unsigned char db_smem[];
-    float *f = WORK ? reinterpret_cast<float *>(work) : reinterpret_cast<float *>(db_smem);                 // (m, 8) compacted features
-    int *src = reinterpret_cast<int *>(f + (size_t)n * DB_D);      // mover -> input index
-    int *lab = src + n;                                            // component label (smallest core index) or INT_MAX
-    int *aux = lab + n;                                            // core flag, then cluster number of a representative
-    __shared__ int s_m, s_changed, s_wave[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    // ---- 1. ordered compaction ----------------------------------------------------------------------------------------
-    if (t == 0) s_m = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 256) {
-        const int i = base + t;
-        const bool mv = i < n && score[i] > thr;
-        const unsigned long long bal = __ballot(mv);
-        if (lane == 0) s_wave[wave] = __popcll(bal);
-        __syncthreads();
-        int off = s_m;
-        for (int w = 0; w < wave; ++w) off += s_wave[w];
-        if (mv) {
-            const int k = off + __popcll(bal & ((1ull << lane) - 1ull));
-            src[k] = i;
+    float *f = WORK ? reinterpret_cast<float *>(work) : reinterpret_cast<float *>(db_smem);
+    int *src = reinterpret_cast<int *>(f + (size_t)n * DB_D), *lab = src + n, *aux = lab + n;
+    for (int i = threadIdx.x; i < n; i += 256) labels[i] = -1;
+    dbscan_workgroup(n, f, src, lab, aux, eps, min_samples,
+        [&](int i) { return score[i] > thr; },
+        [&](int i, float *fk) {
 #pragma unroll
-            for (int c = 0; c < DB_D; ++c) f[k * DB_D + c] = feat[(size_t)chan[c] * pitch + i];
-        }
-        __syncthreads();
-        if (t == 0) s_m += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
-    }
-    const int m = s_m;
-    for (int i = t; i < n; i += 256) labels[i] = -1;
-    // ---- 2. core points -----------------------------------------------------------------------------------------------
-    for (int i = t; i < m; i += 256) {
-        int cnt = 0;
-        for (int j = 0; j < m; ++j) cnt += db_adjacent(f, i, j, eps) ? 1 : 0;
-        aux[i] = cnt >= min_samples;
-        lab[i] = cnt >= min_samples ? i : 0x7fffffff;
-    }
-    __syncthreads();
-    // ---- 3. components of the core graph ----------------------------------------------------------------------------------
-    for (;;) {
-        if (t == 0) s_changed = 0;
-        __syncthreads();
-        for (int i = t; i < m; i += 256) {
-            if (!aux[i]) continue;
-            int best = lab[i];
-            for (int j = 0; j < m; ++j)
-                if (aux[j] && lab[j] < best && db_adjacent(f, i, j, eps)) best = lab[j];
-            if (best < lab[i]) { lab[i] = best; s_changed = 1; }       // racy reads of lab[j] only ever see smaller, valid labels
-        }
-        __syncthreads();
-        for (int i = t; i < m; i += 256)                               // pointer jumping: label of my label
-            if (aux[i]) { const int l = lab[lab[i]]; if (l < lab[i]) lab[i] = l; }
-        __syncthreads();
-        if (!s_changed) break;
-        __syncthreads();
-    }
-    // ---- 4. cluster numbers, border points, output -------------------------------------------------------------------------
-    for (int i = t; i < m; i += 256) {           // representative i (lab[i] == i): its number = representatives before it
-        if (aux[i] && lab[i] == i) {
-            int r = 0;
-            for (int j = 0; j < i; ++j) r += (aux[j] && lab[j] == j) ? 1 : 0;
-            aux[i] = 2 + r;                      // >= 2 marks "core + number"; plain core points keep 1
-        }
-    }
-    __syncthreads();
-    for (int i = t; i < m; i += 256) {
-        int out = -1;
-        if (aux[i]) {
-            out = aux[lab[i]] - 2;
-        } else if (min_samples > 2) {
-            for (int j = 0; j < m; ++j)
-                if (aux[j] && db_adjacent(f, i, j, eps)) {
-                    const int c = aux[lab[j]] - 2;
-                    out = (out < 0 || c < out) ? c : out;
-                }
-        }
-        labels[src[i]] = out;
-    }
+            for (int c = 0; c < DB_D; ++c) fk[c] = feat[(size_t)chan[c] * pitch + i];
+        },
+        [&](int, int s, int c) { labels[s] = c; });
 }
 
 extern "C" int rtk_dbscan(int n, const float *feat, int pitch, const int *channels, const float *score, float threshold, double eps,

@@ -1,12 +1,14 @@
 // track_batched.hip -- the post-backbone half of Track4D.forward (detection + association, models/track4d.py:53-65,108-223) for B
 // independent streams at once: four launches per frame whatever B is, no host round trip (ratrack_amd/tracker.py).
 //
-//   rtk_dbscan_batched      one workgroup per stream: mover selection + DBSCAN (the arithmetic of rtk_dbscan) + the objects'
+//   rtk_dbscan_batched      one workgroup per stream: mover selection + DBSCAN (dbscan_workgroup, rtk_dbscan's) + the objects'
 //                           reference order (by first member point)
 //   rtk_object_descriptors  (stream, object-slot) workgroups: the 141-d descriptor of every object
 //   rtk_affinity_pairs      (stream, pair-tile) workgroups: the Affinity MLP on the live m_b x n_b descriptor differences
-//   rtk_associate_batched   one workgroup per stream: log-Sinkhorn (the arithmetic of rtk_log_sinkhorn), mutual best match,
+//   rtk_associate_batched   one workgroup per stream: log-Sinkhorn (log_ot_lds, rtk_log_sinkhorn's), mutual best match,
 //                           track IDs, point_track_id
+//
+// The DBSCAN and log-OT code lives in assoc_common.h, shared with the B = 1 kernels of fused_misc.hip.
 //
 // Every stream's counts (n_valid, movers, objects, previous objects) stay on the device; the tables are sized for N points / K
 // object slots and only the live part is touched.
@@ -30,107 +32,28 @@ __device__ __forceinline__ int stream_points(const rtk_track_frame_t &fr, int b)
     return n < 0 ? 0 : (n > fr.N ? fr.N : n);
 }
 
-// Ordered compaction over a 256-thread workgroup: the threads with `keep` get consecutive slots in thread order.  Returns the
-// thread's slot (meaningful when keep) and the total in *count.  Contains barriers: every thread calls it.
-__device__ __forceinline__ int ordered_slot(bool keep, int *s_wave, int *count) {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const unsigned long long bal = __ballot(keep);
-    if (lane == 0) s_wave[wave] = __popcll(bal);
-    __syncthreads();
-    int off = 0;
-    for (int w = 0; w < wave; ++w) off += s_wave[w];
-    *count = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();
-    return off + __popcll(bal & ((1ull << lane) - 1ull));
-}
-
 // ------------------------------------------------------------------------------------------------
-// rtk_dbscan_batched.  Steps 1-4 are dbscan_kernel's (fused_misc.hip) on one stream; step 5 numbers the objects as the reference's
+// rtk_dbscan_batched: dbscan_workgroup (assoc_common.h) on one stream's columns, then step 5 numbers the objects as the reference's
 // dict does (models/track4d.py:119-125: in order of their FIRST MEMBER point, border points included -- the numpy block of
-// association.cluster_objects_device).  Tables (n points of the stream): f (n,8) | src | lab | aux | cl.
+// association.cluster_objects_device).  Tables (n points of the stream): f (n,8) | src | lab | aux | cl, 48 B per point.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void dbscan_stream(const rtk_track_frame_t &fr, int b, int n, float thr, double eps, int min_samples,
                                               int K, float *f, int *labels_b, int *obj_b, int *num_objects, int *flags) {
-    int *src = reinterpret_cast<int *>(f + (size_t)n * DB_D);      // mover -> input column
-    int *lab = src + n;                                            // component label (smallest core index) or INT_MAX
-    int *aux = lab + n;                                            // core flag, then cluster number of a representative
+    int *src = reinterpret_cast<int *>(f + (size_t)n * DB_D), *lab = src + n, *aux = lab + n;
     int *cl = aux + n;                                             // cluster id of each mover
-    __shared__ int s_m, s_changed, s_C, s_wave[4];
     const int t = threadIdx.x;
-    // ---- 1. ordered compaction of the movers ------------------------------------------------------------------------------
-    if (t == 0) { s_m = 0; s_C = 0; }
-    __syncthreads();
-    for (int base = 0; base < n; base += 256) {
-        const int i = base + t;
-        const bool mv = i < n && bcn_at(fr.cls, b, 0, i) > thr;
-        int cnt;
-        const int k = s_m + ordered_slot(mv, s_wave, &cnt);
-        if (mv) {
-            src[k] = i;
-            float *fk = f + (size_t)k * DB_D;
+    const auto [m, C] = dbscan_workgroup(n, f, src, lab, aux, eps, min_samples,
+        [&](int i) { return bcn_at(fr.cls, b, 0, i) > thr; },
+        [&](int i, float *fk) {
             fk[0] = bcn_at(fr.pc1, b, 0, i); fk[1] = bcn_at(fr.pc1, b, 1, i); fk[2] = bcn_at(fr.pc1, b, 2, i);
             fk[3] = bcn_at(fr.flow, b, 0, i); fk[4] = bcn_at(fr.flow, b, 1, i); fk[5] = bcn_at(fr.flow, b, 2, i);
             fk[6] = bcn_at(fr.feature1, b, 1, i);                  // v_r
             fk[7] = bcn_at(fr.prop, b, 0, i);
-        }
-        __syncthreads();
-        if (t == 0) s_m += cnt;
-        __syncthreads();
-    }
-    const int m = s_m;
-    // ---- 2. core points -----------------------------------------------------------------------------------------------
-    for (int i = t; i < m; i += 256) {
-        int cnt = 0;
-        for (int j = 0; j < m; ++j) cnt += db_adjacent(f, i, j, eps) ? 1 : 0;
-        aux[i] = cnt >= min_samples;
-        lab[i] = cnt >= min_samples ? i : 0x7fffffff;
-    }
-    __syncthreads();
-    // ---- 3. components of the core graph: min-label propagation with pointer jumping --------------------------------------
-    for (;;) {
-        if (t == 0) s_changed = 0;
-        __syncthreads();
-        for (int i = t; i < m; i += 256) {
-            if (!aux[i]) continue;
-            int best = lab[i];
-            for (int j = 0; j < m; ++j)
-                if (aux[j] && lab[j] < best && db_adjacent(f, i, j, eps)) best = lab[j];
-            if (best < lab[i]) { lab[i] = best; s_changed = 1; }       // racy reads of lab[j] only ever see smaller, valid labels
-        }
-        __syncthreads();
-        for (int i = t; i < m; i += 256)
-            if (aux[i]) { const int l = lab[lab[i]]; if (l < lab[i]) lab[i] = l; }
-        __syncthreads();
-        if (!s_changed) break;
-        __syncthreads();
-    }
-    // ---- 4. cluster numbers (rank of the component's smallest core index), border points -----------------------------------
-    for (int i = t; i < m; i += 256) {
-        if (aux[i] && lab[i] == i) {
-            int r = 0;
-            for (int j = 0; j < i; ++j) r += (aux[j] && lab[j] == j) ? 1 : 0;
-            aux[i] = 2 + r;
-            atomicAdd(&s_C, 1);
-        }
-    }
-    __syncthreads();
-    for (int i = t; i < m; i += 256) {
-        int out = -1;
-        if (aux[i]) {
-            out = aux[lab[i]] - 2;
-        } else if (min_samples > 2) {
-            for (int j = 0; j < m; ++j)
-                if (aux[j] && db_adjacent(f, i, j, eps)) {
-                    const int c = aux[lab[j]] - 2;
-                    out = (out < 0 || c < out) ? c : out;
-                }
-        }
-        cl[i] = out;
-        labels_b[src[i]] = out;
-    }
+        },
+        [&](int k, int s, int c) { cl[k] = c; labels_b[s] = c; });
     __syncthreads();
     // ---- 5. reference order: clusters ranked by their first member (movers are in column order: the smallest mover index) ----
-    const int C = s_C;                       // <= m: lab and aux are free again and hold C entries
+    // C <= m: lab and aux are free again and hold C entries
     for (int c = t; c < C; c += 256) lab[c] = 0x7fffffff;
     __syncthreads();
     for (int i = t; i < m; i += 256)
@@ -427,27 +350,19 @@ __global__ __launch_bounds__(256) void associate_batched_kernel(const AssocArgs 
     int *ind0 = reinterpret_cast<int *>(max0 + K), *ind1 = ind0 + K, *dec = ind1 + K, *sid = dec + K;
     const bool assoc = m > 0 && n > 0;
     if (assoc) {
-        // ---- log_optimal_transport (rtk_log_sinkhorn's arithmetic on this stream's live block) ----
-        for (int e = t; e < R * C; e += 256) {
-            const int i = e / C, j = e % C;
-            Z[i * ld + j] = (i < m && j < n) ? aff[(size_t)i * K + j] : a.alpha;
-        }
-        for (int e = t; e < R; e += 256) u[e] = 0.f;
-        for (int e = t; e < C; e += 256) v[e] = 0.f;
-        const float norm = -logf((float)m + (float)n);
-        __syncthreads();
-        log_sinkhorn_lds(m, n, Z, ld, u, v, norm, a.iters);
+        // ---- log_optimal_transport of this stream's live block (rtk_log_sinkhorn's) ----
+        const float norm = log_ot_lds(m, n, aff, K, a.alpha, a.iters, Z, ld, u, v);
         if (a.scores) {                                   // optional: the whole (m+1, n+1) plan, rtk_log_sinkhorn's `out`
             float *sc = a.scores + (size_t)b * (K + 1) * (K + 1);
             for (int e = t; e < R * C; e += 256) {
                 const int i = e / C, j = e % C;
-                sc[(size_t)i * (K + 1) + j] = Z[i * ld + j] + u[i] + v[j] - norm;
+                sc[(size_t)i * (K + 1) + j] = log_ot_plan(Z, ld, u, v, norm, i, j);
             }
             __syncthreads();                              // (the block below overwrites Z)
         }
         for (int e = t; e < m * n; e += 256) {            // the scores block, in place (each element read and written by one thread)
             const int i = e / n, j = e % n;
-            Z[i * ld + j] = Z[i * ld + j] + u[i] + v[j] - norm;
+            Z[i * ld + j] = log_ot_plan(Z, ld, u, v, norm, i, j);
         }
         __syncthreads();
         // ---- mutual best match.  Exact ties: the lowest index wins (strict > while scanning upwards) ----
