@@ -82,7 +82,10 @@ RTK_EXPORT int rtk_pointwise_mlp(int rows, int rows_per_sample, const rtk_interp
  * one's bias+ReLU is applied after the max over the nsample neighbours.  idx from rtk_ball_query.
  * out (samples*npoint, out_pitch) receives 16*last.cout16 channels at out_offset.
  * src_nuniq / dst_nuniq (optional, (samples)): duplicate-row counters of the source level (q rows >= src_nuniq[b]
- * are read as row 0) and of the centroid level (centroids >= dst_nuniq[b] are skipped). */
+ * are read as row 0) and of the centroid level (centroids >= dst_nuniq[b] are skipped: neither computed nor written).
+ * Non-finite inputs (this entry point and rtk_sa_scale_split): the ReLU and the max over the neighbours follow IEEE maxNum and drop a
+ * NaN (the reference propagates it), so an output can be finite where the reference's is NaN; it is never non-finite where the
+ * reference's is finite.  The cost volume and patch cost below propagate: non-finite exactly where the reference is. */
 RTK_EXPORT int rtk_sa_scale(int samples, int n, int npoint, int nsample, const float *xyz,
                             const float *new_xyz, const int *idx, const float *q, int q_pitch, int c1_16,
                             const float *w1xyz_packed, int nlayers, const rtk_layer_t *layers, float *out,
@@ -109,7 +112,9 @@ RTK_EXPORT int rtk_patch_cost(int samples, int n, const float *xyz, const int64_
  * 256-deep product against float64; an fp32 GEMM: 6.4e-7); the matrix time is 3/16 of the fp32-input MFMA's, the only exact-fp32
  * matrix instruction of gfx950.  Scales: one power of two per weight matrix (chosen by the packer), one per position (chosen by
  * the kernels from the position's own largest activation) -- the path has no operand range to leave, inputs of any fp32
- * magnitude give fp32-accurate results (non-finite inputs give non-finite outputs, as in the reference).
+ * magnitude give fp32-accurate results.  A non-finite activation makes every output of its position non-finite (inf splits into an
+ * inf and a NaN piece); the activations between layers (v_med3) map NaN to +inf (LeakyReLU) or 0 (ReLU): see rtk_sa_scale for what
+ * reaches the outputs.
  *
  * rtk_pack_split_layer: w (cout, cin) row-major fp32 (transposed != 0: the layer is w^T, w stored (cin, cout) row-major -- the
  * backward's W^T products from the forward's weights), both multiples of 32, cout * cin <= 2^22 -> image of cin/16 * cout/32 * 2

@@ -61,7 +61,8 @@ __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
     int b, bx, nbx;
     rtk_decode_block(P.gx, b, bx, nbx);
     const int dst_e = P.dst_nuniq ? __builtin_amdgcn_readfirstlane(P.dst_nuniq[b]) : P.npoint;
-    const int live_groups = (min(dst_e, P.npoint) + CPT - 1) / CPT;
+    const int live_c = min(dst_e, P.npoint);                 // centroids >= live_c are duplicates of centroid 0: neither computed nor written
+    const int live_groups = (live_c + CPT - 1) / CPT;
     if (bx * 4 >= live_groups) return;
     for (int i = threadIdx.x; i < NF * 64; i += blockDim.x) s_w[i] = P.blob[i];
     float w1[V1];
@@ -71,8 +72,8 @@ __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
     const int slot0 = j % NS;                         // neighbour slot of this lane within the first tile
     for (int unit = bx * 4 + (threadIdx.x >> 6); unit < live_groups; unit += nbx * 4) {
         int cl = unit * CPT + (NS >= 16 ? 0 : j / NS);        // centroid of this lane within the sample
-        const bool valid = cl < P.npoint;
-        if (!valid) cl = P.npoint - 1;
+        const bool valid = cl < live_c;                       // (a group of 16 / NS centroids may straddle dst_nuniq)
+        if (!valid) cl = live_c - 1;
         const int c = b * P.npoint + cl;                      // global centroid index (fits 32 bits: asserted by the launcher)
         const int src_e = P.src_nuniq ? P.src_nuniq[b] : 0x7fffffff;
         const float cg = g < 3 ? P.new_xyz[(long)c * 3 + g] : 0.f;
