@@ -76,6 +76,16 @@ RTK_EXPORT int rtk_pointwise_mlp(int rows, int rows_per_sample, const rtk_interp
                                  const rtk_layer_t *layers, float *out, int out_pitch, int out_channels,
                                  int out_channel_major, const int *row_nuniq, float *colmax, rtk_stream_t stream);
 
+/* rtk_pointwise_mlp of one split layer on a 128-channel interpolation segment (the encoder's fp1: split 128 -> 128 image, no other
+ * source, no sample bias, every row live) writing out (rows, out_pitch) channels 0..127 and colmax exactly as rtk_pointwise_mlp does,
+ * and then taking the same tile through one more split layer, 128 -> 256 without activation: proj_out[(rows, proj_pitch)] =
+ * proj[k] applied to the layer's output, k = 0 for samples < frame_split and 1 for the others (the cost volume's first-layer
+ * projections of frame 1 and frame 2, whose per-sample terms the cost volume adds: rtk_cost_volume_split_term).  Bit for bit what
+ * rtk_pointwise_mlp gives for the layer alone and for proj[k] on its output. */
+RTK_EXPORT int rtk_pointwise_mlp_tap(int rows, int rows_per_sample, const rtk_interp_t *interp, const rtk_layer_t *layer, float *out,
+                                     int out_pitch, float *colmax, const rtk_layer_t *proj, int frame_split, float *proj_out,
+                                     int proj_pitch, rtk_stream_t stream);
+
 /* One scale of a set-abstraction level.  q (samples*n, q_pitch): per-point layer-1 projection of the
  * features (BN scale folded); layer 1 = relu(q[idx] + Wx.(xyz[idx] - centroid) + b1) with
  * w1xyz_packed the [1][c1_16][64][4] image of [Wx | b1]; then nlayers more packed layers; the last
@@ -143,6 +153,14 @@ RTK_EXPORT int rtk_cost_volume_split_shared(int samples, int n1, int n2, const f
                                             const void *split_images, const float *image_scales, const float *bias2,
                                             const float *bias3, const rtk_layer_t *wn, float *out, int out_pitch, int workgroups,
                                             rtk_stream_t stream);
+/* ... with layer 1's per-sample term moved out of p1: sample_term (samples, 256) is added to the p1 row of every point of its sample
+ * before the neighbour's p2 row, layer 1 = leaky((p1[i] + sample_term[b]) + p2[idx] + Wd.d), each sum rounded to fp32 -- bit for bit
+ * rtk_cost_volume_split_shared on p1 + sample_term[b].  (p1, p2 without their per-sample terms: rtk_pointwise_mlp_tap.) */
+RTK_EXPORT int rtk_cost_volume_split_term(int samples, int n1, int n2, const float *xyz1, const float *xyz2,
+                                          const int64_t *knn_idx, const float *p1, const float *p2, const float *sample_term,
+                                          const float *wd_packed, const void *split_images, const float *image_scales,
+                                          const float *bias2, const float *bias3, const rtk_layer_t *wn, float *out, int out_pitch,
+                                          int workgroups, rtk_stream_t stream);
 /* rtk_sa_scale for the scales whose MLP is offset layer (c1 = 32 or 64 channels) + ONE layer c1 -> 64, nsample 16 or 32 (sa2 scale 1,
  * sa3 scales 0 and 1 of the PNHead): same arguments, the layer as its split image + inverse scale (rtk_pack_split_layer(64, c1, ...)) + fp32 bias. */
 RTK_EXPORT int rtk_sa_scale_split(int samples, int n, int npoint, int nsample, const float *xyz, const float *new_xyz,
@@ -204,12 +222,17 @@ RTK_EXPORT int rtk_gru_step_head(int b, int layers, int hidden, const float *x, 
 /* Everything that is a function of a sample's global (max-pooled) feature g (samples, cin) in one launch (models/track4d.py:89-95
  * broadcasts it over the points and concatenates it to per-point inputs; a concatenated global half of a layer's input is a
  * per-sample bias of that layer): jobs[j]: out[(s - s0), :cout] = W g[s] + bias for s in [s0, s0 + count), wt = W TRANSPOSED
- * (cin, cout) fp32; and, with bcast, bcast[(s n + r) bcast_pitch + c] = g[s][c] for every row r < n of every sample.  cin % 32 == 0. */
+ * (cin, cout) fp32; and, with bcast, bcast[(s n + r) bcast_pitch + c] = g[s][c] for every row r < n of every sample.  cin % 32 == 0.
+ * A job with wt2 (W2 transposed, (cin, cout)) is paired: out[(s - s0)] = (W g[s] + bias) + W2 g[s - s0 + s2], both maps evaluated
+ * as two jobs of their own would be (the second without bias), then added with one rounding -- bit for bit the sum of those two
+ * jobs' outputs.  wt2 = NULL: s2 is ignored. */
 #define RTK_GT_MAX_JOBS 4
 typedef struct {
     const float *wt, *bias;      /* (cin, cout), (cout) or NULL */
     float *out;                  /* (count, out_pitch) */
     int cout, s0, count, out_pitch;
+    const float *wt2;            /* (cin, cout) or NULL */
+    int s2;                      /* with wt2: s2 + count <= samples */
 } rtk_gterm_job_t;
 RTK_EXPORT int rtk_global_terms(int samples, int cin, const float *g, int njobs, const rtk_gterm_job_t *jobs, float *bcast, int bcast_pitch,
                                 int n, rtk_stream_t stream);

@@ -369,10 +369,18 @@ struct LayerStepS {
         }
     }
     static __device__ __forceinline__ void run(WS &ws, const f4 (&h)[U], float scale, f4 (&acc)[V], f4 (&a)[2][4], u4v (&b)[2]) {
-        constexpr int up = GI / GV, v0 = (GI % GV) * 2;
+        constexpr int up = GI / GV;
         if constexpr (GI + 1 < NG) load<GI + 1>(ws, a[(GI + 1) & 1]);
         if constexpr (GI % GV == 0) split2(h[2 * up], 2 * up + 1 < U ? h[2 * up + 1] : f4_zero(), scale, b);
-        const f4(&c)[4] = a[GI & 1];
+        mm(a[GI & 1], b, acc);
+    }
+    // the same group step on pieces split beforehand (pc[up]: the pieces of input block pair up), for several layers on one input
+    static __device__ __forceinline__ void run_pieces(WS &ws, const u4v (&pc)[(U + 1) / 2][2], f4 (&acc)[V], f4 (&a)[2][4]) {
+        if constexpr (GI + 1 < NG) load<GI + 1>(ws, a[(GI + 1) & 1]);
+        mm(a[GI & 1], pc[GI / GV], acc);
+    }
+    static __device__ __forceinline__ void mm(const f4 (&c)[4], const u4v (&b)[2], f4 (&acc)[V]) {
+        constexpr int v0 = (GI % GV) * 2;
 #define RTK_S16_MM(pa, pb)                                                                            \
         acc[v0] = mfma16_h(__builtin_bit_cast(u4v, c[pa]), b[pb], acc[v0]);                            \
         if constexpr (v0 + 1 < V) acc[v0 + 1] = mfma16_h(__builtin_bit_cast(u4v, c[2 + pa]), b[pb], acc[v0 + 1]);
@@ -388,6 +396,15 @@ __device__ __forceinline__ void mlp_layer_split_impl(WS &ws, const f4 (&h)[U], f
     u4v b[2];
     LayerStepS<U, V, FBASE, 0, WS, F>::template load<0>(ws, a[0]);
     (LayerStepS<U, V, FBASE, GI, WS, F>::run(ws, h, scale, acc, a, b), ...);
+}
+
+// acc[v] += 2^(kw + kx) W . h from the pieces of h (split2 of the input block pairs at this lane's scale 2^kx); the image layout of
+// mlp_layer_ws_split with V output blocks from fragment FBASE on
+template <int U, int V, int FBASE, class WS, int F, int... GI>
+__device__ __forceinline__ void mlp_layer_pieces_impl(WS &ws, const u4v (&pc)[(U + 1) / 2][2], f4 (&acc)[V], std::integer_sequence<int, GI...>) {
+    f4 a[2][4];
+    LayerStepS<U, V, FBASE, 0, WS, F>::template load<0>(ws, a[0]);
+    (LayerStepS<U, V, FBASE, GI, WS, F>::run_pieces(ws, pc, acc, a), ...);
 }
 
 // acc[v] += 2^(kw + kx) W . h on the split path (scale = this lane's 2^kx, lane_scale16); FBASE = index of the layer's first fragment

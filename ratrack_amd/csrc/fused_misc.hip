@@ -137,7 +137,8 @@ extern "C" int rtk_gru_step_head(int b, int layers, int hidden, const float *x, 
 // (models/track4d.py:89-95 broadcasts it over the points and concatenates; here a concatenated global half of a layer's input is a
 // per-sample bias of that layer): up to RTK_GT_MAX_JOBS linear maps out_j[s - s0_j] = W_j g[s] + b_j over sample ranges, and the
 // broadcast of g[s] over the n rows of sample s of a point-major tensor (the global half of pc{1,2}_features).  One workgroup per
-// sample.  (Until round 6: three 64-row launches of the per-point MLP kernel + a framework broadcast copy.)
+// sample.  (Until round 6: three 64-row launches of the per-point MLP kernel + a framework broadcast copy.)  A paired job (wt2) adds
+// a second map of another sample's feature: the cost volume's per-sample term, frame 1's and frame 2's halves in one output.
 // ------------------------------------------------------------------------------------------------
 struct GtParams {
     int samples, cin, njobs, n, bcast_pitch;
@@ -148,30 +149,47 @@ struct GtParams {
 
 __global__ __launch_bounds__(256) void global_terms_kernel(const GtParams P) {
     __shared__ __attribute__((aligned(16))) float s_g[512];
+    __shared__ float s_g2[RTK_GT_MAX_JOBS][512];      // the second input row of each paired job (wt2) that covers this sample
     const int s = blockIdx.x, t = threadIdx.x;
     for (int k = t; k < P.cin; k += 256) s_g[k] = P.g[(long)s * P.cin + k];
+    for (int j = 0; j < P.njobs; ++j)
+        if (P.job[j].wt2 && s >= P.job[j].s0 && s < P.job[j].s0 + P.job[j].count)
+            for (int k = t; k < P.cin; k += 256) s_g2[j][k] = P.g[(long)(s - P.job[j].s0 + P.job[j].s2) * P.cin + k];
     __syncthreads();
     // the outputs of all of this sample's jobs as one list, spread over the sample's workgroups, a thread per output (k ascending), 64 weight
-    // loads in flight per thread: the launch is a few L2 round trips long
+    // loads in flight per thread: the launch is a few L2 round trips long.  A paired job (wt2) takes two consecutive list entries per
+    // channel, starting at an even index: lanes 2 i and 2 i + 1 evaluate its two maps side by side, each exactly as a job of its own
+    // would (the second without bias), and the even lane adds them with one rounding -- one map per thread, as many round trips.
     int total = 0;
     for (int j = 0; j < P.njobs; ++j)
-        if (s >= P.job[j].s0 && s < P.job[j].s0 + P.job[j].count) total += P.job[j].cout;
+        if (s >= P.job[j].s0 && s < P.job[j].s0 + P.job[j].count) total = (P.job[j].wt2 ? (total + 1) & ~1 : total) + (P.job[j].wt2 ? 2 : 1) * P.job[j].cout;
     for (int o = blockIdx.y * 256 + t; o < total; o += 256 * gridDim.y) {
-        int c = o, j = 0;
+        int c = -1, j = 0, base = 0;
         for (; j < P.njobs; ++j) {
             if (s < P.job[j].s0 || s >= P.job[j].s0 + P.job[j].count) continue;
-            if (c < P.job[j].cout) break;
-            c -= P.job[j].cout;
+            if (P.job[j].wt2) base = (base + 1) & ~1;
+            const int span = (P.job[j].wt2 ? 2 : 1) * P.job[j].cout;
+            if (o < base + span) { c = o - base; break; }
+            base += span;
         }
+        if (c < 0) continue;          // the padding index in front of a paired job
         const rtk_gterm_job_t &J = P.job[j];
-        float acc = J.bias ? J.bias[c] : 0.f;
+        const int m = J.wt2 ? (c & 1) : 0;
+        if (J.wt2) c >>= 1;
+        const float *wt = m ? J.wt2 : J.wt, *g = m ? s_g2[j] : s_g;
+        float acc = m == 0 && J.bias ? J.bias[c] : 0.f;
         for (int k0 = 0; k0 < P.cin; k0 += 64) {          // cin % 32 == 0
             float wv[64];
 #pragma unroll
-            for (int q = 0; q < 64; ++q) wv[q] = J.wt[(long)min(k0 + q, P.cin - 1) * J.cout + c];
+            for (int q = 0; q < 64; ++q) wv[q] = wt[(long)min(k0 + q, P.cin - 1) * J.cout + c];
 #pragma unroll
             for (int q = 0; q < 64; ++q)
-                if (k0 + q < P.cin) acc = fmaf(wv[q], s_g[k0 + q], acc);
+                if (k0 + q < P.cin) acc = fmaf(wv[q], g[k0 + q], acc);
+        }
+        if (J.wt2) {
+            const float other = __shfl_xor(acc, 1);      // the partner lane: same iteration, same job (o and o ^ 1)
+            if (m) continue;
+            acc = __fadd_rn(acc, other);
         }
         J.out[(long)(s - J.s0) * J.out_pitch + c] = acc;
     }
@@ -194,7 +212,8 @@ extern "C" int rtk_global_terms(int samples, int cin, const float *g, int njobs,
     P.samples = samples; P.cin = cin; P.njobs = njobs; P.n = n; P.bcast_pitch = bcast_pitch; P.g = g; P.bcast = bcast;
     for (int j = 0; j < njobs; ++j) {
         RTK_REQUIRE(jobs[j].wt && jobs[j].out && jobs[j].cout > 0 && jobs[j].s0 >= 0 && jobs[j].count >= 0 && jobs[j].s0 + jobs[j].count <= samples &&
-                    jobs[j].out_pitch >= jobs[j].cout, "global_terms: bad job %d", j);
+                    jobs[j].out_pitch >= jobs[j].cout && (!jobs[j].wt2 || (jobs[j].s2 >= 0 && jobs[j].s2 + jobs[j].count <= samples)),
+                    "global_terms: bad job %d", j);
         P.job[j] = jobs[j];
     }
     global_terms_kernel<<<dim3(samples, bcast ? 8 : 2), 256, 0, (hipStream_t)stream>>>(P);

@@ -114,6 +114,46 @@ __device__ __forceinline__ void store_tile(const PwParams &P, const f4 (&acc)[V]
     }
 }
 
+// slots u < nslots of this lane's input: the three-NN inverse-distance interpolation of row p (lib/pointnet2_modules.py:141-146)
+template <int U>
+__device__ __forceinline__ void load_interp(const PwParams &P, int p, int b, int g, int nslots, f4 (&h)[U]) {
+    const int *idp = P.interp.idx + (size_t)p * 3;
+    int id[3] = {idp[0], idp[1], idp[2]};
+    if (P.interp.nuniq) {       // known rows beyond the sample's unique count are copies of its row 0
+        const int e = P.interp.nuniq[b];
+        id[0] = id[0] < e ? id[0] : 0; id[1] = id[1] < e ? id[1] : 0; id[2] = id[2] < e ? id[2] : 0;
+    }
+    const float *d2 = P.interp.dist2 + (size_t)p * 3;
+    const float r0 = __fdiv_rn(1.0f, __fadd_rn(__fsqrt_rn(d2[0]), 1e-8f));
+    const float r1 = __fdiv_rn(1.0f, __fadd_rn(__fsqrt_rn(d2[1]), 1e-8f));
+    const float r2 = __fdiv_rn(1.0f, __fadd_rn(__fsqrt_rn(d2[2]), 1e-8f));
+    const float norm = __fadd_rn(__fadd_rn(r0, r1), r2);
+    const float w0 = __fdiv_rn(r0, norm), w1 = __fdiv_rn(r1, norm), w2 = __fdiv_rn(r2, norm);
+    const float *k0 = P.interp.known_feats + ((size_t)b * P.interp.m + id[0]) * P.interp.pitch;
+    const float *k1 = P.interp.known_feats + ((size_t)b * P.interp.m + id[1]) * P.interp.pitch;
+    const float *k2 = P.interp.known_feats + ((size_t)b * P.interp.m + id[2]) * P.interp.pitch;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (u < nslots) {
+            // unconditional loads (lanes past the last channel re-read channel 0 and discard): a load under a per-lane
+            // condition is a basic block of its own and the compiler waits for it before issuing the next one
+            const int c = 16 * u + 4 * g;
+            const bool ok = c < P.interp.channels;
+            const int cc = ok ? c : 0;
+            const f4 a0 = *reinterpret_cast<const f4 *>(k0 + cc);
+            const f4 a1 = *reinterpret_cast<const f4 *>(k1 + cc);
+            const f4 a2 = *reinterpret_cast<const f4 *>(k2 + cc);
+            // interpolate_gpu.cu:168  w0*p0 + w1*p1 + w2*p2  (nvcc: fma(w2,p2,fma(w1,p1,w0*p0)))
+            f4 v;
+            v.x = __fmaf_rn(w2, a2.x, __fmaf_rn(w1, a1.x, __fmul_rn(w0, a0.x)));
+            v.y = __fmaf_rn(w2, a2.y, __fmaf_rn(w1, a1.y, __fmul_rn(w0, a0.y)));
+            v.z = __fmaf_rn(w2, a2.z, __fmaf_rn(w1, a1.z, __fmul_rn(w0, a0.z)));
+            v.w = __fmaf_rn(w2, a2.w, __fmaf_rn(w1, a1.w, __fmul_rn(w0, a0.w)));
+            h[u] = ok ? v : f4_zero();
+        }
+    }
+}
+
 #define PW_NW 4    // waves per workgroup
 #ifndef PW_WGS_TARGET
 #define PW_WGS_TARGET 256      // workgroups per launch: about one per CU, the rest is looped.  Round 6, same box, alternating (ab_knobs.py):
@@ -167,43 +207,7 @@ __global__ __launch_bounds__(64 * PW_NW, 2) void pointwise_mlp_kernel(const PwPa
 
         f4 h[U];
         // ---- segment 0 (optional): three-NN interpolation, lib/pointnet2_modules.py:141-146 -------------
-        if (INTERP) {
-            const int *idp = P.interp.idx + (size_t)p * 3;
-            int id[3] = {idp[0], idp[1], idp[2]};
-            if (P.interp.nuniq) {       // known rows beyond the sample's unique count are copies of its row 0
-                const int e = P.interp.nuniq[b];
-                id[0] = id[0] < e ? id[0] : 0; id[1] = id[1] < e ? id[1] : 0; id[2] = id[2] < e ? id[2] : 0;
-            }
-            const float *d2 = P.interp.dist2 + (size_t)p * 3;
-            const float r0 = __fdiv_rn(1.0f, __fadd_rn(__fsqrt_rn(d2[0]), 1e-8f));
-            const float r1 = __fdiv_rn(1.0f, __fadd_rn(__fsqrt_rn(d2[1]), 1e-8f));
-            const float r2 = __fdiv_rn(1.0f, __fadd_rn(__fsqrt_rn(d2[2]), 1e-8f));
-            const float norm = __fadd_rn(__fadd_rn(r0, r1), r2);
-            const float w0 = __fdiv_rn(r0, norm), w1 = __fdiv_rn(r1, norm), w2 = __fdiv_rn(r2, norm);
-            const float *k0 = P.interp.known_feats + ((size_t)b * P.interp.m + id[0]) * P.interp.pitch;
-            const float *k1 = P.interp.known_feats + ((size_t)b * P.interp.m + id[1]) * P.interp.pitch;
-            const float *k2 = P.interp.known_feats + ((size_t)b * P.interp.m + id[2]) * P.interp.pitch;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (u < ustart[0]) {
-                    // unconditional loads (lanes past the last channel re-read channel 0 and discard): a load under a per-lane
-                    // condition is a basic block of its own and the compiler waits for it before issuing the next one
-                    const int c = 16 * u + 4 * g;
-                    const bool ok = c < P.interp.channels;
-                    const int cc = ok ? c : 0;
-                    const f4 a0 = *reinterpret_cast<const f4 *>(k0 + cc);
-                    const f4 a1 = *reinterpret_cast<const f4 *>(k1 + cc);
-                    const f4 a2 = *reinterpret_cast<const f4 *>(k2 + cc);
-                    // interpolate_gpu.cu:168  w0*p0 + w1*p1 + w2*p2  (nvcc: fma(w2,p2,fma(w1,p1,w0*p0)))
-                    f4 v;
-                    v.x = __fmaf_rn(w2, a2.x, __fmaf_rn(w1, a1.x, __fmul_rn(w0, a0.x)));
-                    v.y = __fmaf_rn(w2, a2.y, __fmaf_rn(w1, a1.y, __fmul_rn(w0, a0.y)));
-                    v.z = __fmaf_rn(w2, a2.z, __fmaf_rn(w1, a1.z, __fmul_rn(w0, a0.z)));
-                    v.w = __fmaf_rn(w2, a2.w, __fmaf_rn(w1, a1.w, __fmul_rn(w0, a0.w)));
-                    h[u] = ok ? v : f4_zero();
-                }
-            }
-        }
+        if (INTERP) load_interp<U>(P, p, b, g, ustart[0], h);
         // ---- plain / per-sample segments --------------------------------------------------------------
         // per-lane row base of every source (row = point, or sample for broadcast sources), then one
         // load per 16-channel slot from the source that owns it (selection is wave-uniform)
@@ -347,5 +351,180 @@ extern "C" int rtk_pointwise_mlp(int rows, int rows_per_sample, const rtk_interp
     }
 #undef PW_CASE
     RTK_CHECK_LAUNCH("pointwise_mlp");
+    return RTK_OK;
+}
+
+// ---- rtk_pointwise_mlp_tap ---------------------------------------------------------------------------------------------
+// The encoder's last layer (fp1: interpolation -> 128, ReLU, column max) followed, on the tile still in registers, by a linear
+// 128 -> 256 projection whose image is chosen per sample (frame 1 / frame 2 of the cost volume): the two per-point launches that
+// read the layer's output back are gone.  The 256 outputs are computed as two halves of eight 16-channel blocks on the same
+// activation pieces (one split per tile): a 16-block accumulator set next to the layer's would not fit two waves per SIMD.
+//
+// The weight stream runs over two images: chunks [0, C1) are the layer's, the rest the frame's projection image, visited half by
+// half -- logical fragment F1 + PH h + PR up + r (half h, input block pair up, r < PR = 2 VH) is fragment PR (2 up + h) + r of the
+// split image (layout of fused_common.h: frag[up][v][p] with 2 VH output blocks), so a chunk is one contiguous run of the image.
+template <int NW, int F, int NF, int C1, int UP, int VH>
+struct WStreamTap {       // WStream's protocol (start_deferred, next, frag, finish) over the two sources; not a WStream, so that no
+                          // routine written for one can take it and issue from the wrong image
+    static constexpr int NCHUNKS = NF / F, PR = 2 * VH, PH = UP * PR;
+    static_assert(NF % F == 0 && PR % F == 0 && C1 < NCHUNKS, "whole chunks; a chunk of the projection is one run of the image");
+    const char *blob;     // the layer's image (chunks [0, C1))
+    const char *proj;     // the sample's projection image
+    f4 *lds;
+    unsigned lane_off;
+    int cur, buf, wave, lane;
+    __device__ __forceinline__ void issue(int chunk, int into) {
+        const char *base;
+        if (chunk < C1) {
+            base = blob + (size_t)chunk * F * 1024;
+        } else {
+            const int l = (chunk - C1) * F, h = l / PH, up = (l % PH) / PR, r = l % PR;
+            base = proj + (size_t)(PR * (2 * up + h) + r) * 1024;
+        }
+#pragma unroll
+        for (int i = 0; i < (F + NW - 1) / NW; ++i) {
+            const int f = wave + i * NW;
+            if (f < F)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(base + (size_t)i * NW * 1024 + lane_off),
+                                                 (__attribute__((address_space(3))) void *)(lds + (into * F + f) * 64), 16, 0, 0);
+        }
+    }
+    // WStream::start_deferred: chunk 0 requested, the state that of a pass that has just ended; the first next() waits
+    __device__ __forceinline__ void start_deferred(const f4 *blob_, const f4 *proj_, f4 *lds_, int wave_, int lane_) {
+        blob = reinterpret_cast<const char *>(blob_);
+        proj = reinterpret_cast<const char *>(proj_);
+        lds = lds_; wave = wave_; lane = lane_;
+        lane_off = (unsigned)(wave * 64 + lane) * 16u;
+        cur = NCHUNKS - 1; buf = 1;
+        issue(0, 0);
+    }
+    __device__ __forceinline__ void next() {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        buf ^= 1;
+        cur = cur + 1 == NCHUNKS ? 0 : cur + 1;
+        asm volatile("" : "+s"(cur));      // (WStream::next)
+        issue(cur + 1 == NCHUNKS ? 0 : cur + 1, buf ^ 1);
+    }
+    __device__ __forceinline__ f4 frag(int f_in_chunk) const { return lds[(buf * F + f_in_chunk) * 64 + lane]; }
+    __device__ __forceinline__ void finish() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+};
+
+struct TapParams {
+    PwParams pw;                  // the layer: interpolation segment, layer[0], out (the layer's output), colmax
+    const float *proj_w[2];       // split images of the projection: samples < frame_split, the others
+    const float *proj_b[2];
+    float proj_inv[2];
+    int frame_split;
+    float *pout;                  // (rows, pout_pitch): the projection
+    int pout_pitch;
+};
+
+template <int U, int V1, int VP>
+__global__ __launch_bounds__(64 * PW_NW, 2) void pointwise_tap_kernel(const TapParams T) {
+    __shared__ __attribute__((aligned(16))) f4 s_w[2 * PW_F * 64];
+    const PwParams &P = T.pw;
+    const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
+    const int wave_in_wg = threadIdx.x >> 6;
+    int b, bx, nbx;
+    rtk_decode_block(P.gx, b, bx, nbx);
+    const int rps = P.rows_per_sample;
+    const int groups = (rps + PW_NW * 16 - 1) / (PW_NW * 16);
+    if (bx >= groups) return;
+    constexpr int UP = (V1 + 1) / 2, VH = VP / 2, F1 = split16_nf(U, V1), PH = UP * 2 * VH;
+    static_assert(VP % 2 == 0 && F1 % PW_F == 0, "whole chunks of the layer, two equal halves of the projection");
+    WStreamTap<PW_NW, PW_F, F1 + 2 * PH, F1 / PW_F, UP, VH> ws;
+    const bool f2 = b >= T.frame_split;                    // uniform over the workgroup: one sample
+    const float *pbias = f2 ? T.proj_b[1] : T.proj_b[0];
+    const float pinv = f2 ? T.proj_inv[1] : T.proj_inv[0];
+    ws.start_deferred(reinterpret_cast<const f4 *>(P.layer[0].w_packed), reinterpret_cast<const f4 *>(f2 ? T.proj_w[1] : T.proj_w[0]), s_w,
+                      wave_in_wg, lane);
+
+    for (int G = bx; G < groups; G += nbx) {
+        asm volatile("" ::: "memory");
+        const int r = G * (PW_NW * 16) + wave_in_wg * 16 + j;
+        const bool valid = r < rps;
+        const int p = b * rps + (valid ? r : rps - 1);
+        f4 h[U];
+        load_interp<U>(P, p, b, g, U, h);
+        // the layer: pw_layer's split path (the first next() waits for chunk 0 together with the loads above)
+        f4 a1[V1];
+        {
+            const LaneScale s1 = lane_scale16(h);
+            init_zero<V1>(a1);
+            ws.next();
+            mlp_layer_split_impl<U, V1, 0, decltype(ws), PW_F>(ws, h, s1.s, a1, std::make_integer_sequence<int, ((U + 1) / 2) * ((V1 + 1) / 2)>{});
+            scale_bias<V1>(a1, s1.inv * P.layer[0].inv_scale, P.layer[0].bias, g);
+            apply_act<V1>(a1, P.layer[0].act);
+        }
+        store_tile<V1>(P, a1, p, b, g, valid);
+        // the projection: a1's pieces once, then each half on them (rtk_pointwise_mlp's arithmetic for the same layer: bit for bit)
+        const LaneScale sc = lane_scale16(a1);
+        u4v pc[UP][2];
+#pragma unroll
+        for (int up = 0; up < UP; ++up) split2(a1[2 * up], 2 * up + 1 < V1 ? a1[2 * up + 1] : f4_zero(), sc.s, pc[up]);
+        const float c = sc.inv * pinv;
+        float *o = T.pout + (size_t)p * T.pout_pitch + 4 * g;
+        auto half = [&](auto hc) {
+            constexpr int hv = decltype(hc)::value;
+            f4 acc[VH];
+            init_zero<VH>(acc);
+            mlp_layer_pieces_impl<V1, VH, F1 + hv * PH, decltype(ws), PW_F>(ws, pc, acc, std::make_integer_sequence<int, UP * (VH / 2)>{});
+            scale_bias<VH>(acc, c, pbias + 16 * VH * hv, g);
+            if (valid) {
+#pragma unroll
+                for (int v = 0; v < VH; ++v) *reinterpret_cast<f4 *>(o + 16 * (VH * hv + v)) = acc[v];
+            }
+        };
+        half(std::integral_constant<int, 0>{});
+        half(std::integral_constant<int, 1>{});
+    }
+    ws.finish();
+}
+
+extern "C" int rtk_pointwise_mlp_tap(int rows, int rows_per_sample, const rtk_interp_t *interp, const rtk_layer_t *layer, float *out,
+                                     int out_pitch, float *colmax, const rtk_layer_t *proj, int frame_split, float *proj_out, int proj_pitch,
+                                     rtk_stream_t stream) {
+    RTK_REQUIRE(rows > 0 && rows_per_sample > 0 && rows % rows_per_sample == 0 && rows / rows_per_sample <= 65535,
+                "pointwise_mlp_tap: bad row counts (%d, %d)", rows, rows_per_sample);
+    RTK_REQUIRE(interp && interp->known_feats && interp->idx && interp->dist2 && interp->pitch % 4 == 0 && interp->channels % 4 == 0 &&
+                (interp->channels + 15) / 16 == 8, "pointwise_mlp_tap: bad interp segment (128 channels)");
+    RTK_REQUIRE(layer && layer->w_packed && layer->bias && layer->cin16 == 8 && layer->cout16 == 8 && (layer->act & RTK_LAYER_SPLIT),
+                "pointwise_mlp_tap: the layer must be a split 128 -> 128 image");
+    RTK_REQUIRE(proj && frame_split >= 0 && proj_out && proj_pitch % 4 == 0 && proj_pitch >= 256, "pointwise_mlp_tap: bad projection output");
+    for (int k = 0; k < 2; ++k)
+        RTK_REQUIRE(proj[k].w_packed && proj[k].bias && proj[k].cin16 == 8 && proj[k].cout16 == 16 && (proj[k].act & RTK_LAYER_SPLIT) &&
+                    (proj[k].act & 0xff) == 0, "pointwise_mlp_tap: projection %d must be a split 128 -> 256 image without activation", k);
+    RTK_REQUIRE(out && out_pitch % 4 == 0 && out_pitch >= 128, "pointwise_mlp_tap: bad out_pitch %d", out_pitch);
+    TapParams T;
+    memset(&T, 0, sizeof(T));
+    PwParams &P = T.pw;
+    P.rows = rows;
+    P.rows_per_sample = rows_per_sample;
+    P.interp = *interp;
+    P.layer[0] = *layer;
+    P.layer[0].act = layer->act & 0xff;
+    P.out = out;
+    P.out_pitch = out_pitch;
+    P.out_channels = 128;
+    P.colmax = colmax;
+    for (int k = 0; k < 2; ++k) {
+        T.proj_w[k] = proj[k].w_packed;
+        T.proj_b[k] = proj[k].bias;
+        T.proj_inv[k] = proj[k].inv_scale;
+    }
+    T.frame_split = frame_split;
+    T.pout = proj_out;
+    T.pout_pitch = proj_pitch;
+    // the grid of launch_pw
+    const int samples = rows / rows_per_sample;
+    const int groups = (rows_per_sample + PW_NW * 16 - 1) / (PW_NW * 16);
+    int gx = PW_WGS_TARGET / samples;
+    if (gx < 1) gx = 1;
+    if (gx > groups) gx = groups;
+    P.gx = samples % 8 == 0 ? gx : 0;
+    const dim3 blocks = P.gx ? dim3(gx * samples) : dim3(gx, samples);
+    pointwise_tap_kernel<8, 8, 16><<<blocks, 64 * PW_NW, 0, (hipStream_t)stream>>>(T);
+    RTK_CHECK_LAUNCH("pointwise_mlp_tap");
     return RTK_OK;
 }

@@ -118,6 +118,7 @@ struct CvSplitParams {
     const float *xyz1, *xyz2;
     const int64_t *knn;
     const float *p1, *p2;
+    const float *st;              // optional (samples, 256): per-sample term of layer 1, added to the p1 row of each point of the sample
     const float *wd;              // [16][64] image of [Wd | 0] (fused_common.h): Wd[c][k] = wd[(c / 16) * 64 + 16 k + c % 16]
     const f4 *blob;               // split images of layers 2, 3 ...
     const float *wsc;             // ... and the inverses of their power-of-two weight scales (rtk_pack_split_layer)
@@ -299,6 +300,9 @@ __device__ __forceinline__ f4 mul_row_bcast(const f4 q, const f4 r) {
         : "v"(q.x), "v"(q.y), "v"(q.z), "v"(q.w), "v"(r.x), "v"(r.y), "v"(r.z), "v"(r.w), "n"(K));
     return o;
 }
+__device__ __forceinline__ f4 add4_rn(const f4 a, const f4 b) {
+    return (f4){__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w)};
+}
 template <int V0, int V1>
 __device__ __forceinline__ void cv_layer1_blocks(const CvSplitParams &P, const f4 q0, const f4 q1, float b0, float b1, int hh, int col, float kinf, f4 (&h)[32]) {
     static_assert(V1 <= 8, "eight 32-channel blocks");
@@ -370,6 +374,7 @@ void cost_volume_split_kernel(const CvSplitParams P) {
         nb = (long)b * P.n2 + (long)P.knn[i * 16 + j];
         cv_rows_request<0>(P.p2, (int)nb, rows, lane);
         q0 = ldc4(P.p1 + i * 256 + 4 * hh + 8 * j); q1 = ldc4(P.p1 + i * 256 + 4 * hh + 8 * (16 + j));
+        if (P.st) { q0 = add4_rn(q0, ldc4(P.st + b * 256 + 4 * hh + 8 * j)); q1 = add4_rn(q1, ldc4(P.st + b * 256 + 4 * hh + 8 * (16 + j))); }
         dx = __fsub_rn(P.xyz2[nb * 3], P.xyz1[i * 3]); dy = __fsub_rn(P.xyz2[nb * 3 + 1], P.xyz1[i * 3 + 1]);
         dz = __fsub_rn(P.xyz2[nb * 3 + 2], P.xyz1[i * 3 + 2]);
     }
@@ -384,7 +389,7 @@ void cost_volume_split_kernel(const CvSplitParams P) {
         const long in_ = (long)bn * P.n1 + (validn ? ptn : P.n1 - 1);
         long knn_next = 0;
         if (more) knn_next = (long)P.knn[in_ * 16 + j];
-        // layer 1: leaky(p1[i] + p2[nb] + Wd.d)     (bias folded into p1)
+        // layer 1: leaky(p1[i] + p2[nb] + Wd.d)     (bias folded into p1, or into the per-sample term: (p1[i] + st[b]) + p2[nb])
         f4 h[32];
         float t2[8];
         {
@@ -459,15 +464,17 @@ void cost_volume_split_kernel(const CvSplitParams P) {
         out_block(1);
         // ---- next tile: its direction and its p1 slots -------------------------------------------------------------------------
         float cn[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};              // the six coordinates; subtracted after the last block (the
-        f4 q0n = q0, q1n = q1;                                        // subtraction is where the wave waits for them)
-        if (more) {
+        f4 q0n = q0, q1n = q1, s0n = q0, s1n = q1;                    // subtraction is where the wave waits for them; so is the
+        if (more) {                                                   // per-sample term's addition)
 #pragma unroll
             for (int c = 0; c < 3; ++c) { cn[c] = ldc(P.xyz2 + nbn * 3 + c); cn[3 + c] = ldc(P.xyz1 + in_ * 3 + c); }
             q0n = ldc4(P.p1 + in_ * 256 + 4 * hh + 8 * j); q1n = ldc4(P.p1 + in_ * 256 + 4 * hh + 8 * (16 + j));
         }
+        if (more && P.st) { s0n = ldc4(P.st + bn * 256 + 4 * hh + 8 * j); s1n = ldc4(P.st + bn * 256 + 4 * hh + 8 * (16 + j)); }
 #pragma unroll
         for (int v = 2; v < SPLIT_VB; ++v) out_block(v);
         pt = ptn; valid = validn; i = in_; nb = nbn; q0 = q0n; q1 = q1n;
+        if (P.st) { q0 = add4_rn(q0n, s0n); q1 = add4_rn(q1n, s1n); }
         dx = __fsub_rn(cn[0], cn[3]); dy = __fsub_rn(cn[1], cn[4]); dz = __fsub_rn(cn[2], cn[5]);
     }
     ws.finish();
@@ -798,7 +805,7 @@ static int cv_split_fill(const char *who, CvSplitParams &P, int samples, int n1,
     P.blob = reinterpret_cast<const f4 *>(split_images);
     P.wsc = image_scales;
     P.wn.wa = wn[0].w_packed; P.wn.wb = wn[1].w_packed; P.wn.wc = wn[2].w_packed; P.wn.bb = wn[1].bias; P.wn.bc = wn[2].bias;
-    P.p1 = P.p2 = P.wd = P.bias2 = P.bias3 = nullptr;
+    P.p1 = P.p2 = P.st = P.wd = P.bias2 = P.bias3 = nullptr;
     P.out = nullptr; P.out_pitch = 0; P.sv1 = P.sv2 = P.sv3 = nullptr; P.mk1 = P.mk2 = nullptr; P.amax = nullptr;
     const int groups = (n1 + 2 * SP_NW - 1) / (2 * SP_NW);
     // one workgroup per CU (the tile keeps the whole register file); the rest is looped.  (Measured and rejected: 2 or 4 queued
@@ -821,7 +828,8 @@ static int cu_count() {
 static int cv_split_forward(const char *who, int samples, int n1, int n2, const float *xyz1, const float *xyz2, const int64_t *knn_idx,
                             const float *p1, const float *p2, const float *wd_packed, const void *split_images, const float *image_scales,
                             const float *bias2, const float *bias3, const rtk_layer_t *wn, float *out, int out_pitch, float *a1, float *a2,
-                            float *a3, void *mask1, void *mask2, float *amax, int workgroups, rtk_stream_t stream) {
+                            float *a3, void *mask1, void *mask2, float *amax, int workgroups, rtk_stream_t stream,
+                            const float *sample_term = nullptr) {
     CvSplitParams P;
     dim3 grid;
     if (cv_split_fill(who, P, samples, n1, n2, xyz1, xyz2, knn_idx, split_images, image_scales, wn, grid) != RTK_OK) return RTK_ERR_INVALID;
@@ -831,7 +839,7 @@ static int cv_split_forward(const char *who, int samples, int n1, int n2, const 
     const bool save = a1 != nullptr;
     RTK_REQUIRE(!save || ((double)samples * n1 * 16.0 * 1024.0 < 4294967296.0), "%s: more than 4 GiB per saved activation (32-bit row "
                 "offsets): split the batch", who);
-    P.p1 = p1; P.p2 = p2; P.wd = wd_packed; P.bias2 = bias2; P.bias3 = bias3; P.out = out; P.out_pitch = out_pitch;
+    P.p1 = p1; P.p2 = p2; P.st = sample_term; P.wd = wd_packed; P.bias2 = bias2; P.bias3 = bias3; P.out = out; P.out_pitch = out_pitch;
     P.sv1 = a1; P.sv2 = a2; P.sv3 = a3; P.mk1 = (uint2 *)mask1; P.mk2 = (uint2 *)mask2; P.amax = amax;
     if (samples % 8 == 0) {      // flattened tiles (see the kernel): `workgroups` of them, a multiple of 8, at most one per tile
         const int tiles_x = (samples / 8) * ((n1 + 2 * SP_NW - 1) / (2 * SP_NW));
@@ -862,6 +870,15 @@ extern "C" int rtk_cost_volume_split_shared(int samples, int n1, int n2, const f
     RTK_REQUIRE(workgroups >= 0, "cost_volume_split_shared: workgroups = %d", workgroups);
     return cv_split_forward("cost_volume_split_shared", samples, n1, n2, xyz1, xyz2, knn_idx, p1, p2, wd_packed, split_images, image_scales,
                             bias2, bias3, wn, out, out_pitch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workgroups, stream);
+}
+
+extern "C" int rtk_cost_volume_split_term(int samples, int n1, int n2, const float *xyz1, const float *xyz2, const int64_t *knn_idx,
+                                          const float *p1, const float *p2, const float *sample_term, const float *wd_packed,
+                                          const void *split_images, const float *image_scales, const float *bias2, const float *bias3,
+                                          const rtk_layer_t *wn, float *out, int out_pitch, int workgroups, rtk_stream_t stream) {
+    RTK_REQUIRE(workgroups >= 0 && sample_term, "cost_volume_split_term: workgroups = %d, sample_term = %p", workgroups, (const void *)sample_term);
+    return cv_split_forward("cost_volume_split_term", samples, n1, n2, xyz1, xyz2, knn_idx, p1, p2, wd_packed, split_images, image_scales,
+                            bias2, bias3, wn, out, out_pitch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workgroups, stream, sample_term);
 }
 
 extern "C" int rtk_cost_volume_split_train(int samples, int n1, int n2, const float *xyz1, const float *xyz2, const int64_t *knn_idx,

@@ -41,12 +41,15 @@ _vp, _ci = ctypes.c_void_p, ctypes.c_int
 _lib.SIGNATURES.update({
     "rtk_pointwise_mlp": [_ci, _ci, ctypes.POINTER(_Interp), _ci, ctypes.POINTER(_Src), _vp, _ci, ctypes.POINTER(_Layer), _vp,
                           _ci, _ci, _ci, _vp, _vp, _vp],
+    "rtk_pointwise_mlp_tap": [_ci, _ci, ctypes.POINTER(_Interp), ctypes.POINTER(_Layer), _vp, _ci, _vp, ctypes.POINTER(_Layer), _ci, _vp, _ci,
+                              _vp],
     "rtk_sa_scale": [_ci] * 4 + [_vp] * 4 + [_ci, _ci, _vp, _ci, ctypes.POINTER(_Layer), _vp, _ci, _ci, _vp, _vp, _vp],
     "rtk_cost_volume": [_ci] * 3 + [_vp] * 6 + [ctypes.POINTER(_Layer), ctypes.POINTER(_Layer), _vp, _ci, _vp],
     "rtk_patch_cost": [_ci] * 2 + [_vp] * 3 + [_ci, ctypes.POINTER(_Layer), _vp, _ci, _ci, _vp],
     "rtk_pack_split_layer": [_ci, _ci, _vp, _ci, _vp, _vp, _vp],
     "rtk_cost_volume_split": [_ci] * 3 + [_vp] * 10 + [ctypes.POINTER(_Layer), _vp, _ci, _vp],
     "rtk_cost_volume_split_shared": [_ci] * 3 + [_vp] * 10 + [ctypes.POINTER(_Layer), _vp, _ci, _ci, _vp],
+    "rtk_cost_volume_split_term": [_ci] * 3 + [_vp] * 11 + [ctypes.POINTER(_Layer), _vp, _ci, _ci, _vp],
     "rtk_split_mlp2": [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "rtk_sa_scale_split": [_ci] * 4 + [_vp] * 4 + [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp],
     "rtk_prepare_inputs": [_ci] * 2 + [_vp] * 6 + [_vp],
@@ -74,7 +77,7 @@ _lib.SIGNATURES.update({
 
 class _GtJob(ctypes.Structure):
     _fields_ = [("wt", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("out", ctypes.c_void_p), ("cout", ctypes.c_int), ("s0", ctypes.c_int),
-                ("count", ctypes.c_int), ("out_pitch", ctypes.c_int)]
+                ("count", ctypes.c_int), ("out_pitch", ctypes.c_int), ("wt2", ctypes.c_void_p), ("s2", ctypes.c_int)]
 
 
 class _CopyJob(ctypes.Structure):
@@ -334,6 +337,26 @@ def pointwise(rows, rows_per_sample, srcs, chain, out, out_channels=None, sample
 
 
 pointwise_mlp = pointwise
+
+
+def pointwise_tap(rows, rows_per_sample, chain, out, colmax, interp, proj, frame_split, proj_out):
+    """rtk_pointwise_mlp_tap: pointwise(rows, rows_per_sample, [], chain, out, interp=interp, colmax=colmax) for a one-layer split chain
+    on a 128-channel interpolation segment, and on the same tiles proj_out (rows, 256) = proj[0] (samples < frame_split) or proj[1]
+    (the others) applied to its output; proj: two one-layer 128 -> 256 chains without activation."""
+    assert PW_SPLIT and chain.n == 1 and all(c.n == 1 for c in proj)
+    kf, ch, m, idx, d2 = interp[:5]
+    nu = interp[5] if len(interp) > 5 else None
+    ptr, pitch = _colptr(kf)
+    ip = ctypes.pointer(_Interp(ptr, pitch, ch, m, idx.data_ptr(), d2.data_ptr(), nu.data_ptr() if nu is not None else None))
+    if _TRACE is not None:
+        _TRACE.append(("pointwise", rows, sum(co * ci for co, ci in chain.dims) + 3 * ch))
+        _TRACE.append(("pointwise", rows, sum(co * ci for co, ci in proj[0].dims)))
+    pa = (_Layer * 2)(proj[0].split_arr()[0], proj[1].split_arr()[0])
+    optr, opitch = _colptr(out)
+    pptr, ppitch = _colptr(proj_out)
+    _lib.call("rtk_pointwise_mlp_tap", rows, rows_per_sample, ip, chain.split_arr(), optr, opitch, colmax.data_ptr(), pa, frame_split,
+              pptr, ppitch, _stream())
+    return out, proj_out
 
 
 def offset_image(w4, device):
@@ -713,9 +736,11 @@ def sa_scale(geo, W, lvl, s, q, qcol, out, out_offset):
               sc.chain.n, sc.chain.arr, optr, opitch, out_offset, src_nu, geo.nuniq[lvl].data_ptr(), _stream())
 
 
-def run_pnhead(W, geo, q1, out=None, gmax=None):
+def run_pnhead(W, geo, q1, out=None, gmax=None, tap=None):
     """q1 (samples*n, 32): per-point sa1 layer-1 projections (scale 0 | scale 1).  Returns l0_points (samples*n, 128) (written
     into `out`, a possibly column-sliced (samples*n, 128) view, when given).
+    tap (encoder only): (proj chains (frame 1, frame 2), frame_split, proj_out (samples*n, 256)): the last layer also writes the
+    projections of its output (pointwise_tap).
     All centroid-level tensors hold valid data only in rows < geo.nuniq[level][sample]; the rest are duplicates of the
     sample's row 0 and are never read (consumers alias them)."""
     S_, n, S = geo.samples, geo.n, geo.npoint
@@ -747,8 +772,12 @@ def run_pnhead(W, geo, q1, out=None, gmax=None):
     d2, idx, m = geo.nn["fp1"]
     if gmax is None:                                                      # global max-pool, fused into fp1's epilogue (ZERO-initialised)
         gmax = torch.zeros(S_, 128, dtype=torch.float32, device=dev)
-    out = pointwise(S_ * n, n, [], W.fp["fp1"], out if out is not None else new(S_ * n, 128),
-                    interp=(f2, 128, m, idx.reshape(-1, 3), d2.reshape(-1, 3), nu[0]), colmax=gmax)
+    out = out if out is not None else new(S_ * n, 128)
+    interp = (f2, 128, m, idx.reshape(-1, 3), d2.reshape(-1, 3), nu[0])
+    if tap is not None:
+        pointwise_tap(S_ * n, n, W.fp["fp1"], out, gmax, interp, *tap)
+    else:
+        pointwise(S_ * n, n, [], W.fp["fp1"], out, interp=interp, colmax=gmax)
     return out, gmax
 
 
@@ -771,6 +800,8 @@ class FusedBackbone:
         self._split_hook = None
         self.side, self.use_side_stream = None, True    # geometry kernels on a forked stream (GraphPipeline drops it beyond depth 2)
         self.cv_shared = False                          # the cost volume on a share of the CUs (GraphPipeline sets it from depth 3)
+        self.proj_tap = True                            # split path: the encoder's last layer also writes the cost volume's projections
+                                                        # (False: the standalone launch sequence, the tests' comparison)
         self._last_cv = None
         self.enc = _PNHeadWeights(sd, "pn_head.", dev)
         self.dec = _PNHeadWeights(sd, "fd_layer.mse.", dev)
@@ -858,22 +889,35 @@ class FusedBackbone:
         # (B,256,N) tensors are permuted VIEWS of it -- no layout pass over the outputs
         feat12 = new(2 * B * N, 256)
         gmax = torch.zeros(3 * B, 128, dtype=torch.float32, device=dev)                  # both PNHeads' global max-pools: one fill
-        loc, glob = run_pnhead(self.enc, geo, q1, out=feat12[:, 0:128], gmax=gmax[:2 * B])   # (2B*N, 128) view, (2B, 128)
+        # split path: the encoder's last layer also writes the cost volume's first-layer projections of its output (frame 1 with
+        # p1_loc, frame 2 with p2_loc, no per-sample terms: those depend on the global max-pool that this very launch completes)
+        tap = self.proj_tap and self.cv_split and PW_SPLIT
+        p12 = new(2 * B * N, 256) if tap else None
+        loc, glob = run_pnhead(self.enc, geo, q1, out=feat12[:, 0:128], gmax=gmax[:2 * B],       # (2B*N, 128) view, (2B, 128)
+                               tap=((self.p1_loc, self.p2_loc), B, p12) if tap else None)
         f1, f2 = loc[:B * N], loc[B * N:]
         # everything that is a function of the global features, one launch: the per-sample terms of the cost volume's first layer
-        # (frame 1: with the layer's bias; frame 2) and of the decoder's sa1 projection, and the broadcast that fills the global half
-        # of pc{1,2}_features
-        sb1, sb2, sbq = new(B, 256), new(B, 256), new(B, 32)
-        global_terms(glob, [(self.p1_glob_wt, self.p1_glob_b, sb1, 0), (self.p2_glob_wt, None, sb2, B), (self.dec_q1_glob_wt, None, sbq, 0)],
-                     bcast=feat12[:, 128:], n=N)
+        # (frame 1: with the layer's bias; frame 2 -- on the split path as their sum, which the cost volume adds to the frame-1 rows)
+        # and of the decoder's sa1 projection, and the broadcast that fills the global half of pc{1,2}_features
+        sbq = new(B, 32)
+        if tap:
+            st = new(B, 256)
+            global_terms(glob, [(self.p1_glob_wt, self.p1_glob_b, st, 0, self.p2_glob_wt, B), (self.dec_q1_glob_wt, None, sbq, 0)],
+                         bcast=feat12[:, 128:], n=N)
+            p1, p2 = p12[:B * N], p12[B * N:]
+        else:
+            st = None
+            sb1, sb2 = new(B, 256), new(B, 256)
+            global_terms(glob, [(self.p1_glob_wt, self.p1_glob_b, sb1, 0), (self.p2_glob_wt, None, sb2, B), (self.dec_q1_glob_wt, None, sbq, 0)],
+                         bcast=feat12[:, 128:], n=N)
+            p1 = pointwise(B * N, N, [(f1, 128, False)], self.p1_loc, new(B * N, 256), sample_bias=sb1)
+            p2 = pointwise(B * N, N, [(f2, 128, False)], self.p2_loc, new(B * N, 256), sample_bias=sb2)
         # ---- cost volume ---------------------------------------------------------------------------------
-        p1 = pointwise(B * N, N, [(f1, 128, False)], self.p1_loc, new(B * N, 256), sample_bias=sb1)
-        p2 = pointwise(B * N, N, [(f2, 128, False)], self.p2_loc, new(B * N, 256), sample_bias=sb2)
         x1, x2 = xyz[:B], xyz[B:]
         geo.wait("knn")
         knn1, knn2 = geo.knn
         cor1 = new(B * N, 256)
-        self._last_cv = (B, N, x1, x2, knn1, p1, p2, cor1)
+        self._last_cv = (B, N, x1, x2, knn1, p1, p2, cor1, st)
         if self._split_hook is not None:
             # segmented capture (capture(split_cost_volume=True)): the graph ends here, the dominant kernel is launched
             # eagerly between two HIP events at replay time, a second graph takes over.  Every geometry stage has been
@@ -914,7 +958,9 @@ class FusedBackbone:
         return flow, h_out, cls, cor_cm, pc1_features, pc2_features, prop_cm
 
     # --------------------------------------------------------------------------------------------------
-    def _cost_volume(self, B, N, x1, x2, knn1, p1, p2, cor1):
+    def _cost_volume(self, B, N, x1, x2, knn1, p1, p2, cor1, sample_term=None):
+        """sample_term (B, 256) (split path only): layer 1's per-sample term, not folded into p1 (rtk_cost_volume_split_term)."""
+        assert sample_term is None or self.cv_split
         if _TRACE is not None:      # per (point, neighbour) pair: direction term, layers 2+3, WeightNet 3-8-8-256, weighted sum
             _TRACE.append(("cost_volume", B * N * 16, 3 * 256 + 2 * 256 * 256 + (3 * 8 + 8 * 8 + 8 * 256) + 256))
         if self.cv_split:
@@ -925,6 +971,12 @@ class FusedBackbone:
                 nb = min(step, B - b0)
                 wgs = cv_shared_workgroups(nb, N, x1.device) if self.cv_shared else 0
                 r0 = b0 * N
+                if sample_term is not None:
+                    _lib.call("rtk_cost_volume_split_term", nb, N, N, x1[b0:].data_ptr(), x2[b0:].data_ptr(), knn1[b0:].data_ptr(),
+                              p1[r0:].data_ptr(), p2[r0:].data_ptr(), sample_term[b0:].data_ptr(), self.cv_wd.data_ptr(),
+                              self.cv_images.data_ptr(), self.cv_scales.data_ptr(), self.cv_bias23[0].data_ptr(), self.cv_bias23[1].data_ptr(),
+                              self.wn1.arr, cor1[r0:].data_ptr(), 256, wgs, _stream())
+                    continue
                 _lib.call("rtk_cost_volume_split_shared", nb, N, N, x1[b0:].data_ptr(), x2[b0:].data_ptr(), knn1[b0:].data_ptr(), p1[r0:].data_ptr(),
                           p2[r0:].data_ptr(), self.cv_wd.data_ptr(), self.cv_images.data_ptr(), self.cv_scales.data_ptr(),
                           self.cv_bias23[0].data_ptr(), self.cv_bias23[1].data_ptr(), self.wn1.arr, cor1[r0:].data_ptr(), 256, wgs, _stream())
@@ -1038,16 +1090,22 @@ class FusedBackbone:
 
 
 def global_terms(g, jobs, bcast=None, n=0):
-    """rtk_global_terms: g (samples, cin); jobs [(wt (cin, cout), bias (cout) or None, out (count, cout), s0)]: out = W g[s0 : s0 + count] + b;
-    bcast (samples * n, pitch) view: g[s] copied into its first cin columns for every row of sample s."""
+    """rtk_global_terms: g (samples, cin); jobs [(wt (cin, cout), bias (cout) or None, out (count, cout), s0[, wt2 (cin, cout), s2])]:
+    out = W g[s0 : s0 + count] + b, paired jobs (with wt2): out = (W g[s0 : s0 + count] + b) + W2 g[s2 : s2 + count] (the two maps
+    rounded as two jobs would be, then added); bcast (samples * n, pitch) view: g[s] copied into its first cin columns for every row of
+    sample s."""
     samples, cin = g.shape
     arr = (_GtJob * max(len(jobs), 1))()
-    for j, (wt, bias, out, s0) in enumerate(jobs):
+    for j, job in enumerate(jobs):
+        wt, bias, out, s0 = job[:4]
+        wt2, s2 = job[4:] if len(job) > 4 else (None, 0)
         assert wt.shape == (cin, out.shape[1]) and out.is_contiguous() and wt.is_contiguous()
+        assert wt2 is None or (wt2.shape == wt.shape and wt2.is_contiguous())
         arr[j].wt, arr[j].bias, arr[j].out = wt.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr()
         arr[j].cout, arr[j].s0, arr[j].count, arr[j].out_pitch = out.shape[1], s0, out.shape[0], out.shape[1]
+        arr[j].wt2, arr[j].s2 = wt2.data_ptr() if wt2 is not None else None, s2
     if _TRACE is not None:
-        _TRACE.append(("global_terms", 1, sum(cin * o.shape[0] * o.shape[1] for _, _, o, _ in jobs)))
+        _TRACE.append(("global_terms", 1, sum(cin * j[2].shape[0] * j[2].shape[1] * (2 if len(j) > 4 else 1) for j in jobs)))
     bptr, bpitch = _colptr(bcast) if bcast is not None else (None, 0)
     _lib.call("rtk_global_terms", samples, cin, g.data_ptr(), len(jobs), arr, bptr, bpitch, n, _stream())
 

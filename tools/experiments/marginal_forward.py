@@ -19,7 +19,7 @@ for i in range(8):
     d = synth.make_frame_pairs(64, 256, 1000 + 100 * i)
     batches.append([torch.from_numpy(d[k]).to(dev) for k in ("pc1", "pc2", "feature1", "feature2")] + [torch.zeros(5, 64, 128, device=dev)])
 FAM = {"cost_volume": ["rtk_cost_volume_split", "rtk_cost_volume_split_shared"], "sa_scale": ["rtk_sa_scale", "rtk_sa_scale_split"],
-       "pointwise": ["rtk_pointwise_mlp"], "patch_cost": ["rtk_patch_cost"], "gru": ["rtk_gru_step_head"], "global_terms": ["rtk_global_terms"],
+       "pointwise": ["rtk_pointwise_mlp", "rtk_pointwise_mlp_tap"], "patch_cost": ["rtk_patch_cost"], "gru": ["rtk_gru_step_head"], "global_terms": ["rtk_global_terms"],
        "geometry_front": ["rtk_geometry_front"], "geometry_tables": ["rtk_geometry_tables"], "input copy": ["rtk_copy_multi"]}
 orig = _lib.call
 
