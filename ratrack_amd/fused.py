@@ -88,6 +88,10 @@ _lib.SIGNATURES.update({
     "rtk_gru_step_head": [_ci] * 3 + [_vp] * 11 + [_ci, _vp],
     "rtk_global_terms": [_ci, _ci, _vp, _ci, ctypes.POINTER(_GtJob), _vp, _ci, _ci, _vp],
     "rtk_copy_multi": [_ci, ctypes.POINTER(_CopyJob), _vp],
+    # device-side ground truth and scoring (include/rtk_gt.h, ratrack_amd/gt_device.py); the argument blocks are rtk_gt_in_t /
+    # rtk_gt_out_t / rtk_eval_in_t (gt_device.GtIn, GtOut, EvalIn), passed by address
+    "rtk_gt_labels": [_vp, _vp, _vp],
+    "rtk_eval_frame": [_vp, _vp, _vp, _vp],
 })
 
 

@@ -18,6 +18,11 @@ Host-side numpy / torch code, like the reference's (the epoch loop builds the GT
   tie rule (which depends on the cloud size) by the kernels -- so the valid part of every padded sample equals its own B = 1
   run (tests/test_vod_gt_cpu.py, tests/test_fused_gpu.py::test_padded_variable_n_batch).
 
+Device path: `ratrack_amd.gt_device` computes the membership / ids of `filter_object_points` and the warped positions of
+`gt_scene_flow` for a whole batch of frame pairs in one HIP launch (`pack_boxes` + `ground_truth`, include/rtk_gt.h), from the boxes
+this module makes; the functions here stay the host statement it is tested against, and the only home of the rider merge, the
+minimum object size and `map_gt_objects`.
+
 Third-party dependency of the reference that is absent here: Open3D 0.18.0 (src/environment.yml).  Its
 `OrientedBoundingBox(center, R, extent).get_point_indices_within_bounding_box(points)` is restated from its published
 implementation (cpp/open3d/geometry/BoundingVolume.cpp): with the box axes d_k = R e_k, a point p is inside iff
