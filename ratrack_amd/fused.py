@@ -92,6 +92,12 @@ _lib.SIGNATURES.update({
     # rtk_gt_out_t / rtk_eval_in_t (gt_device.GtIn, GtOut, EvalIn), passed by address
     "rtk_gt_labels": [_vp, _vp, _vp],
     "rtk_eval_frame": [_vp, _vp, _vp, _vp],
+    # ground-truth objects and the tracking score (include/rtk_score.h, ratrack_amd/track_score.py): rtk_gt_objects_in_t / _out_t and
+    # rtk_track_score_in_t / _state_t / _out_t by address; the two *_lds_bytes are host functions that return a byte count
+    "rtk_gt_objects": [_vp, _vp, _vp],
+    "rtk_track_score": [_vp, _vp, _vp, _vp],
+    "rtk_gt_objects_lds_bytes": [_ci, _ci],
+    "rtk_track_score_lds_bytes": [_ci, _ci, _ci],
 })
 
 

@@ -11,8 +11,9 @@ point carries) and `vod_gt.gt_scene_flow` compute on the host for that stream's 
 `mask[0]` is an artefact of the reference's B = 1).  Nothing here synchronises with the device except `GroundTruth.check()`,
 `FrameMetrics.stream()` and `MetricAccumulator.result()`.
 
-Not covered (host code as before): the rider merge and the minimum object size (`objs_combined`), `map_gt_objects`, the tracking
-loss, label-file parsing.
+Not covered here: the rider merge and the minimum object size (`objs_combined`), `map_gt_objects` and the target of the tracking
+loss are `ratrack_amd.track_score` (two more launches over the same `BoxBatch`); training the tracking term and label-file parsing
+stay host code.
 """
 import ctypes
 

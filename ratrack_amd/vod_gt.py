@@ -20,8 +20,8 @@ Host-side numpy / torch code, like the reference's (the epoch loop builds the GT
 
 Device path: `ratrack_amd.gt_device` computes the membership / ids of `filter_object_points` and the warped positions of
 `gt_scene_flow` for a whole batch of frame pairs in one HIP launch (`pack_boxes` + `ground_truth`, include/rtk_gt.h), from the boxes
-this module makes; the functions here stay the host statement it is tested against, and the only home of the rider merge, the
-minimum object size and `map_gt_objects`.
+this module makes, and `ratrack_amd.track_score` the rider merge, the minimum object size and `map_gt_objects` in two more
+(include/rtk_score.h); the functions here stay the host statement both are tested against.
 
 Third-party dependency of the reference that is absent here: Open3D 0.18.0 (src/environment.yml).  Its
 `OrientedBoundingBox(center, R, extent).get_point_indices_within_bounding_box(points)` is restated from its published
