@@ -1,32 +1,15 @@
-"""ctypes binding of librtk_hip.so (the C ABI declared in include/rtk_pointnet2.h).
+"""ctypes binding of librtk_hip.so (the C ABI declared in include/*.h and restated once, in abi.py).
 
 There is NO CPU or eager fallback: if the HIP library is missing or fails to load, every op raises.
 """
 import ctypes
 import os
 
+from .abi import SIGNATURES      # name -> argtypes (restype is always int)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 SO_PATH = os.path.join(_HERE, "lib", "librtk_hip.so")
-
-_c_int, _c_float, _c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
-
-# name -> argtypes (restype is always int); mirrors include/rtk_pointnet2.h one to one
-SIGNATURES = {
-    "rtk_furthest_point_sampling": [_c_int] * 3 + [_c_void_p] * 3 + [_c_void_p],
-    "rtk_gather_points": [_c_int] * 4 + [_c_void_p] * 3 + [_c_void_p],
-    "rtk_gather_points_grad": [_c_int] * 4 + [_c_void_p] * 3 + [_c_void_p],
-    "rtk_ball_query": [_c_int] * 3 + [_c_float, _c_int] + [_c_void_p] * 3 + [_c_void_p],
-    "rtk_group_points": [_c_int] * 5 + [_c_void_p] * 3 + [_c_void_p],
-    "rtk_group_points_grad": [_c_int] * 5 + [_c_void_p] * 3 + [_c_void_p],
-    "rtk_group_points_grad_set": [_c_int] * 5 + [_c_void_p] * 3 + [_c_void_p],
-    "rtk_three_nn": [_c_int] * 3 + [_c_void_p] * 4 + [_c_void_p],
-    "rtk_knn": [_c_int] * 4 + [_c_void_p] * 4 + [_c_void_p],
-    "rtk_three_interpolate": [_c_int] * 4 + [_c_void_p] * 4 + [_c_void_p],
-    "rtk_three_interpolate_grad": [_c_int] * 4 + [_c_void_p] * 4 + [_c_void_p],
-    "rtk_three_interpolate_grad_set": [_c_int] * 4 + [_c_void_p] * 4 + [_c_void_p],
-    "rtk_knn_point": [_c_int] * 4 + [_c_void_p] * 3 + [_c_void_p],
-}
 
 _lib = None
 
@@ -53,7 +36,7 @@ def load():
     except OSError as e:  # e.g. libamdhip64 missing
         raise RtkError("cannot load %s: %s" % (SO_PATH, e))
     lib.rtk_last_error.restype = ctypes.c_char_p
-    lib.rtk_version.restype = _c_int
+    lib.rtk_version.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -66,7 +49,7 @@ def _fn(name):
     if fn is None:
         fn = getattr(load(), name)        # AttributeError if the library does not export it
         fn.argtypes = SIGNATURES[name]
-        fn.restype = _c_int
+        fn.restype = ctypes.c_int
         _bound[name] = fn
     return fn
 

@@ -77,7 +77,8 @@ def cluster_objects_device(point_features, cls, eps=1.5, min_samples=2, threshol
     host-side clustering: ONE kernel (rtk_dbscan: mover selection + DBSCAN, labels identical to `dbscan`) and ONE small
     device->host copy of the per-point labels (the object list is host-structured: a dict of per-object tensors).
     point_features (1,139,N) CUDA fp32, cls (1,N) motion-segmentation probabilities."""
-    from . import _lib, fused  # noqa: F401  (fused registers the signatures)
+    from . import _lib
+    from .abi import stream
     pf = point_features.contiguous()
     n = pf.shape[2]
     dev = pf.device
@@ -87,7 +88,7 @@ def cluster_objects_device(point_features, cls, eps=1.5, min_samples=2, threshol
     score = cls.detach().reshape(-1).contiguous().float()
     labels = torch.empty(n, dtype=torch.int32, device=dev)
     _lib.call("rtk_dbscan", n, pf.detach().data_ptr(), n, chan.data_ptr(), score.data_ptr(), float(threshold), float(eps), int(min_samples),
-              labels.data_ptr(), torch.cuda.current_stream().cuda_stream)
+              labels.data_ptr(), stream())
     lab = labels.cpu().numpy()
     pts = np.nonzero(lab >= 0)[0]
     if pts.size == 0:
@@ -199,12 +200,12 @@ def log_optimal_transport(scores, alpha, iters):
 
 def _log_optimal_transport_hip(aff_mat, alpha, iters):
     """log_optimal_transport on the GPU as ONE kernel (rtk_log_sinkhorn) instead of ~8 framework kernels per iteration."""
-    from . import _lib, fused  # noqa: F401  (fused registers the signature)
+    from . import _lib
+    from .abi import stream
     _, m, n = aff_mat.shape
     scores = aff_mat.detach().reshape(m, n).contiguous().float()
     out = torch.empty(1, m + 1, n + 1, dtype=torch.float32, device=aff_mat.device)
-    _lib.call("rtk_log_sinkhorn", m, n, scores.data_ptr(), float(alpha), int(iters), out.data_ptr(),
-              torch.cuda.current_stream().cuda_stream)
+    _lib.call("rtk_log_sinkhorn", m, n, scores.data_ptr(), float(alpha), int(iters), out.data_ptr(), stream())
     return out
 
 

@@ -127,7 +127,6 @@ def irregular_ops(batch, n, dev, npoint=512, iters=20, pmc=None):
     M = batch * n * 16
     src_rows = torch.randn(M, 256, device=dev)
     dst_rows = f32(batch * n, 256)
-    from . import train_ops  # noqa: F401  (registers the signatures)
     ms = _time(lambda: _lib.call("rtk_scatter_add_rows", batch, n * 16, n, 256, knn.data_ptr(), src_rows.data_ptr(), dst_rows.data_ptr(),
                                  st()), iters)
     add("scatter_add_rows_kernel", 2, ms, M * 256 * 4 + M * 8 + batch * n * 256 * 4,

@@ -1,0 +1,26 @@
+// batch_common.h -- device helpers shared by the kernels that work on B streams at once (gt_eval.hip, track_score.hip,
+// track_batched.hip): one definition of each, so that the contract they carry is stated once.
+#pragma once
+
+#include "rtk_common.h"
+#include "rtk_fused.h"
+
+// element (b, c, p) of a (B,C,N) or (B,N) fp32 tensor read in place through its strides
+__device__ __forceinline__ float bcn_at(const rtk_bcn_view_t &v, int b, int c, int p) {
+    return v.ptr[(long long)b * v.sb + (long long)c * v.sc + (long long)p * v.sp];
+}
+
+// a count read from the device, brought into [0, hi]
+__device__ __forceinline__ int count_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// |(p - c) . R[:,k]| <= half_k on the three axes, closed; the operation order is part of the contract (rtk_gt.h).
+__device__ __forceinline__ bool box_inside(const double *bx, double x, double y, double z) {
+    const double d0 = x - bx[0], d1 = y - bx[1], d2 = z - bx[2];
+    bool in = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double pr = (d0 * bx[3 + k] + d1 * bx[6 + k]) + d2 * bx[9 + k];
+        in = in && (fabs(pr) <= bx[12 + k]);
+    }
+    return in;
+}

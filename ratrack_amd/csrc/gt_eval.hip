@@ -18,29 +18,12 @@
 // arithmetic is the application of the box motion, which the reference also does in fp32.
 #include <math.h>
 
+#include "batch_common.h"
 #include "rtk_common.h"
 #include "rtk_gt.h"
 
 #define GT_THREADS 256
 #define GT_WAVES (GT_THREADS / RTK_WAVE)
-
-__device__ __forceinline__ float gt_at(const rtk_bcn_view_t &v, int b, int c, int p) {
-    return v.ptr[(long long)b * v.sb + (long long)c * v.sc + (long long)p * v.sp];
-}
-
-__device__ __forceinline__ int gt_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// |(p - c) . R[:,k]| <= half_k on the three axes, closed; the operation order is part of the contract (rtk_gt.h).
-__device__ __forceinline__ bool gt_inside(const double *bx, double x, double y, double z) {
-    const double d0 = x - bx[0], d1 = y - bx[1], d2 = z - bx[2];
-    bool in = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double pr = (d0 * bx[3 + k] + d1 * bx[6 + k]) + d2 * bx[9 + k];
-        in = in && (fabs(pr) <= bx[12 + k]);
-    }
-    return in;
-}
 
 // per-stream LDS: box1[K][16] | box2[K][16] (float64) | motion[K][12] (fp32) | pair[K] | id1[K] | c1[K] | c2[K] (int32)
 static size_t gt_lds_bytes(int K) { return (size_t)K * (2 * RTK_GT_BOX_WORDS * sizeof(double) + 12 * sizeof(float) + 4 * sizeof(int)); }
@@ -54,9 +37,9 @@ __global__ __launch_bounds__(GT_THREADS) void gt_labels_kernel(const rtk_gt_in_t
     int *pair = reinterpret_cast<int *>(mot + (size_t)K * 12), *id1 = pair + K, *c1 = id1 + K, *c2 = c1 + K;
 
     const int raw1 = in.frame1.count[b], raw2 = in.frame2.count[b];
-    const int cnt1 = gt_clamp(raw1, K), cnt2 = gt_clamp(raw2, K);
+    const int cnt1 = count_clamp(raw1, K), cnt2 = count_clamp(raw2, K);
     const int nv1 = in.n_valid ? in.n_valid[b] : N, nv2 = in.n_valid ? in.n_valid[in.B + b] : N2;
-    const int n1 = gt_clamp(nv1, N), n2 = gt_clamp(nv2, N2);
+    const int n1 = count_clamp(nv1, N), n2 = count_clamp(nv2, N2);
     if (t == 0) out.flags[b] = ((raw1 != cnt1 || raw2 != cnt2) ? 1 : 0) | ((nv1 != n1 || nv2 != n2) ? 2 : 0);
 
     const size_t kb = (size_t)b * K;
@@ -77,9 +60,9 @@ __global__ __launch_bounds__(GT_THREADS) void gt_labels_kernel(const rtk_gt_in_t
         const int p = base + t;
         const bool live = p < n2;
         double x = 0.0, y = 0.0, z = 0.0;
-        if (live) { x = (double)gt_at(in.pc2, b, 0, p); y = (double)gt_at(in.pc2, b, 1, p); z = (double)gt_at(in.pc2, b, 2, p); }
+        if (live) { x = (double)bcn_at(in.pc2, b, 0, p); y = (double)bcn_at(in.pc2, b, 1, p); z = (double)bcn_at(in.pc2, b, 2, p); }
         for (int k = 0; k < cnt2; ++k) {
-            const bool hit = live && gt_inside(box2 + (size_t)k * RTK_GT_BOX_WORDS, x, y, z);
+            const bool hit = live && box_inside(box2 + (size_t)k * RTK_GT_BOX_WORDS, x, y, z);
             const unsigned long long m = __ballot(hit);
             if (lane == 0 && m) atomicAdd(&c2[k], __popcll(m));
         }
@@ -93,11 +76,11 @@ __global__ __launch_bounds__(GT_THREADS) void gt_labels_kernel(const rtk_gt_in_t
         const int p = base + t;
         const bool col = p < N, live = p < n1;
         float xf = 0.f, yf = 0.f, zf = 0.f;
-        if (col) { xf = gt_at(in.pc1, b, 0, p); yf = gt_at(in.pc1, b, 1, p); zf = gt_at(in.pc1, b, 2, p); }
+        if (col) { xf = bcn_at(in.pc1, b, 0, p); yf = bcn_at(in.pc1, b, 1, p); zf = bcn_at(in.pc1, b, 2, p); }
         const double x = (double)xf, y = (double)yf, z = (double)zf;
         int last = -1;
         for (int k = 0; k < cnt1; ++k) {
-            const bool hit = live && gt_inside(box1 + (size_t)k * RTK_GT_BOX_WORDS, x, y, z);
+            const bool hit = live && box_inside(box1 + (size_t)k * RTK_GT_BOX_WORDS, x, y, z);
             const unsigned long long m = __ballot(hit);
             if (lane == 0 && m) atomicAdd(&c1[k], __popcll(m));
             last = hit ? k : last;
@@ -179,7 +162,7 @@ __global__ __launch_bounds__(GT_THREADS) void eval_frame_kernel(const rtk_eval_i
         if (t < RTK_EVAL_VALUES) V[t] = 0.0;
         return;
     }
-    const int n = in.n_valid ? gt_clamp(in.n_valid[b], N) : N;
+    const int n = in.n_valid ? count_clamp(in.n_valid[b], N) : N;
     // LRR30 radar / HDL-64E lidar: range (m), elevation, azimuth (rad)
     const double pi = 3.141592653589793;
     const double res_radar[3] = {0.2, 1.0 * pi / 180, 1.6 * pi / 180};
@@ -190,11 +173,11 @@ __global__ __launch_bounds__(GT_THREADS) void eval_frame_kernel(const rtk_eval_i
     const float *mask = in.mask + (size_t)b * N;
     const unsigned char *gcls = in.gt_cls + (size_t)b * N;
     for (int p = t; p < n; p += GT_THREADS) {
-        const double x = (double)gt_at(in.pc1, b, 0, p), y = (double)gt_at(in.pc1, b, 1, p), z = (double)gt_at(in.pc1, b, 2, p);
+        const double x = (double)bcn_at(in.pc1, b, 0, p), y = (double)bcn_at(in.pc1, b, 1, p), z = (double)bcn_at(in.pc1, b, 2, p);
         double e2 = 0.0, l2 = 0.0;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const double w = (double)gt_at(in.warp, b, j, p), g = (double)gt_at(in.gt_warp, b, j, p), d = w - g;
+            const double w = (double)bcn_at(in.warp, b, j, p), g = (double)bcn_at(in.gt_warp, b, j, p), d = w - g;
             e2 += d * d;
             l2 += g * g;
         }
@@ -214,7 +197,7 @@ __global__ __launch_bounds__(GT_THREADS) void eval_frame_kernel(const rtk_eval_i
         const double rel = rn / gt_len;
         if (rn <= 0.10 || rel <= 0.10) acc[7] += 1.0;
         if (rn <= 0.20 || rel <= 0.20) acc[8] += 1.0;
-        const bool pre = gt_at(in.cls, b, 0, p) > in.threshold, gt = gcls[p] != 0;
+        const bool pre = bcn_at(in.cls, b, 0, p) > in.threshold, gt = gcls[p] != 0;
         acc[9] += (pre && gt) ? 1.0 : 0.0;        // tp
         acc[10] += (!pre && !gt) ? 1.0 : 0.0;     // tn
         acc[11] += (pre && !gt) ? 1.0 : 0.0;      // fp

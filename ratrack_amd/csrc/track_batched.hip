@@ -15,14 +15,11 @@
 #include <math.h>
 
 #include "assoc_common.h"
+#include "batch_common.h"
 #include "rtk_common.h"
 #include "rtk_fused.h"
 
 #define DB_LDS_BYTES (128 * 1024)
-
-__device__ __forceinline__ float bcn_at(const rtk_bcn_view_t &v, int b, int c, int p) {
-    return v.ptr[(long long)b * v.sb + (long long)c * v.sc + (long long)p * v.sp];
-}
 
 __device__ __forceinline__ bool stream_active(const rtk_track_frame_t &fr, int b) { return !fr.active || fr.active[b]; }
 

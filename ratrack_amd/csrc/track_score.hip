@@ -24,29 +24,12 @@
 // prediction order by that one thread.
 #include <math.h>
 
+#include "batch_common.h"
 #include "rtk_common.h"
 #include "rtk_score.h"
 
 #define TS_THREADS 256
 #define TS_WAVES (TS_THREADS / RTK_WAVE)
-
-__device__ __forceinline__ float ts_at(const rtk_bcn_view_t &v, int b, int c, int p) {
-    return v.ptr[(long long)b * v.sb + (long long)c * v.sc + (long long)p * v.sp];
-}
-
-__device__ __forceinline__ int ts_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// rtk_gt_labels' box test (gt_eval.hip gt_inside): the operation order is part of the contract (rtk_gt.h)
-__device__ __forceinline__ bool ts_inside(const double *bx, double x, double y, double z) {
-    const double d0 = x - bx[0], d1 = y - bx[1], d2 = z - bx[2];
-    bool in = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double pr = (d0 * bx[3 + k] + d1 * bx[6 + k]) + d2 * bx[9 + k];
-        in = in && (fabs(pr) <= bx[12 + k]);
-    }
-    return in;
-}
 
 // masks are written two words (one wave) at a time: an even number of words per row
 static inline int ts_row_words(int N) { return 2 * ((N + 63) / 64); }
@@ -74,14 +57,14 @@ __global__ __launch_bounds__(TS_THREADS) void gt_objects_kernel(const rtk_gt_obj
     unsigned *cur = reinterpret_cast<unsigned *>(centre + (size_t)K * 3), *canon = cur + (size_t)K * WR;
     int *cnt = reinterpret_cast<int *>(canon + WR), *near = cnt + K, *state = near + K, *size = state + K;
 
-    const int raw = in.frame1.count[b], nb = ts_clamp(raw, K);
-    const int nv = in.n_valid ? in.n_valid[b] : N, n = ts_clamp(nv, N);
+    const int raw = in.frame1.count[b], nb = count_clamp(raw, K);
+    const int nv = in.n_valid ? in.n_valid[b] : N, n = count_clamp(nv, N);
     if (t == 0) out.flags[b] = (raw != nb ? RTK_SCORE_FLAG_BOXES : 0) | (nv != n ? RTK_SCORE_FLAG_NVALID : 0);
     const size_t kb = (size_t)b * K;
     for (int e = t; e < nb * RTK_GT_BOX_WORDS; e += TS_THREADS) box[e] = in.frame1.boxes[kb * RTK_GT_BOX_WORDS + e];
     for (int p = t; p < N; p += TS_THREADS) {
         const bool live = p < n;
-        pts[p] = make_float4(live ? ts_at(in.pc1, b, 0, p) : 0.f, live ? ts_at(in.pc1, b, 1, p) : 0.f, live ? ts_at(in.pc1, b, 2, p) : 0.f, 0.f);
+        pts[p] = make_float4(live ? bcn_at(in.pc1, b, 0, p) : 0.f, live ? bcn_at(in.pc1, b, 1, p) : 0.f, live ? bcn_at(in.pc1, b, 2, p) : 0.f, 0.f);
     }
     __syncthreads();
 
@@ -94,7 +77,7 @@ __global__ __launch_bounds__(TS_THREADS) void gt_objects_kernel(const rtk_gt_obj
         const double x = (double)xf, y = (double)yf, z = (double)zf;
         const int w = (p >> 6) * 2;               // the wave's two words (p < WR * 32 for the whole wave, or for none of it)
         for (int k = 0; k < nb; ++k) {
-            const unsigned long long m = __ballot(live && ts_inside(box + (size_t)k * RTK_GT_BOX_WORDS, x, y, z));
+            const unsigned long long m = __ballot(live && box_inside(box + (size_t)k * RTK_GT_BOX_WORDS, x, y, z));
             if (lane == 0 && p < WR * 32) {
                 cur[(size_t)k * WR + w] = (unsigned)m;
                 cur[(size_t)k * WR + w + 1] = (unsigned)(m >> 32);
@@ -265,11 +248,11 @@ __global__ __launch_bounds__(TS_THREADS) void track_score_kernel(const rtk_track
         if (t == 0) out.aff_defined[b] = 0;
         return;
     }
-    const int nv = in.n_valid ? in.n_valid[b] : N, n = ts_clamp(nv, N);
-    const int rawp = in.num_objects[b], P = ts_clamp(rawp, Kobj);
-    const int G = ts_clamp(in.gt_count[b], K);
+    const int nv = in.n_valid ? in.n_valid[b] : N, n = count_clamp(nv, N);
+    const int rawp = in.num_objects[b], P = count_clamp(rawp, Kobj);
+    const int G = count_clamp(in.gt_count[b], K);
     const bool reset = in.reset && in.reset[b];
-    int used = ts_clamp(st.table_used[b], T);
+    int used = count_clamp(st.table_used[b], T);
     int prevP = st.prev_count[b], prevG = st.prev_gt[b];
     long long *cnt = st.counters + (size_t)b * RTK_SCORE_COUNTERS;
 
@@ -309,7 +292,7 @@ __global__ __launch_bounds__(TS_THREADS) void track_score_kernel(const rtk_track
     // ---- this frame's tables: coordinates, the kept objects of every column, the two compacted lists ----
     for (int p = t; p < N; p += TS_THREADS) {
         const bool live = p < n;
-        pts[p] = make_float4(live ? ts_at(in.pc1, b, 0, p) : 0.f, live ? ts_at(in.pc1, b, 1, p) : 0.f, live ? ts_at(in.pc1, b, 2, p) : 0.f, 0.f);
+        pts[p] = make_float4(live ? bcn_at(in.pc1, b, 0, p) : 0.f, live ? bcn_at(in.pc1, b, 1, p) : 0.f, live ? bcn_at(in.pc1, b, 2, p) : 0.f, 0.f);
         unsigned long long m = 0ull;
         if (live) {
             for (int j = 0; j < G; ++j)

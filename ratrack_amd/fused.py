@@ -18,87 +18,9 @@ import torch
 
 from . import _lib
 from . import pointnet2_hip as _native
+from .abi import CopyJob as _CopyJob, GtermJob as _GtJob, Interp as _Interp, Layer as _Layer, Src as _Src, stream as _stream
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
-
-
-# ---- ctypes mirrors of the structs in include/rtk_fused.h -------------------------------------------
-class _Src(ctypes.Structure):
-    _fields_ = [("ptr", ctypes.c_void_p), ("pitch", ctypes.c_int), ("channels", ctypes.c_int), ("per_sample", ctypes.c_int)]
-
-
-class _Layer(ctypes.Structure):
-    _fields_ = [("w_packed", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("cin16", ctypes.c_int), ("cout16", ctypes.c_int),
-                ("act", ctypes.c_int), ("inv_scale", ctypes.c_float)]
-
-
-class _Interp(ctypes.Structure):
-    _fields_ = [("known_feats", ctypes.c_void_p), ("pitch", ctypes.c_int), ("channels", ctypes.c_int), ("m", ctypes.c_int),
-                ("idx", ctypes.c_void_p), ("dist2", ctypes.c_void_p), ("nuniq", ctypes.c_void_p)]
-
-
-_vp, _ci = ctypes.c_void_p, ctypes.c_int
-_lib.SIGNATURES.update({
-    "rtk_pointwise_mlp": [_ci, _ci, ctypes.POINTER(_Interp), _ci, ctypes.POINTER(_Src), _vp, _ci, ctypes.POINTER(_Layer), _vp,
-                          _ci, _ci, _ci, _vp, _vp, _vp],
-    "rtk_pointwise_mlp_tap": [_ci, _ci, ctypes.POINTER(_Interp), ctypes.POINTER(_Layer), _vp, _ci, _vp, ctypes.POINTER(_Layer), _ci, _vp, _ci,
-                              _vp],
-    "rtk_sa_scale": [_ci] * 4 + [_vp] * 4 + [_ci, _ci, _vp, _ci, ctypes.POINTER(_Layer), _vp, _ci, _ci, _vp, _vp, _vp],
-    "rtk_cost_volume": [_ci] * 3 + [_vp] * 6 + [ctypes.POINTER(_Layer), ctypes.POINTER(_Layer), _vp, _ci, _vp],
-    "rtk_patch_cost": [_ci] * 2 + [_vp] * 3 + [_ci, ctypes.POINTER(_Layer), _vp, _ci, _ci, _vp],
-    "rtk_pack_split_layer": [_ci, _ci, _vp, _ci, _vp, _vp, _vp],
-    "rtk_cost_volume_split": [_ci] * 3 + [_vp] * 10 + [ctypes.POINTER(_Layer), _vp, _ci, _vp],
-    "rtk_cost_volume_split_shared": [_ci] * 3 + [_vp] * 10 + [ctypes.POINTER(_Layer), _vp, _ci, _ci, _vp],
-    "rtk_cost_volume_split_term": [_ci] * 3 + [_vp] * 11 + [ctypes.POINTER(_Layer), _vp, _ci, _ci, _vp],
-    "rtk_split_mlp2": [_ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rtk_sa_scale_split": [_ci] * 4 + [_vp] * 4 + [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp],
-    "rtk_prepare_inputs": [_ci] * 2 + [_vp] * 6 + [_vp],
-    "rtk_fps_centroids": [_ci] * 3 + [_vp] * 8 + [_vp],
-    "rtk_knn_point_masked": [_ci] * 4 + [_vp] * 4 + [_vp],
-    "rtk_fps_relevel": [_ci] * 3 + [_vp] * 9 + [_ci, _vp, _vp],
-    "rtk_gru_step": [_ci] * 3 + [_vp] * 8 + [_vp],
-    "rtk_to_channel_major": [_ci] * 3 + [_vp, _ci, _ci, _vp, _ci, _ci, _vp],
-    "rtk_ball_query_pair": [_ci] * 3 + [ctypes.c_float, _ci, ctypes.c_float, _ci] + [_vp] * 5 + [_vp],
-    "rtk_geometry_front": [_ci] * 4 + [_vp, _vp, _ci] + [_vp] * 13 + [_vp, _vp, _ci, _vp],
-    "rtk_geometry_tables": [_ci] * 3 + [_vp] * 3 + [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_ci), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                            ctypes.POINTER(_vp), _vp],
-    "rtk_three_nn_masked": [_ci] * 3 + [_vp] * 6 + [_vp],
-    "rtk_to_channel_major_multi": [_ci] * 3 + [_vp, _vp],
-    "rtk_log_sinkhorn": [_ci, _ci, _vp, ctypes.c_float, _ci, _vp, _vp],
-    "rtk_dbscan": [_ci, _vp, _ci, _vp, _vp, ctypes.c_float, ctypes.c_double, _ci, _vp, _vp],
-    # batched tracking (ratrack_amd/tracker.py); the frame struct is rtk_track_frame_t (tracker.TrackFrame)
-    "rtk_dbscan_batched": [_vp, ctypes.c_float, ctypes.c_double, _ci, _ci, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp],
-    "rtk_object_descriptors": [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp],
-    "rtk_affinity_pairs": [_ci, _ci] + [_vp] * 7 + [_vp],
-    "rtk_associate_batched": [_ci] * 3 + [_vp] * 7 + [ctypes.c_float, _ci] + [_vp] * 9 + [_vp],
-    "rtk_track_max_objects": [],
-})
-
-
-class _GtJob(ctypes.Structure):
-    _fields_ = [("wt", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("out", ctypes.c_void_p), ("cout", ctypes.c_int), ("s0", ctypes.c_int),
-                ("count", ctypes.c_int), ("out_pitch", ctypes.c_int), ("wt2", ctypes.c_void_p), ("s2", ctypes.c_int)]
-
-
-class _CopyJob(ctypes.Structure):
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("bytes", ctypes.c_long)]
-
-
-_lib.SIGNATURES.update({
-    "rtk_gru_step_head": [_ci] * 3 + [_vp] * 11 + [_ci, _vp],
-    "rtk_global_terms": [_ci, _ci, _vp, _ci, ctypes.POINTER(_GtJob), _vp, _ci, _ci, _vp],
-    "rtk_copy_multi": [_ci, ctypes.POINTER(_CopyJob), _vp],
-    # device-side ground truth and scoring (include/rtk_gt.h, ratrack_amd/gt_device.py); the argument blocks are rtk_gt_in_t /
-    # rtk_gt_out_t / rtk_eval_in_t (gt_device.GtIn, GtOut, EvalIn), passed by address
-    "rtk_gt_labels": [_vp, _vp, _vp],
-    "rtk_eval_frame": [_vp, _vp, _vp, _vp],
-    # ground-truth objects and the tracking score (include/rtk_score.h, ratrack_amd/track_score.py): rtk_gt_objects_in_t / _out_t and
-    # rtk_track_score_in_t / _state_t / _out_t by address; the two *_lds_bytes are host functions that return a byte count
-    "rtk_gt_objects": [_vp, _vp, _vp],
-    "rtk_track_score": [_vp, _vp, _vp, _vp],
-    "rtk_gt_objects_lds_bytes": [_ci, _ci],
-    "rtk_track_score_lds_bytes": [_ci, _ci, _ci],
-})
 
 
 def copy_multi(pairs):
@@ -110,15 +32,6 @@ def copy_multi(pairs):
             assert d.is_contiguous() and s_.is_contiguous() and d.shape == s_.shape and d.dtype == s_.dtype and d.device == s_.device
             jobs[j].src, jobs[j].dst, jobs[j].bytes = s_.data_ptr(), d.data_ptr(), d.numel() * d.element_size()
         _lib.call("rtk_copy_multi", len(part), jobs, _stream())
-
-
-class _LayoutJob(ctypes.Structure):
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("channels", ctypes.c_int), ("src_pitch", ctypes.c_int),
-                ("per_sample", ctypes.c_int), ("dst_channels", ctypes.c_int), ("dst_channel_offset", ctypes.c_int)]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def ceil16(c):
@@ -588,13 +501,13 @@ class Geometry:
                 if CHECK_FPS_RELEVEL and not torch.cuda.is_current_stream_capturing():
                     check_fps_relevel(new_xyz[0], torch.stack(self.fps_idx[1:]), xyz_all[1:], torch.stack(list(cnt[1:3])))
                 radii = (ctypes.c_float * 6)(*[float(r) for row in _PNHeadWeights.RADII for r in row])
-                nsam = (_ci * 6)(*ns_all)
-                balls = (_vp * 6)(*[t.data_ptr() for t in ball])
+                nsam = (ctypes.c_int * 6)(*ns_all)
+                balls = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in ball])
                 self.nn = {}
                 for i, (name, (u, k)) in enumerate({"fp3": (2, 3), "fp2": (1, 2), "fp1": (0, 1)}.items()):
                     self.nn[name] = (d2_parts[i].view(S_, nn_rows[i], 3), nn_idx[i].view(S_, nn_rows[i], 3), self.xyz[k].shape[1])
-                nni = (_vp * 3)(*[self.nn[k][1].data_ptr() for k in ("fp3", "fp2", "fp1")])
-                nnd = (_vp * 3)(*[self.nn[k][0].data_ptr() for k in ("fp3", "fp2", "fp1")])
+                nni = (ctypes.c_void_p * 3)(*[self.nn[k][1].data_ptr() for k in ("fp3", "fp2", "fp1")])
+                nnd = (ctypes.c_void_p * 3)(*[self.nn[k][0].data_ptr() for k in ("fp3", "fp2", "fp1")])
                 _lib.call("rtk_geometry_tables", S_, n, npoint, xyz.data_ptr(), xyz_all.data_ptr(), cnt[0].data_ptr(), radii, nsam, balls, nni, nnd,
                           _stream())
                 for lvl in range(3):

@@ -21,41 +21,12 @@ import numpy as np
 import torch
 
 from . import _lib, vod_gt
-from .tracker import _View, _view      # rtk_bcn_view_t; importing tracker registers the signatures (fused.py)
+from .abi import EvalIn, GtBoxes, GtIn, GtOut, stream as _stream, view as _view
 
 MAX_BOXES = 256                        # RTK_GT_MAX_BOXES
 KEYS = ("rne", "50-50 rne", "mov_rne", "stat_rne", "sas", "ras", "epe", "acc", "sen", "miou")
 SUM_KEYS = ("points", "error", "rn_error", "rn_error_moving", "moving", "rn_error_static", "static", "sas", "ras", "tp", "tn", "fp", "fn")
 _FLAG_BOXES, _FLAG_NVALID = 1, 2
-
-
-class GtBoxes(ctypes.Structure):
-    """rtk_gt_boxes_t."""
-    _fields_ = [("boxes", ctypes.c_void_p), ("box_id", ctypes.c_void_p), ("count", ctypes.c_void_p)]
-
-
-class GtIn(ctypes.Structure):
-    """rtk_gt_in_t."""
-    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("N2", ctypes.c_int), ("K", ctypes.c_int), ("pc1", _View), ("pc2", _View),
-                ("n_valid", ctypes.c_void_p), ("frame1", GtBoxes), ("frame2", GtBoxes), ("pair", ctypes.c_void_p),
-                ("motion", ctypes.c_void_p), ("ego", ctypes.c_void_p)]
-
-
-class GtOut(ctypes.Structure):
-    """rtk_gt_out_t."""
-    _fields_ = [("gt_cls", ctypes.c_void_p), ("box_index", ctypes.c_void_p), ("obj_id", ctypes.c_void_p), ("gt_warp", ctypes.c_void_p),
-                ("pc1_comp", ctypes.c_void_p), ("counts1", ctypes.c_void_p), ("counts2", ctypes.c_void_p), ("flags", ctypes.c_void_p)]
-
-
-class EvalIn(ctypes.Structure):
-    """rtk_eval_in_t."""
-    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("pc1", _View), ("warp", _View), ("gt_warp", _View), ("cls", _View),
-                ("mask", ctypes.c_void_p), ("gt_cls", ctypes.c_void_p), ("threshold", ctypes.c_float), ("n_valid", ctypes.c_void_p),
-                ("active", ctypes.c_void_p)]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ---- box tables ----------------------------------------------------------------------------------------------------------

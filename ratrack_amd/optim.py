@@ -7,14 +7,11 @@ here a device table of {param, grad, exp_avg, exp_avg_sq, numel, first workgroup
 
 The table is rebuilt whenever the set of (parameter, gradient) addresses changes.  Under stream capture it is filled by an
 asynchronous copy from a pinned host buffer -- a memcpy node of the graph, replayed with the same contents."""
-import ctypes
-
 import torch
 
 from . import _lib
+from .abi import stream
 
-_p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-_lib.SIGNATURES.update({"rtk_adam_multi": [_i, _p, ctypes.c_long, _p, _f, _f, _f, _f, _f, _p, _p]})
 CHUNK = 4096
 
 
@@ -84,8 +81,7 @@ class FusedAdam(torch.optim.Optimizer):
         lr = g["lr"]
         lr_ptr, lr_val = (lr.data_ptr(), 0.0) if isinstance(lr, torch.Tensor) else (None, float(lr))
         _lib.call("rtk_adam_multi", len(rows), self._table.data_ptr(), self._blocks, lr_ptr, lr_val, float(g["betas"][0]),
-                  float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self._ticket.data_ptr(),
-                  torch.cuda.current_stream().cuda_stream)
+                  float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self._ticket.data_ptr(), stream())
         # the kernel wrote the parameters through raw pointers: bump their version counters, as an in-place torch op would have
         # (Track4D's folded eval engine watches them; a graph replay re-runs the kernel, not this line -- Trainer drops the engine)
         torch.autograd.graph.increment_version(live)

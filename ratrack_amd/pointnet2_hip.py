@@ -10,10 +10,7 @@ of silently computing elsewhere.
 import torch
 
 from . import _lib
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+from .abi import stream as _stream
 
 
 def _chk(t, dtype, name):

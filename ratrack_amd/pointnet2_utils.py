@@ -12,6 +12,7 @@ from torch.autograd import Function
 
 from . import _lib
 from . import pointnet2_hip as _native
+from .abi import stream
 
 
 def _new(like, shape, dtype):
@@ -133,7 +134,7 @@ class ThreeInterpolate(Function):
         # writes the same values into an uninitialised buffer
         grad = torch.empty((B, c, ctx.m), dtype=torch.float32, device=grad_out.device)
         _lib.call("rtk_three_interpolate_grad_set", B, c, n, ctx.m, grad_out.contiguous().data_ptr(), idx.data_ptr(), weight.data_ptr(),
-                  grad.data_ptr(), torch.cuda.current_stream().cuda_stream)
+                  grad.data_ptr(), stream())
         return grad, None, None
 
 
@@ -161,7 +162,7 @@ class GroupingOperation(Function):
         B, C, npoint, nsample = grad_out.shape
         grad = torch.empty((B, C, ctx.N), dtype=torch.float32, device=grad_out.device)      # see ThreeInterpolate.backward
         _lib.call("rtk_group_points_grad_set", B, C, ctx.N, npoint, nsample, grad_out.contiguous().data_ptr(), idx.data_ptr(),
-                  grad.data_ptr(), torch.cuda.current_stream().cuda_stream)
+                  grad.data_ptr(), stream())
         return grad, None
 
 

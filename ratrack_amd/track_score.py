@@ -32,8 +32,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .gt_device import GtBoxes, _flag_bytes, _n_valid
-from .tracker import _View, _view      # rtk_bcn_view_t; importing tracker registers the signatures (fused.py)
+from .abi import GtBoxes, GtObjectsIn, GtObjectsOut, ScoreIn, ScoreOut, ScoreState, stream as _stream, view as _view
+from .gt_device import _flag_bytes, _n_valid
 
 LDS_LIMIT = 65536                      # RTK_SCORE_LDS_LIMIT
 MAX_BOXES = 64                         # RTK_SCORE_MAX_BOXES
@@ -41,39 +41,6 @@ MAX_OBJECTS = 256                      # RTK_SCORE_MAX_OBJECTS
 MAX_POINTS = 32768                     # RTK_SCORE_MAX_POINTS
 COUNTERS = ("frames", "gt", "pred", "tp", "fp", "fn", "idsw", "tracks", "mt", "pt", "ml")
 FLAG_BOXES, FLAG_NVALID, FLAG_TRACKS, FLAG_OBJECTS = 1, 2, 4, 8
-
-
-class GtObjectsIn(ctypes.Structure):
-    """rtk_gt_objects_in_t."""
-    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("pc1", _View), ("n_valid", ctypes.c_void_p),
-                ("frame1", GtBoxes), ("types", ctypes.c_void_p), ("min_obj_points", ctypes.c_int)]
-
-
-class GtObjectsOut(ctypes.Structure):
-    """rtk_gt_objects_out_t."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("slot", "label_id", "count", "size", "members", "centre", "flags")]
-
-
-class ScoreIn(ctypes.Structure):
-    """rtk_track_score_in_t."""
-    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("Kobj", ctypes.c_int), ("K", ctypes.c_int), ("T", ctypes.c_int), ("pc1", _View)] + \
-               [(n, ctypes.c_void_p) for n in ("obj", "num_objects", "object_ids", "n_valid", "gt_slot", "gt_label_id", "gt_count", "gt_size",
-                                               "gt_members", "reset", "active")]
-
-
-class ScoreState(ctypes.Structure):
-    """rtk_track_score_state_t."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("counters", "iou_sum", "table_key", "table_last", "table_seen", "table_matched", "table_used",
-                                               "prev_gt_id", "prev_count", "prev_gt", "flags")]
-
-
-class ScoreOut(ctypes.Structure):
-    """rtk_track_score_out_t."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("pred_gt_slot", "pred_gt_id", "gt_pred", "iou", "aff_target", "aff_defined")]
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ---- what fits -------------------------------------------------------------------------------------------------------------

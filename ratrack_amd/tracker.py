@@ -24,30 +24,12 @@ import os
 import torch
 
 from . import _lib
-from . import fused  # noqa: F401  (registers the signatures of include/rtk_fused.h)
+from .abi import TrackFrame, View as _View, stream, view as _view  # noqa: F401  (_View: tests and tools take it from here)
 
 DESC = 141
 DBSCAN_POINT_BYTES = 48          # RTK_DBSCAN_POINT_BYTES
 DBSCAN_LDS_BYTES = 128 * 1024
 _FLAG_OVERFLOW, _FLAG_NVALID = 1, 2
-
-
-class _View(ctypes.Structure):
-    _fields_ = [("ptr", ctypes.c_void_p), ("sb", ctypes.c_longlong), ("sc", ctypes.c_longlong), ("sp", ctypes.c_longlong)]
-
-
-class TrackFrame(ctypes.Structure):
-    """rtk_track_frame_t."""
-    _fields_ = [("B", ctypes.c_int), ("N", ctypes.c_int), ("pc1", _View), ("flow", _View), ("feature1", _View), ("prop", _View),
-                ("cls", _View), ("n_valid", ctypes.c_void_p), ("active", ctypes.c_void_p)]
-
-
-def _view(t):
-    """(B,C,N) or (B,N) fp32 CUDA tensor, any strides -> rtk_bcn_view_t (read in place: no copy)."""
-    assert t.is_cuda and t.dtype == torch.float32, (t.device, t.dtype)
-    if t.dim() == 2:
-        return _View(t.data_ptr(), t.stride(0), 0, t.stride(1))
-    return _View(t.data_ptr(), t.stride(0), t.stride(1), t.stride(2))
 
 
 def max_objects_limit():
@@ -206,7 +188,7 @@ class BatchedTracker:
         B, K = self.B, self.K
         N = pc1.shape[2]
         dev = self.dev
-        st = torch.cuda.current_stream().cuda_stream
+        st = stream()
         cur, prev = self.cur, 1 - self.cur
         i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
         labels, obj, num, flags = i32(B, N), i32(B, N), i32(B), i32(B)

@@ -10,49 +10,8 @@ import os
 import torch
 
 from . import _lib, fused
-
-_i, _f, _d, _p = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
-_LayerP = ctypes.POINTER(fused._Layer)
-_lib.SIGNATURES.update({
-    "rtk_cost_volume_train": [_i] * 3 + [_p] * 6 + [_LayerP, _LayerP, _p, _i, _p, _p, _p, _p, _p, _p],
-    "rtk_cost_volume_bwd": [_i] * 3 + [_p] * 3 + [_LayerP, _LayerP, _p, _p, _i] + [_p] * 12 + [_p],
-    "rtk_cost_volume_split_train": [_i] * 3 + [_p] * 10 + [_LayerP, _p, _i, _p, _p, _p, _p, _p, _p, _p],
-    "rtk_cost_volume_bwd_split": [_i] * 3 + [_p] * 5 + [_LayerP, _p, _i] + [_p] * 13 + [_p],
-    "rtk_pack_split_layer": [_i, _i, _p, _i, _p, _p, _p],
-    "rtk_scatter_add_rows": [_i] * 4 + [_p] * 3 + [_p],
-    "rtk_sa_first_layer": [_i] * 6 + [_p] * 4 + [_i] + [_p] * 3 + [_p],
-    "rtk_group_inverse_index": [_i] * 3 + [_p] * 3 + [_p],
-    "rtk_three_interpolate_grad_gather": [_i] * 4 + [_p] * 6 + [_p],
-    "rtk_sa_first_layer_bwd": [_i] * 5 + [_p] * 6 + [_i, _p, _p],
-    "rtk_conv_bn_fwd": [_i] * 6 + [_p] * 7 + [_p],
-    "rtk_conv_wgrad": [_i] * 6 + [_p] * 5 + [ctypes.c_long, _p],
-    "rtk_conv_bn_bwd": [_i] * 6 + [_p] * 6 + [_d, _i, _p, _p, _p],
-    "rtk_train_group_geometry": [_i] * 5 + [_p] * 3 + [_i] + [_p] * 3 + [_p],
-    "rtk_train_interp_weights": [_i] * 3 + [_p] * 5 + [_p],
-    "rtk_train_row_weights": [_i] * 3 + [_p] * 2 + [_p],
-    "rtk_gru_step_bwd": [_i] * 3 + [_p] * 15 + [_p],
-    "rtk_gru_pack_params": [_i, _i, ctypes.POINTER(ctypes.c_void_p)] + [_p] * 6 + [_p],
-    "rtk_gru_wgrad": [_i] * 3 + [_p] * 9 + [_p],
-    "rtk_patch_cost_bwd": [_i, _i, _p, _p, _p, _i, _LayerP, _p, _p, _i, _p, _p, _p, _p, _p, _p],
-    "rtk_patch_dfeat_gather": [_i, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p],
-    "rtk_bn_train_stats": [_i] * 5 + [_p] * 3 + [_p],
-    "rtk_bn_relu_fwd": [_i] * 5 + [_p, _p, _i, _p, _p],
-    "rtk_bn_relu_fwd_fin": [_i] * 5 + [_p, _p, _p, _i, _p, _p],
-    "rtk_conv_bn_fwd_fin": [_i] * 6 + [_p] * 8 + [_p],
-    "rtk_bn_relu_bwd_stats": [_i] * 5 + [_p, _p, _p, _i, _p, _p],
-    "rtk_bn_relu_bwd_apply": [_i] * 5 + [_p] * 5 + [_d, _p, _i, _p, _p, _p],
-    "rtk_bn_relu_bwd_small": [_i] * 4 + [_p] * 4 + [_d, _p, _p, _p, _i, _p],
-    "rtk_train_point_weights": [_i] * 3 + [_p] * 3 + [_p],
-})
-
-
-class _IIJob(ctypes.Structure):          # rtk_inverse_index_job_t (include/rtk_train.h)
-    _fields_ = [("n_src", ctypes.c_int), ("positions", ctypes.c_int), ("idx", ctypes.c_void_p), ("off", ctypes.c_void_p), ("inv", ctypes.c_void_p),
-                ("live", ctypes.c_void_p), ("live_mult", ctypes.c_int)]
-
-
-_lib.SIGNATURES.update({"rtk_group_inverse_index_multi": [_i, _i, ctypes.POINTER(_IIJob), _p]})
-
+from .abi import BnFin as _BnFin, InverseIndexJob as _IIJob, PackJob as _PackJob, PoolSrc as _PoolSrc, PwOperand as _PwOperand, \
+    PwWgradJob as _PwWgJob, TnJob as _TnJob, ptr as _ptr, stream as _stream
 
 def group_inverse_index_multi(samples, jobs):
     """jobs: list of (n_src, positions, idx int32 (samples, positions), off int32 (samples, n_src + 1), inv int16 (samples, positions)
@@ -67,47 +26,6 @@ def group_inverse_index_multi(samples, jobs):
             arr[k].n_src, arr[k].positions, arr[k].idx, arr[k].off, arr[k].inv = n_src, P, idx.data_ptr(), off.data_ptr(), inv.data_ptr()
             arr[k].live, arr[k].live_mult = _ptr(live), mult
         _lib.call("rtk_group_inverse_index_multi", samples, len(part), arr, _stream())
-
-
-class _PoolSrc(ctypes.Structure):        # rtk_pool_src_t (include/rtk_train.h)
-    _fields_ = [("dout", ctypes.c_void_p), ("karg", ctypes.c_void_p), ("par", ctypes.c_void_p), ("sums2", ctypes.c_void_p),
-                ("dgamma_dbeta", ctypes.c_void_p)]
-
-
-_PoolP = ctypes.POINTER(_PoolSrc)
-_lib.SIGNATURES.update({
-    "rtk_bn_relu_pool_fwd_fin_arg": [_i] * 5 + [_p, _p, _p, _p, _p, _p, _p],
-    "rtk_pool_bwd_stats_arg": [_i] * 4 + [_p] * 5 + [_p],
-    "rtk_conv_wgrad_stats": [_i] * 6 + [_p, _PoolP, _p, _p, _p, _d, _p, _p, _p, _p, _p, _p, ctypes.c_long, _p],
-    "rtk_conv_bn_bwd_apply": [_i] * 6 + [_p, _PoolP, _p, _p, _p, _p, _p, _d, _p, _p, _p],
-})
-
-
-class _PwOperand(ctypes.Structure):      # rtk_pw_operand_t (include/rtk_train.h)
-    _fields_ = [("ptr", ctypes.c_void_p), ("sample_stride", ctypes.c_long), ("pitch", ctypes.c_int), ("channels", ctypes.c_int),
-                ("layout", ctypes.c_int), ("col0", ctypes.c_int)]
-
-
-_PwP = ctypes.POINTER(_PwOperand)
-
-
-class _PwWgJob(ctypes.Structure):        # rtk_pw_wgrad_job_t (include/rtk_train.h)
-    _fields_ = [("samples", ctypes.c_int), ("positions", ctypes.c_int), ("dz", _PwP), ("nsrc", ctypes.c_int), ("srcs", _PwP),
-                ("dw", ctypes.c_void_p), ("w_pitch", ctypes.c_int), ("dbias", ctypes.c_void_p)]
-
-
-_lib.SIGNATURES.update({
-    "rtk_pw_wgrad_multi": [_i, ctypes.POINTER(_PwWgJob), _p, ctypes.c_long, _p],
-    "rtk_pw_conv": [_i, _i, _i, _PwP, _i, _PwP, _p, _i, _i, _p, _i, _p, _i, _p, _i, _p],
-    "rtk_pw_wgrad": [_i, _i, _PwP, _i, _PwP, _p, _i, _p, _p, ctypes.c_long, _p],
-    "rtk_backbone_loss": [_i, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p],
-    "rtk_pack_weights": [_i, _p, _p],
-    "rtk_weightnet_bwd": [ctypes.c_long, _i] + [_p] * 14 + [ctypes.c_long, _p],
-})
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ---- zero arena ----------------------------------------------------------------------------------------------------------------
@@ -163,10 +81,6 @@ def arena_zeros(n, dtype, device):
         return _zeros((n,), dtype, device)
     assert dtype in (torch.int32,), dtype
     return _zeros((n,), torch.float32, device).view(dtype)
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
 
 
 class _BNReLU(torch.autograd.Function):
@@ -542,9 +456,6 @@ def pw_bn_relu(srcs, weight, bn, row_weight=None, count=None, groups=1, cols=Non
 
 # ---- global feature appended to every point ---------------------------------------------------------------------------------
 
-_lib.SIGNATURES.update({"rtk_gmax_cat_fwd": [_i, _i, _i, _p, _p, _p, _p], "rtk_gmax_cat_bwd": [_i, _i, _i, _p, _p, _p, _p]})
-
-
 class _GmaxCat(torch.autograd.Function):
     """(S,C,N) -> (S,2C,N) = cat(f, max over the points broadcast) (models/track4d.py:92-95), one kernel each way."""
 
@@ -574,12 +485,6 @@ def gmax_cat(f):
 
 
 # ---- SharedMLP chain of one set-abstraction scale ------------------------------------------------------------------------
-
-class _BnFin(ctypes.Structure):          # rtk_bn_fin_t (include/rtk_train.h)
-    _fields_ = [("sums", ctypes.c_void_p), ("count", ctypes.c_double), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
-                ("eps", ctypes.c_float), ("momentum", ctypes.c_float), ("running_mean", ctypes.c_void_p), ("running_var", ctypes.c_void_p),
-                ("num_batches_tracked", ctypes.c_void_p), ("group_counts", ctypes.c_void_p)]
-
 
 def _bn_fin(bn, sums, count, groups, group_counts=None):
     """(rtk_bn_fin_t by reference, par buffer): the BatchNorm of `sums` is finalised by the kernel that consumes it (one launch less
@@ -764,11 +669,6 @@ def sa_chain(feats, w0, idx, dxyz, layers, row_w, count, groups, inv=None):
 
 # ---- cost volume -------------------------------------------------------------------------------------------------------
 
-class _PackJob(ctypes.Structure):      # rtk_pack_job_t (include/rtk_train.h)
-    _fields_ = [("src", ctypes.c_void_p), ("src2", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("rows", ctypes.c_int), ("cols", ctypes.c_int),
-                ("pitch", ctypes.c_int), ("transpose", ctypes.c_int), ("kind", ctypes.c_int)]
-
-
 def _pack_weights(specs, device):
     """specs: list of (kind, matrix-or-vector, transpose, second tensor or None): every kernel image of an operator's live weights in
     ONE launch (rtk_pack_weights) into one workspace.  kind 0 = fragment-major MFMA image (fused.pack_layer), 1 = offset-layer image
@@ -855,15 +755,6 @@ class _CvWeights:
         self.wn = wn
         if backward and nm:
             self.layers_t = ctypes.cast(ctypes.byref(self.layers, 2 * ctypes.sizeof(L)), ctypes.POINTER(L))      # W3^T, W2^T
-
-
-class _TnJob(ctypes.Structure):          # rtk_tn_job_t (include/rtk_train.h)
-    _fields_ = [("x", ctypes.c_void_p), ("y", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_pitch", ctypes.c_int),
-                ("x_amax", ctypes.c_void_p), ("y_amax", ctypes.c_void_p)]
-
-
-_lib.SIGNATURES.update({"rtk_tn_gemm256_split": [_i, ctypes.POINTER(_TnJob), ctypes.c_long, _p, ctypes.c_long, _p],
-                        "rtk_absmax": [_p, ctypes.c_long, _p, _p]})
 
 
 TN_MAX_ROWS = (1 << 22) - 16      # rtk_tn_gemm256_split addresses its operands through 32-bit buffer resources: m < 2^22 rows per launch

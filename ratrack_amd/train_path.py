@@ -22,6 +22,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import pointnet2_utils as PU
+from .abi import stream
 from .train_ops import bn_relu, conv1x1, cost_volume, patch_cost, pw_bn_relu, pw_linear, sa_chain, sa_chain_supported
 
 
@@ -53,8 +54,7 @@ class TrainGeometry:
             assert n_valid.shape == (S_,) and n_valid.dtype == torch.int32 and n_valid.is_cuda and n_valid.is_contiguous()
             self.point_w = torch.empty(S_, n, dtype=torch.float32, device=xyz.device)
             self.point_counts = torch.empty(groups, dtype=torch.float64, device=xyz.device)
-            _lib.call("rtk_train_point_weights", S_, n, groups, n_valid.data_ptr(), self.point_w.data_ptr(), self.point_counts.data_ptr(),
-                      torch.cuda.current_stream().cuda_stream)
+            _lib.call("rtk_train_point_weights", S_, n, groups, n_valid.data_ptr(), self.point_w.data_ptr(), self.point_counts.data_ptr(), stream())
         U = self.U = min(n, npoint)
         dev = xyz.device
         f32 = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
@@ -78,7 +78,7 @@ class TrainGeometry:
         # interpolation's backward is a gather as well
         self.interp_inv = {name: (i32(S_, U + 1), torch.empty(S_, 3 * io.shape[1], dtype=torch.int16, device=dev))
                            if 3 * io.shape[1] <= 65536 and io.shape[1] <= 2048 else None for name, (io, _) in self.interp.items()}
-        st = lambda: torch.cuda.current_stream().cuda_stream
+        st = stream
 
         def level_tables(geo, lvl):
             nu = geo.nuniq
@@ -278,8 +278,7 @@ def _knn16(points, query, n_valid):
         return knn_point(16, points, query).contiguous()
     B, S, _ = query.shape
     idx = torch.empty(B, S, 16, dtype=torch.int64, device=query.device)
-    _lib.call("rtk_knn_point_masked", B, S, points.shape[1], 16, query.data_ptr(), points.data_ptr(), idx.data_ptr(), n_valid.data_ptr(),
-              torch.cuda.current_stream().cuda_stream)
+    _lib.call("rtk_knn_point_masked", B, S, points.shape[1], 16, query.data_ptr(), points.data_ptr(), idx.data_ptr(), n_valid.data_ptr(), stream())
     return idx
 
 
