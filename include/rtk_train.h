@@ -439,6 +439,60 @@ RTK_EXPORT int rtk_backbone_loss(int b, int n, const float *pc1, const float *fl
 RTK_EXPORT int rtk_adam_multi(int n_tensors, const void *table, long total_blocks, const float *lr_ptr, float lr, float beta1,
                               float beta2, float eps, float weight_decay, int *ticket, rtk_stream_t stream);
 
+/* ---- tracking term of B sequences (ratrack_amd/track_train.py, csrc/track_train.hip) --------------------------------------------
+ * The backward of losses/loss.py:48-72 (binary cross entropy of the Affinity MLP's output against the identity-match matrix) behind
+ * rtk_object_descriptors / rtk_affinity_pairs (rtk_fused.h), for every live (previous, current) object pair of every stream.  The
+ * previous frame's objects are detached (main_utils.py:158-160): nothing flows into desc_prev.  No floating-point atomics anywhere:
+ * every sum has a fixed order, the results are reproducible bit for bit.
+ *
+ * Workspace: RTK_AFF_TRAIN_ROW floats (8192 bytes) per live pair, rows in stream order and, inside a stream, in the reference's pair
+ * order (i previous, j current -> i * n_b + j):
+ *   [a0 (141) | a1 (564) | a2 (282) | a3 (70) | a4 (35)]  the MLP's input and its four ReLU outputs
+ *   [d1 (564) | d2 (282) | d3 (70) | d4 (35) | d5 (1)]    the gradients of the five pre-activations
+ *   [the pair's cross-entropy term (1) | 3 unused]
+ * followed by ceil(max_pairs / RTK_AFF_TRAIN_CHUNK) partial weight images of RTK_AFFINITY_WEIGHTS floats (rtk_affinity_wgrad). */
+#define RTK_AFF_TRAIN_ROW 2048
+#define RTK_AFF_TRAIN_CHUNK 512
+/* weights_bwd: the five layers' weights as nn.Linear keeps them, (Cout, Cin) row-major, one after the other, no biases: the operand
+ * order in which the input-gradient products read them coalesced. */
+#define RTK_AFFINITY_WEIGHTS_BWD (141 * 564 + 564 * 282 + 282 * 70 + 70 * 35 + 35)
+
+/* rtk_affinity_train.  Per stream b the live block is m_b x n_b (prev_count, reset, num_objects clamped as in rtk_affinity_pairs);
+ * a stream takes part iff it is active (active NULL: all), aff_defined[b] != 0, m_b n_b > 0 and its rows end at or before max_pairs
+ * in the running sum of the participating streams' pair counts; otherwise loss[b] = 0 and it contributes no gradient.
+ * flags (B): 1 = the stream's pairs fell beyond max_pairs (nothing of it is computed: raise max_pairs).
+ * pair_offset (B + 1) int32: first workspace row of each stream (-1: beyond the cap), [B] = rows in use.
+ * loss (B): mean over the block of -(t max(log a, -100) + (1 - t) max(log1p(-a), -100)), a = the pair's affinity computed with
+ * rtk_affinity_pairs' arithmetic (the same fmaf chains), t = aff_target[b][i][j] ((B,K,K), as rtk_track_score emits it).
+ * scale (B) != NULL: the upstream gradient of loss[b].  The gradient of the pre-sigmoid is
+ * scale[b] / (m_b n_b) * (a - t) / max(a (1 - a), 1e-12) * (1 - a) a; it is taken back through the five layers (rows of the
+ * workspace, see above) and d_desc (B,K,141), fully written, = the gradient of desc: the sum over the previous objects i, in
+ * ascending i, of the first pre-activation's gradient, then one product with the first layer's weight.  Three launches.
+ * scale == NULL: loss only, read off aff (B,K,K) = rtk_affinity_pairs' output for the same arguments; d_desc, weights, weights_bwd,
+ * desc, desc_prev and the workspace are not touched (may be NULL).  Two launches. */
+RTK_EXPORT int rtk_affinity_train(int B, int K, const float *weights, const float *weights_bwd, const float *desc_prev,
+                                  const int *prev_count, const unsigned char *reset, const unsigned char *active, const float *desc,
+                                  const int *num_objects, const float *aff, const float *aff_target, const unsigned char *aff_defined,
+                                  const float *scale, int max_pairs, float *loss, float *d_desc, int *pair_offset, int *flags,
+                                  float *workspace, long workspace_floats, rtk_stream_t stream);
+
+/* rtk_affinity_wgrad: d_weights (RTK_AFFINITY_WEIGHTS floats, the layout of the packed image: per layer dW^T (Cin, Cout), then the bias
+ * gradient), fully written (zeros when no pair is live), = the sum over the rows rtk_affinity_train left in the workspace of
+ * a_{l-1} (x) d_l | d_l.  A workgroup owns a 64 x 64 block of one layer and one chunk of RTK_AFF_TRAIN_CHUNK rows, which it adds up
+ * in row order (fmaf chains per 16 rows, added in order; the bias sums compensated); a second kernel adds the chunks' partial images
+ * in chunk order.  The split depends on nothing but the rows, so the
+ * result does not depend on max_pairs.  Same B, max_pairs, pair_offset and workspace as the rtk_affinity_train call.  Two launches. */
+RTK_EXPORT int rtk_affinity_wgrad(int B, int max_pairs, const int *pair_offset, float *workspace, long workspace_floats,
+                                  float *d_weights, rtk_stream_t stream);
+
+/* rtk_object_descriptors_bwd: d_desc (B,K,141) -> d_flow (B,3,N), d_prop (B,128,N), contiguous and fully written.  A point p of
+ * object k (obj (B,N), num_objects (B) of rtk_dbscan_batched on the same frame) gets d_flow[c][p] = d_desc[k][134 + c] / |k| and
+ * d_prop[c][p] = d_desc[k][6 + c] if p is the member that attains the maximum of channel c (ties: the LOWEST point index, what
+ * torch.max(dim) documents), else 0; points of no object, padding columns and inactive streams get zeros.  The other descriptor
+ * entries depend on inputs only.  arg_ws: B * K * 129 int32 of scratch (the arg-max table and the objects' sizes).  Two launches. */
+RTK_EXPORT int rtk_object_descriptors_bwd(const rtk_track_frame_t *frame, int K, const int *obj, const int *num_objects,
+                                          const float *d_desc, float *d_flow, float *d_prop, int *arg_ws, rtk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -240,6 +240,9 @@ SIGNATURES = {
     "rtk_gmax_cat_bwd": [_i, _i, _i, _p, _p, _p, _p],
     "rtk_backbone_loss": [_i, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p],
     "rtk_adam_multi": [_i, _p, _l, _p, _f, _f, _f, _f, _f, _p, _p],
+    "rtk_affinity_train": [_i, _i] + [_p] * 12 + [_i] + [_p] * 5 + [_l, _p],
+    "rtk_affinity_wgrad": [_i, _i, _p, _p, _l, _p, _p],
+    "rtk_object_descriptors_bwd": [_p, _i] + [_p] * 6 + [_p],
 }
 
 

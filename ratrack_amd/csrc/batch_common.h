@@ -13,6 +13,15 @@ __device__ __forceinline__ float bcn_at(const rtk_bcn_view_t &v, int b, int c, i
 // a count read from the device, brought into [0, hi]
 __device__ __forceinline__ int count_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
+// one frame of the batched tracker (rtk_track_frame_t): does stream b take part, and how many of its N columns are points
+__device__ __forceinline__ bool stream_active(const rtk_track_frame_t &fr, int b) { return !fr.active || fr.active[b]; }
+
+__device__ __forceinline__ int stream_points(const rtk_track_frame_t &fr, int b) {
+    if (!fr.n_valid) return fr.N;
+    const int n = fr.n_valid[b];
+    return n < 0 ? 0 : (n > fr.N ? fr.N : n);
+}
+
 // |(p - c) . R[:,k]| <= half_k on the three axes, closed; the operation order is part of the contract (rtk_gt.h).
 __device__ __forceinline__ bool box_inside(const double *bx, double x, double y, double z) {
     const double d0 = x - bx[0], d1 = y - bx[1], d2 = z - bx[2];

@@ -21,14 +21,6 @@
 
 #define DB_LDS_BYTES (128 * 1024)
 
-__device__ __forceinline__ bool stream_active(const rtk_track_frame_t &fr, int b) { return !fr.active || fr.active[b]; }
-
-__device__ __forceinline__ int stream_points(const rtk_track_frame_t &fr, int b) {
-    if (!fr.n_valid) return fr.N;
-    const int n = fr.n_valid[b];
-    return n < 0 ? 0 : (n > fr.N ? fr.N : n);
-}
-
 // ------------------------------------------------------------------------------------------------
 // rtk_dbscan_batched: dbscan_workgroup (assoc_common.h) on one stream's columns, then step 5 numbers the objects as the reference's
 // dict does (models/track4d.py:119-125: in order of their FIRST MEMBER point, border points included -- the numpy block of

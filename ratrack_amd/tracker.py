@@ -70,7 +70,9 @@ def check_n_valid(n_valid, N):
 
 class StepResult:
     """One step's outputs (device tensors): flow (B,3,N), cls (B,N), h (5,B,128), point_track_id (B,N) int32, num_objects (B,),
-    object_ids / object_conf (B,K), aff (B,K,K) (only [:m_b, :n_b] meaningful), indices1() (B,K) int32 (-1: no match)."""
+    object_ids / object_conf (B,K), aff (B,K,K) (only [:m_b, :n_b] meaningful), indices1() (B,K) int32 (-1: no match);
+    descriptors / desc_prev (B,K,141): this frame's and the previous objects' descriptors (the tracker's own buffers: the next
+    step but one overwrites them)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -143,8 +145,10 @@ def raise_on_flags(flags, K, only=None):
 class BatchedTracker:
     """Tracks `streams` independent sequences in lockstep (see the module docstring)."""
 
-    def __init__(self, net, streams, max_objects=128, iters=500, alpha=0.9, eps=1.5, threshold=0.5):
-        if net.training:
+    def __init__(self, net, streams, max_objects=128, iters=500, alpha=0.9, eps=1.5, threshold=0.5, train_mode=False):
+        """train_mode: accept a train-mode net -- for a caller that runs the backbone itself and uses `associate` and the state only
+        (track_train.SequenceTrainer); `step()` stays the eval-mode path."""
+        if net.training and not train_mode:
             raise ValueError("BatchedTracker runs the eval-mode (fused) backbone: call net.eval() first")
         kmax = max_objects_limit()
         if not 1 <= max_objects <= kmax:
@@ -216,7 +220,7 @@ class BatchedTracker:
         self.cur = prev                    # this frame's objects are the next frame's previous objects: a swap, not a copy
         out = StepResult(flow=flow, cls=cls, h=self.h, point_track_id=point_track_id, num_objects=num, object_ids=object_ids,
                          object_conf=object_conf, _indices1=indices1, aff=aff, num_prev=num_prev, flags=flags, labels=labels, obj=obj,
-                         descriptors=desc, active=active, pc1=pc1, feature1=feature1, prop=prop, max_objects=K, _cache=None)
+                         descriptors=desc, desc_prev=desc_prev, active=active, pc1=pc1, feature1=feature1, prop=prop, max_objects=K, _cache=None)
         self.last = out
         return out
 
