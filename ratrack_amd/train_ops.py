@@ -941,6 +941,12 @@ def _weightnet_backward(d4, dq3, dt2, wa, ba, wb, bb, wc):
     return dwa.view(8, 3), dba, dwb.view(8, 8), dbb, dwc.view(C, 8), dbc
 
 
+# Largest cloud whose inverse tables fit 16-bit entries and their LDS budget (rtk_group_inverse_index): up to it the patch-cost and
+# interpolation backwards gather through an inverse table, above it they scatter (rtk_scatter_add_rows, the atomic three_interpolate).
+# A module constant so that a test can force the scatter form at a small n.
+INVERSE_TABLE_MAX_POINTS = 2048
+
+
 class _PatchCost(torch.autograd.Function):
     """out[i] = sum_k WeightNet(xyz[knn[i,k]] - xyz[i]) * feat[knn[i,k]]  (model_utils.py:238-248): forward = the inference
     kernel rtk_patch_cost, backward = rtk_patch_cost_bwd + the LDS scatter + the WeightNet's small GEMMs."""
@@ -969,7 +975,7 @@ class _PatchCost(torch.autograd.Function):
         dt2 = torch.empty(M, 8, dtype=torch.float32, device=dev)
         d4 = torch.empty(M, 4, dtype=torch.float32, device=dev)
         dfeat = torch.empty(B * n, 256, dtype=torch.float32, device=dev)
-        if n <= 2048:                          # the 16-bit inverse table and its LDS budget (rtk_group_inverse_index)
+        if n <= INVERSE_TABLE_MAX_POINTS:      # the 16-bit inverse table and its LDS budget (rtk_group_inverse_index)
             # feature gradient as a gather over the inverse kNN table (positions sorted by the row they gathered), the WeightNet output
             # recomputed from its hidden activation: nothing of size (M, 256) is materialised for it
             t2 = torch.empty(M, 8, dtype=torch.float32, device=dev)

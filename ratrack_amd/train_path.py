@@ -45,7 +45,7 @@ class TrainGeometry:
         element counts from the device (`point_w`, `point_counts`; groups = number of consecutive batch slices with their own
         statistics): results, gradients and running statistics of every sample equal those of its own unpadded B = 1 run, and
         the captured step does not depend on the clouds' sizes."""
-        from . import fused
+        from . import fused, train_ops
         S_, n, _ = xyz.shape
         self.samples, self.n, self.npoint = S_, n, npoint
         self.xyz = xyz                            # (S_, n, 3) contiguous: the correlator takes its point-major coordinates from here
@@ -76,8 +76,9 @@ class TrainGeometry:
                        for name, (u, k) in {"fp3": (2, 3), "fp2": (1, 2), "fp1": (0, 1)}.items()}
         # inverse tables of the interpolation indices (known point -> the (unknown point, slot) positions that use it): the
         # interpolation's backward is a gather as well
+        limit = train_ops.INVERSE_TABLE_MAX_POINTS
         self.interp_inv = {name: (i32(S_, U + 1), torch.empty(S_, 3 * io.shape[1], dtype=torch.int16, device=dev))
-                           if 3 * io.shape[1] <= 65536 and io.shape[1] <= 2048 else None for name, (io, _) in self.interp.items()}
+                           if 3 * io.shape[1] <= 65536 and io.shape[1] <= limit else None for name, (io, _) in self.interp.items()}
         st = stream
 
         def level_tables(geo, lvl):

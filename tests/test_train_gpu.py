@@ -182,11 +182,12 @@ def _train_once(dedup, B, N, pretrain=False):
                 total=float(total.detach())), grads, stats
 
 
-@pytest.mark.parametrize("B,N", [(2, 256), (3, 200), (2, 640), (64, 256)])
+@pytest.mark.parametrize("B,N", [(2, 256), (3, 200), (2, 640), (64, 256), (1, 2304)])
 def test_dedup_train_step_matches_module_path(B, N):
     """Same weights, same batch: forward outputs, every parameter gradient and every BatchNorm running statistic of the
     de-duplicated path agree with the module path that computes all 512 centroid rows.  (64, 256) is BASELINE config 3 at
-    its full size."""
+    its full size.  (1, 2304) lies above train_ops.INVERSE_TABLE_MAX_POINTS: geometry by separate launches with the training hooks, fp1
+    interpolated through the atomic three_interpolate, the patch-cost backward in its scatter form."""
     out_d, g_d, s_d = _train_once(True, B, N)
     out_m, g_m, s_m = _train_once(False, B, N)
     for k in ("flow", "cls", "prop", "h", "f1", "f2"):

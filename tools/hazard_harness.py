@@ -6,8 +6,10 @@ The reference's forward is deterministic (models/track4d.py:67-106; SURVEY secti
 between the geometry stream and the main stream, a buffer recycled under a pending kernel, or a read of memory nobody wrote.
 The harness makes each of those loud instead of waiting for a 1-in-90 tolerance failure:
 
-  poison     every torch.empty / empty_like handed out while a case runs is filled first -- floats with NaN, integers with 1
-             (an in-range, wrong index) -- so a read of uninitialised bytes changes the result deterministically;
+  poison     every torch.empty / empty_like / empty_strided / new_empty handed out while a case runs is filled first -- floats with
+             NaN, integers with 1 (an in-range, wrong index) by default, poison(float_fill, int_fill) otherwise -- so a read of
+             uninitialised bytes changes the result deterministically (tests/test_unwritten_memory_gpu.py runs the training,
+             tracking and scoring paths under it);
   churn      between iterations random-sized NaN-filled blocks are allocated and dropped on the main stream (warm pools whose
              free blocks hold poison), `torch.cuda.empty_cache()` now and then;
   no-sync    iterations are enqueued back to back, comparisons are device-side flags read every `--check-every` iterations,
@@ -43,29 +45,39 @@ NAMES = ["flow", "h", "cls", "cor", "pc1_features", "pc2_features", "prop"]
 
 # ---- poison allocator ---------------------------------------------------------------------------------------------------
 class poison:
-    """While active, torch.empty / torch.empty_like / Tensor.new_empty return poisoned device tensors."""
+    """While active, torch.empty / torch.empty_like / torch.empty_strided / Tensor.new_empty / Tensor.new_empty_strided return
+    poisoned device tensors: floats hold `float_fill` (default NaN), integers `int_fill` (default 1: an in-range, wrong index).
+    Eager execution only: nothing is filled while the current stream is being captured."""
     active = False
     _saved = None
+    _INTS = (torch.int32, torch.int64, torch.int16, torch.uint8, torch.int8)
 
-    @staticmethod
-    def _fill(t):
-        if t.is_cuda and t.numel():
+    def __init__(self, float_fill=float("nan"), int_fill=1):
+        self.float_fill, self.int_fill = float(float_fill), int(int_fill)
+        self.fills = 0          # tensors poisoned so far
+
+    def _fill(self, t):
+        if t.is_cuda and t.numel() and not torch.cuda.is_current_stream_capturing():
             if t.is_floating_point():
-                t.fill_(float("nan"))
-            elif t.dtype in (torch.int32, torch.int64, torch.int16, torch.uint8, torch.int8):
-                t.fill_(1)
+                t.fill_(self.float_fill)
+                self.fills += 1
+            elif t.dtype in poison._INTS:
+                t.fill_(self.int_fill)
+                self.fills += 1
         return t
 
     def __enter__(self):
-        e, el = torch.empty, torch.empty_like
-        poison._saved = (e, el)
-        torch.empty = lambda *a, **k: poison._fill(e(*a, **k))
-        torch.empty_like = lambda *a, **k: poison._fill(el(*a, **k))
+        assert not poison.active, "poison does not nest"
+        saved = (torch.empty, torch.empty_like, torch.empty_strided, torch.Tensor.new_empty, torch.Tensor.new_empty_strided)
+        poison._saved = saved
+        wrap = lambda f: (lambda *a, **k: self._fill(f(*a, **k)))
+        torch.empty, torch.empty_like, torch.empty_strided = wrap(saved[0]), wrap(saved[1]), wrap(saved[2])
+        torch.Tensor.new_empty, torch.Tensor.new_empty_strided = wrap(saved[3]), wrap(saved[4])
         poison.active = True
         return self
 
     def __exit__(self, *a):
-        torch.empty, torch.empty_like = poison._saved
+        torch.empty, torch.empty_like, torch.empty_strided, torch.Tensor.new_empty, torch.Tensor.new_empty_strided = poison._saved
         poison.active = False
         return False
 
