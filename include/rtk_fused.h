@@ -115,6 +115,12 @@ RTK_EXPORT int rtk_cost_volume(int samples, int n1, int n2, const float *xyz1, c
 RTK_EXPORT int rtk_patch_cost(int samples, int n, const float *xyz, const int64_t *knn_idx,
                               const float *feat, int feat_pitch, const rtk_layer_t *wn, float *out,
                               int out_pitch, int out_channel_major, rtk_stream_t stream);
+/* The same operator on the kernel with one wave per point (16 positions); rtk_patch_cost runs a 32-position tile (two points per
+ * wave, csrc/fused_patch.hip) and hands the channel-major output, and feature buffers of 4 GiB and more, to this one.  Same
+ * arguments, same contract, the same bits. */
+RTK_EXPORT int rtk_patch_cost_wave16(int samples, int n, const float *xyz, const int64_t *knn_idx,
+                                     const float *feat, int feat_pitch, const rtk_layer_t *wn, float *out,
+                                     int out_pitch, int out_channel_major, rtk_stream_t stream);
 
 /* ---- split matrix path (csrc/split_mfma.h): fp32 results from the fp16 matrix pipe --------------------------------------
  * Every fp32 operand, scaled by an exact power of two, is the sum of two fp16 pieces up to 2^-23 of itself; a product is the

@@ -160,6 +160,7 @@ SIGNATURES = {
     "rtk_sa_scale": [_i] * 4 + [_p] * 4 + [_i, _i, _p, _i, P(Layer), _p, _i, _i, _p, _p, _p],
     "rtk_cost_volume": [_i] * 3 + [_p] * 6 + [P(Layer), P(Layer), _p, _i, _p],
     "rtk_patch_cost": [_i] * 2 + [_p] * 3 + [_i, P(Layer), _p, _i, _i, _p],
+    "rtk_patch_cost_wave16": [_i] * 2 + [_p] * 3 + [_i, P(Layer), _p, _i, _i, _p],
     "rtk_pack_split_layer": [_i, _i, _p, _i, _p, _p, _p],
     "rtk_cost_volume_split": [_i] * 3 + [_p] * 10 + [P(Layer), _p, _i, _p],
     "rtk_cost_volume_split_shared": [_i] * 3 + [_p] * 10 + [P(Layer), _p, _i, _i, _p],

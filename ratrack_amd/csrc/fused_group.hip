@@ -17,11 +17,11 @@
 #include "fused_common.h"
 #include "rtk_fused.h"
 #include "rtk_train.h"
+#include "wn_tile.h"      // relu_med4 / max_med4: ReLU and maximum in one instruction each
 
 // The single k-step "offset" layer: A operand image [V][64] floats, lane (g, i) holds W4[16v + i][g] with
 // W4 = [Wx | b] (Cout x 4); B operand: lane (g, j) holds (dx, dy, dz, 1)[g] of pair j.
 
-__device__ __forceinline__ f4 f4_max(f4 a, f4 b) { return (f4){fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)}; }
 __device__ __forceinline__ f4 f4_relu(f4 a) { return (f4){fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f)}; }
 
 // =================================================================================================
@@ -48,6 +48,7 @@ struct SaParams {
 // NS = neighbours per centroid; V1/V2/V3 = layer widths / 16 (V3 = 0: two-layer MLP).
 template <int NS, int V1, int V2, int V3>
 __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
+    const float kinf = rtk_hidden_inf();
     constexpr int NF = V1 * V2 + V2 * V3;
     constexpr int VL = V3 ? V3 : V2;                 // width of the last layer
     constexpr int TILES = NS > 16 ? NS / 16 : 1;     // tiles per work unit (NS = 32: one centroid = 2 tiles)
@@ -92,26 +93,26 @@ __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
 #pragma unroll
             for (int v = 0; v < V1; ++v) a1[v] = mfma4(w1[v], bop, a1[v]);      // + Wx.d + b1 (one MFMA k-step, C-in = q row)
 #pragma unroll
-            for (int v = 0; v < V1; ++v) a1[v] = f4_relu(a1[v]);
+            for (int v = 0; v < V1; ++v) a1[v] = relu_med4(a1[v], kinf);
             f4 a2[V2];
             if constexpr (V3 == 0) {
 #pragma unroll
                 for (int v = 0; v < V2; ++v) a2[v] = f4_zero();     // last layer: bias + ReLU after the max
                 mlp_layer_res<V1, V2>(s_w, lane, a1, a2);
 #pragma unroll
-                for (int v = 0; v < V2; ++v) best[v] = t == 0 ? a2[v] : f4_max(best[v], a2[v]);
+                for (int v = 0; v < V2; ++v) best[v] = t == 0 ? a2[v] : max_med4(best[v], a2[v], kinf);
             } else {
 #pragma unroll
                 for (int v = 0; v < V2; ++v) a2[v] = bias_frag(P.bias2, v, g);
                 mlp_layer_res<V1, V2>(s_w, lane, a1, a2);
 #pragma unroll
-                for (int v = 0; v < V2; ++v) a2[v] = f4_relu(a2[v]);
+                for (int v = 0; v < V2; ++v) a2[v] = relu_med4(a2[v], kinf);
                 f4 a3[V3 ? V3 : 1];
 #pragma unroll
                 for (int v = 0; v < V3; ++v) a3[v] = f4_zero();
                 mlp_layer_res<V2, (V3 ? V3 : 1)>(s_w + V1 * V2 * 64, lane, a2, a3);
 #pragma unroll
-                for (int v = 0; v < V3; ++v) best[v] = t == 0 ? a3[v] : f4_max(best[v], a3[v]);
+                for (int v = 0; v < V3; ++v) best[v] = t == 0 ? a3[v] : max_med4(best[v], a3[v], kinf);
             }
         }
         // bias, max over the neighbours of each centroid (DPP within the 16-lane row), ReLU.  The bias goes in BEFORE the maximum
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
         for (int v = 0; v < VL; ++v) {
             f4 m = best[v] + bias_frag(bl, v, g);
             row_max_group_f4<(NS > 16 ? 16 : NS)>(m);
-            best[v] = f4_relu(m);
+            best[v] = relu_med4(m, kinf);
         }
         if (valid && slot0 == 0) {
             float *o = P.out + (long)c * P.out_pitch + P.out_offset + 4 * g;
@@ -718,7 +719,7 @@ extern "C" int rtk_scatter_add_rows(int samples, int m, int n, int channels, con
 }
 
 // =================================================================================================
-// rtk_patch_cost
+// rtk_patch_cost_wave16: the patch aggregation with a wave per point (16 positions)
 // =================================================================================================
 struct PcParams {
     int samples, n;
@@ -778,9 +779,11 @@ __global__ __launch_bounds__(256, PC_WAVES) void patch_cost_kernel(const PcParam
     }
 }
 
-extern "C" int rtk_patch_cost(int samples, int n, const float *xyz, const int64_t *knn_idx, const float *feat,
-                              int feat_pitch, const rtk_layer_t *wn, float *out, int out_pitch, int out_channel_major,
-                              rtk_stream_t stream) {
+// (rtk_patch_cost itself: fused_patch.hip -- the 32-position tile, which falls back to this kernel for the channel-major output and
+// for buffers beyond its 32-bit row offsets; the two return the same bits)
+extern "C" int rtk_patch_cost_wave16(int samples, int n, const float *xyz, const int64_t *knn_idx, const float *feat,
+                                     int feat_pitch, const rtk_layer_t *wn, float *out, int out_pitch, int out_channel_major,
+                                     rtk_stream_t stream) {
     RTK_REQUIRE(samples > 0 && n >= 16 && xyz && knn_idx && feat && out && feat_pitch % 4 == 0 && feat_pitch >= 256,
                 "patch_cost: bad arguments");
     RTK_REQUIRE(out_channel_major || (out_pitch % 4 == 0 && out_pitch >= 256), "patch_cost: bad out_pitch");

@@ -61,7 +61,6 @@ __device__ __forceinline__ f4 leaky_med4(f4 t, float inf) {
                 __builtin_amdgcn_fmed3f(t.w, u.w, inf)};
 }
 __device__ __forceinline__ f4 scale_bias4(f4 a, float c, f4 b) { return __builtin_elementwise_fma(a, (f4){c, c, c, c}, b); }
-__device__ __forceinline__ float rtk_hidden_inf();
 
 // ---- two 256 x 256 layers with LeakyReLU(0.1) over a list of positions (the inner layers of the cost volume, standalone) ----
 __global__ __launch_bounds__(64 * SP_NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
@@ -105,14 +104,6 @@ void split_mlp2_kernel(int positions, const float *__restrict__ x, const f4 *__r
 // the 32x32 tile), a workgroup (one wave per SIMD) eight points per iteration.  Layer 1 (K = 3) and the WeightNet's last
 // layer (K = 8) stay on the fp32-input MFMA (v_mfma_f32_32x32x2_f32, same C/D layout); the two 256 x 256 layers -- 99 % of the
 // flops -- run split.
-__device__ __forceinline__ f16v mfma_f32x2(float a, float b, f16v c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-
-struct WnSplit {                  // WeightNet images as packed for the 16x16 kernels (fused_group.hip)
-    const float *wa;              // [Wa | ba]: Wa[o][k] = wa[16 k + o], ba[o] = wa[48 + o]
-    const float *wb, *wc;         // Wb[o][c] = wb[(16 (c / 4) + o) 4 + c % 4];  Wc[ch][k] = wc[((ch / 16) 64 + 16 (k / 4) + ch % 16) 4 + k % 4]
-    const float *bb, *bc;
-};
-
 struct CvSplitParams {
     int samples, n1, n2, gx;
     const float *xyz1, *xyz2;
@@ -155,24 +146,7 @@ __device__ __forceinline__ const f4 *cv_at(const float *base, unsigned byte_off)
     return reinterpret_cast<const f4 *>(reinterpret_cast<const char *>(base) + byte_off);
 }
 
-// WeightNet hidden layers (3 -> 8 -> 8, ReLU) of this lane's position: uniform weights, every lane its own direction
-__device__ __forceinline__ void wn_hidden(const WnSplit &W, float dx, float dy, float dz, float (&t2)[8]) {
-    float t1[8];
-#pragma unroll
-    for (int o = 0; o < 8; ++o) {
-        float a = __fmaf_rn(ldc(W.wa + o), dx, 0.f);
-        a = __fmaf_rn(ldc(W.wa + 16 + o), dy, a);
-        a = __fmaf_rn(ldc(W.wa + 32 + o), dz, a);
-        t1[o] = fmaxf(__fadd_rn(a, ldc(W.wa + 48 + o)), 0.f);
-    }
-#pragma unroll
-    for (int o = 0; o < 8; ++o) {
-        float a = ldc(W.bb + o);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) a = __fmaf_rn(ldc(W.wb + (16 * (c >> 2) + o) * 4 + (c & 3)), t1[c], a);
-        t2[o] = fmaxf(a, 0.f);
-    }
-}
+// (the WeightNet's hidden layers, wn_hidden: wn_tile.h)
 // relu(Wc.t2 + bc) for the 32-channel block v in the tile layout (K = 8 on the fp32-input MFMA: four k-steps of two), in two
 // halves: this lane's operands of the block (bias, four weights: 20 registers), and the product.  The epilogues request block
 // v + 1's operands before they work on block v -- the conditional stores of a block end a basic block each, and hipcc's scheduler
@@ -199,20 +173,7 @@ __device__ __forceinline__ f16v wn_pre(const WnBlock &k, int hh, const float (&t
     for (int st = 0; st < 4; ++st) w = mfma_f32x2(k.w[st], hh ? t2[2 * st + 1] : t2[2 * st], w);
     return w;
 }
-// max(x, 0.1 x) and max(x, 0) in ONE instruction each.  fmaxf() costs two under IEEE mode -- hipcc first quiets a possible signalling
-// NaN in every operand it did not compute itself (v_max_f32 x, x, x on each accumulator read): 32 extra VALU instructions per
-// 32-channel block of the epilogue, 256 per layer boundary -- and a median with a literal +inf (v_med3_f32) is folded back into
-// exactly that maxnum.  Both are the median with a +inf the optimiser cannot see (an SGPR written by a volatile asm, once per
-// kernel: rtk_hidden_inf): ReLU = med3(x, 0, inf), LeakyReLU = med3(x, 0.1 x, inf) (leaky_med above) -- instructions the compiler
-// knows, so it places the wait states a matrix-core result needs itself (round 4's LeakyReLU was a written-out v_max_f32 that
-// relied on the product in front of it for that).  Same bits as fmaxf for every non-NaN input.
-__device__ __forceinline__ float rtk_hidden_inf() {
-    float v;
-    asm volatile("s_mov_b32 %0, 0x7f800000" : "=s"(v));
-    return v;
-}
-__device__ __forceinline__ float relu1(float x, float inf) { return __builtin_amdgcn_fmed3f(x, 0.f, inf); }
-__device__ __forceinline__ f4 relu_med4(f4 t, float inf) { return (f4){relu1(t.x, inf), relu1(t.y, inf), relu1(t.z, inf), relu1(t.w, inf)}; }
+// (relu1 / relu_med4, the one-instruction ReLU on a hidden +inf: wn_tile.h)
 
 // ---- layer 1's operands ---------------------------------------------------------------------------------------------------
 // The tile layout gives a lane 32 bytes of a gathered p2 row per load instruction (its own position's row, two lanes per position):

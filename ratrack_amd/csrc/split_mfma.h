@@ -36,8 +36,7 @@
 //     frag[s][v][p][lane = 32 hh + i][t] = piece_p( 2^k W[32 v + i][32 (s / 2) + 16 (s % 2) + 8 (t / 4) + 4 hh + t % 4] ),  p = 0: h, 1: l
 #pragma once
 #include "fused_common.h"
-
-typedef float f16v __attribute__((ext_vector_type(16)));
+#include "wn_tile.h"      // f16v, ldc / ldc4, the fp32-input 32x32 instruction, relu1
 
 __device__ __forceinline__ f16v mfma_h(u4v a, u4v b, f16v c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8v, a), __builtin_bit_cast(h8v, b), c, 0, 0, 0);
@@ -162,12 +161,6 @@ struct StoreRowsSide {            // h[e] -> 16 bytes at base + ro + 32 e  (this
         }
     }
 };
-// Loads of kernel-lifetime constants (weights, biases) through the constant address space: the compiler may move them over the
-// kernel's stores (a plain global load stays behind every store it might alias -- in the cost volume's epilogue that put one exposed
-// L2 round trip in front of each of the eight output blocks) and turns the wave-uniform ones into scalar loads.
-__device__ __forceinline__ float ldc(const float *p) { return *(const __attribute__((address_space(4))) float *)p; }
-__device__ __forceinline__ f4 ldc4(const float *p) { return *(const __attribute__((address_space(4))) f4 *)p; }
-
 // The layer's bias in the tile layout (slot e = 4 v + q: channels 32 v + 8 q + 4 hh + r) arrives in four QUARTERS of eight slots, each
 // requested while the quarter before it is being worked on (1 KiB per layer, the same for every tile: first-level cache hits); the
 // first one during the layer's last k-step (BiasSide, two slots per group step).  (All 32 slots at once are 128 registers next to
