@@ -149,12 +149,20 @@ RTK_EXPORT int rtk_cost_volume_split(int samples, int n1, int n2, const float *x
                                      const int64_t *knn_idx, const float *p1, const float *p2, const float *wd_packed,
                                      const void *split_images, const float *image_scales, const float *bias2,
                                      const float *bias3, const rtk_layer_t *wn, float *out, int out_pitch, rtk_stream_t stream);
-/* ... on a share of the chip.  The kernel keeps a CU whole (486 registers per lane, 112 KiB of LDS): launched with one workgroup per
+/* ... on a share of the chip.  The kernel keeps a CU whole (434 registers per lane, 144 KiB of LDS): launched with one workgroup per
  * CU it stops every other kernel for its duration.  With several batches in flight (ratrack_amd.fused.GraphPipeline) the step is
  * shorter when it takes `workgroups` < the CU count -- 3/4 of them at B = 64: the kernel itself runs 16 % longer, the pipelined
  * forward 2 % faster, the other batches' kernels keep a quarter of every XCD.  workgroups = 0: all CUs (rtk_cost_volume_split);
  * rounded down to a multiple of 8 (one share per XCD: all tiles of sample s run on XCD s % 8); ignored unless samples % 8 == 0. */
 RTK_EXPORT int rtk_cost_volume_split_shared(int samples, int n1, int n2, const float *xyz1, const float *xyz2,
+                                            const int64_t *knn_idx, const float *p1, const float *p2, const float *wd_packed,
+                                            const void *split_images, const float *image_scales, const float *bias2,
+                                            const float *bias3, const rtk_layer_t *wn, float *out, int out_pitch, int workgroups,
+                                            rtk_stream_t stream);
+/* rtk_cost_volume_split_shared as it was before the kernel kept its constants in LDS: layer 1's direction weights, the WeightNet's
+ * layers and the biases are read from global memory on every tile.  Same arguments, bit-identical result; the comparison implementation
+ * of tests and timing tools, not called by the package. */
+RTK_EXPORT int rtk_cost_volume_split_gconst(int samples, int n1, int n2, const float *xyz1, const float *xyz2,
                                             const int64_t *knn_idx, const float *p1, const float *p2, const float *wd_packed,
                                             const void *split_images, const float *image_scales, const float *bias2,
                                             const float *bias3, const rtk_layer_t *wn, float *out, int out_pitch, int workgroups,

@@ -175,6 +175,107 @@ __device__ __forceinline__ f16v wn_pre(const WnBlock &k, int hh, const float (&t
 }
 // (relu1 / relu_med4, the one-instruction ReLU on a hidden +inf: wn_tile.h)
 
+// CV_LDS_HIDDEN: the WeightNet's hidden weights (104 words, wave-uniform) in the image too, read as broadcasts into vector registers
+// instead of four 16-word scalar loads per tile into scalar registers the kernel does not have (they were spilled to lanes and back).
+#ifndef CV_LDS_HIDDEN
+#define CV_LDS_HIDDEN 1
+#endif
+// CV_WN_AHEAD: how many output blocks ahead of their use the epilogue requests a block's WeightNet operands from the LDS image (2: the
+// distance the global loads needed; 1: the block's operands are read at the top of the block before it).
+#ifndef CV_WN_AHEAD
+#define CV_WN_AHEAD 2
+#endif
+// ---- the forward kernel's constants, resident in LDS ----------------------------------------------------------------------------
+// What every tile of every workgroup reads and no tile owns -- layer 1's direction weights, the WeightNet's output layer and the three
+// 256-channel biases, 15 KiB -- is copied into LDS once per workgroup, permuted so that a lane's read in the tile loop is one ds_read at
+// an immediate offset from a per-lane base (lane * 4 for the A operands, 16 hh for the biases) instead of a global load behind 64-bit
+// address arithmetic.  A operands: [block v][k-step][lane], 64 consecutive words per read; biases: channel order, so that the slot
+// channels 32 v + 8 q + 4 hh .. + 3 is ONE 16-byte read with two distinct addresses per instruction (hh = 0, 1: broadcasts).
+struct CvConsts {
+    float wd[SPLIT_VB * 2 * 64];      // A[i = col][k = hh] of block v's two k-steps of [Wd | 0]: what ldc(wr + 16 (2 k + hh)) of cv_layer1_blocks reads
+    float wc[SPLIT_VB * 4 * 64];      // ... of block v's four k-steps of Wc: WnBlock::w[st]
+    float bc[256], bias2[256], bias3[256];
+#if CV_LDS_HIDDEN
+    float hid[128];                   // the WeightNet's hidden layers: [Wa | ba] as [k][o] (32), Wb as [o][c] (64), bb (8); every lane reads the same word
+#endif
+};
+static_assert(sizeof(CvConsts) == 15 * 1024 + (CV_LDS_HIDDEN ? 512 : 0), "4 + 8 + 3 KiB (+ the hidden layers)");
+// The fill in two halves: four 16-byte loads per thread (the biases by waves 0..2, one each), and the permuting stores.
+struct CvConstsFill {
+    f4 wd, wc[2], bias;
+    float hid;
+};
+__device__ __forceinline__ CvConstsFill cv_consts_load(const float *wd, const WnSplit &W, const float *bias2, const float *bias3, int wave, int lane) {
+    CvConstsFill k;
+    const int t = wave * 64 + lane;
+    k.wd = ldc4(wd + 4 * t);                                             // [g = channel / 16][m = 2 k + hh][channel % 16]: words 4 t .. 4 t + 3
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {                                        // the live half of the image (k < 8): 512 slots (g, k / 4, channel % 16) of four k
+        const int u = 256 * n + t;
+        k.wc[n] = ldc4(W.wc + (u >> 5) * 256 + ((u >> 4) & 1) * 64 + (u & 15) * 4);
+    }
+    const float *bs = wave == 0 ? W.bc : wave == 1 ? bias2 : bias3;      // (wave-uniform; wave 3's copy is not stored)
+    k.bias = ldc4(bs + 4 * lane);
+#if CV_LDS_HIDDEN
+    {
+        const int u = t < 32 ? 0 : t - 32, o = u >> 3, c = u & 7;          // threads 0..31: wa, 32..95: wb, 96..103: bb (the others: a word nobody stores)
+        const float *hs = t < 32 ? W.wa + 16 * (t >> 3) + (t & 7) : t < 96 ? W.wb + (16 * (c >> 2) + o) * 4 + (c & 3) : W.bb + (t < 104 ? t - 96 : 0);
+        k.hid = ldc(hs);
+    }
+#endif
+    return k;
+}
+__device__ __forceinline__ void cv_consts_store(CvConsts &C, const CvConstsFill &k, int wave, int lane) {
+    const int t = wave * 64 + lane;
+    {
+        const int g = t >> 4, m = (t >> 2) & 3;                          // block g / 2, columns 16 (g % 2) + 4 (t % 4) .. + 3, k-step m / 2, hh = m % 2
+        *reinterpret_cast<f4 *>(C.wd + ((g >> 1) * 2 + (m >> 1)) * 64 + (m & 1) * 32 + (g & 1) * 16 + 4 * (t & 3)) = k.wd;
+    }
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int u = 256 * n + t, g = u >> 5, kq = (u >> 4) & 1, c15 = u & 15;
+#pragma unroll
+        for (int k3 = 0; k3 < 4; ++k3)                                   // k = 4 kq + k3 = 2 st + hh
+            C.wc[((g >> 1) * 4 + 2 * kq + (k3 >> 1)) * 64 + (k3 & 1) * 32 + (g & 1) * 16 + c15] = k.wc[n][k3];
+    }
+    if (wave < 3) *reinterpret_cast<f4 *>((wave == 0 ? C.bc : wave == 1 ? C.bias2 : C.bias3) + 4 * lane) = k.bias;
+#if CV_LDS_HIDDEN
+    if (t < 104) C.hid[t] = k.hid;
+#endif
+}
+#if CV_LDS_HIDDEN
+// wn_hidden (wn_tile.h, ascending order) on the LDS image: the same operations on the same values
+__device__ __forceinline__ void wn_hidden_lds(const CvConsts &C, float dx, float dy, float dz, float (&t2)[8]) {
+    float t1[8];
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+        float a = __fmaf_rn(C.hid[o], dx, 0.f);
+        a = __fmaf_rn(C.hid[8 + o], dy, a);
+        a = __fmaf_rn(C.hid[16 + o], dz, a);
+        t1[o] = fmaxf(__fadd_rn(a, C.hid[24 + o]), 0.f);
+    }
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+        float a = C.hid[96 + o];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) a = __fmaf_rn(C.hid[32 + 8 * o + c], t1[c], a);
+        t2[o] = fmaxf(a, 0.f);
+    }
+}
+#endif
+// wn_block / split_bias from the LDS image: the same values into the same registers
+__device__ __forceinline__ WnBlock wn_block_lds(const CvConsts &C, int v, int hh, int lane) {
+    WnBlock k;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const f4 t = *reinterpret_cast<const f4 *>(C.bc + 32 * v + 8 * q + 4 * hh);
+        k.bias[4 * q] = t.x; k.bias[4 * q + 1] = t.y; k.bias[4 * q + 2] = t.z; k.bias[4 * q + 3] = t.w;
+    }
+#pragma unroll
+    for (int st = 0; st < 4; ++st) k.w[st] = C.wc[(4 * v + st) * 64 + lane];
+    return k;
+}
+
 // ---- layer 1's operands ---------------------------------------------------------------------------------------------------
 // The tile layout gives a lane 32 bytes of a gathered p2 row per load instruction (its own position's row, two lanes per position):
 // 32 partial cache lines per instruction, each fetched whole from L2 and -- four instructions in a row touching the same line
@@ -182,7 +283,7 @@ __device__ __forceinline__ f16v wn_pre(const WnBlock &k, int hh, const float (&t
 // of them gone when every lane reads the same row).  So the rows come through LDS instead: one global_load_lds per two positions
 // moves 2 x 512 contiguous bytes (channels 128 HALF .. 128 HALF + 127 of both rows) into the wave's own 16 KiB of LDS, every line
 // fetched once, and the lanes read their slots from there.  Two rounds per tile (HALF = 0, 1: 64 KiB per workgroup next to the
-// weight stream's 48, so that a CU keeps 48 KiB for other kernels' workgroups); round 0 of the NEXT tile is requested right after layer 1 and lands under layers 2 and 3.
+// weight stream's 64 and the 15 KiB of constants); round 0 of the NEXT tile is requested right after layer 1 and lands under layers 2 and 3.
 // Slot p of a position's 512 bytes holds source chunk p ^ (position & 15): the 16 lanes that read together (one hh, 16 positions)
 // then hit 16 different bank groups.
 constexpr int CV_ROWS_F4 = 32 * 32;      // f4 per wave: 32 positions x 32 slots of 16 bytes
@@ -264,8 +365,8 @@ __device__ __forceinline__ f4 mul_row_bcast(const f4 q, const f4 r) {
 __device__ __forceinline__ f4 add4_rn(const f4 a, const f4 b) {
     return (f4){__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w)};
 }
-template <int V0, int V1>
-__device__ __forceinline__ void cv_layer1_blocks(const CvSplitParams &P, const f4 q0, const f4 q1, float b0, float b1, int hh, int col, float kinf, f4 (&h)[32]) {
+template <int V0, int V1, bool LDSC>
+__device__ __forceinline__ void cv_layer1_blocks(const CvSplitParams &P, const CvConsts &C, const f4 q0, const f4 q1, float b0, float b1, int hh, int col, float kinf, f4 (&h)[32]) {
     static_assert(V1 <= 8, "eight 32-channel blocks");
     auto block = [&](auto vc) {
         constexpr int v = decltype(vc)::value;
@@ -277,10 +378,16 @@ __device__ __forceinline__ void cv_layer1_blocks(const CvSplitParams &P, const f
         };
         slot(std::integral_constant<int, 0>{}); slot(std::integral_constant<int, 1>{});
         slot(std::integral_constant<int, 2>{}); slot(std::integral_constant<int, 3>{});
-        const int ch = 32 * v + col;                         // A[i = col][k = hh]
-        const float *wr = P.wd + (ch >> 4) * 64 + (ch & 15);
-        c = mfma_f32x2(ldc(wr + 16 * hh), b0, c);
-        c = mfma_f32x2(ldc(wr + 16 * (2 + hh)), b1, c);
+        float a0, a1;                                        // A[i = col][k = hh] of the two k-steps
+        if constexpr (LDSC) {
+            a0 = C.wd[(2 * v) * 64 + 32 * hh + col]; a1 = C.wd[(2 * v + 1) * 64 + 32 * hh + col];
+        } else {
+            const int ch = 32 * v + col;
+            const float *wr = P.wd + (ch >> 4) * 64 + (ch & 15);
+            a0 = ldc(wr + 16 * hh); a1 = ldc(wr + 16 * (2 + hh));
+        }
+        c = mfma_f32x2(a0, b0, c);
+        c = mfma_f32x2(a1, b1, c);
 #pragma unroll
         for (int q = 0; q < 4; ++q) h[4 * v + q] = leaky_med4((f4){c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]}, kinf);
     };
@@ -296,12 +403,15 @@ __device__ __forceinline__ void cv_layer1_blocks(const CvSplitParams &P, const f
 #ifndef CV_FWD_VGPRS
 #define CV_FWD_VGPRS 448
 #endif
-template <bool SAVE>
+// LDSC: the constants come from the LDS image (CvConsts); false: from global memory on every tile, the kernel as it was before the
+// image existed -- kept as the comparison implementation (rtk_cost_volume_split_gconst), same arithmetic on the same values.
+template <bool SAVE, bool LDSC = true>
 __global__ __launch_bounds__(64 * SP_NW) __attribute__((amdgpu_waves_per_eu(1, 1), amdgpu_num_vgpr(CV_FWD_VGPRS)))
 void cost_volume_split_kernel(const CvSplitParams P) {
     const float kinf = rtk_hidden_inf();
     __shared__ __attribute__((aligned(16))) f4 s_w[2 * CV_F * 64];
     __shared__ __attribute__((aligned(16))) f4 s_rows[SP_NW * CV_ROWS_F4];
+    __shared__ __attribute__((aligned(16))) CvConsts s_c;      // (LDSC; 64 + 64 + 15 KiB of the CU's 160: the registers give the workgroup the CU anyway)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hh = lane >> 5, col = lane & 31, pp = col >> 4,
               j = col & 15;      // wave index in an SGPR: the DMA's LDS destination (M0) is then scalar arithmetic
     f4 *rows = s_rows + wave * CV_ROWS_F4;
@@ -320,7 +430,20 @@ void cost_volume_split_kernel(const CvSplitParams P) {
     int b, bx;
     locate(t0 < ntiles ? t0 : 0, b, bx);
     WStreamA<SP_NW, CV_F, 2 * SPLIT_NF> ws;
+    // The constants' loads travel with the stream's first chunk; their stores and barrier come after start_parts' own, by every thread of
+    // every workgroup (also one that has no tile).
+    CvConstsFill cfill;
+    if constexpr (LDSC) cfill = cv_consts_load(P.wd, P.wn, P.bias2, P.bias3, wave, lane);
     ws.start_parts(P.blob, s_w, wave, lane);
+    if constexpr (LDSC) {
+        cv_consts_store(s_c, cfill, wave, lane);
+        __syncthreads();
+    }
+    const float *bias2 = (LDSC ? s_c.bias2 : P.bias2) + 4 * hh, *bias3 = (LDSC ? s_c.bias3 : P.bias3) + 4 * hh;
+    auto wnb = [&](int v) {
+        if constexpr (LDSC) return wn_block_lds(s_c, v, hh, lane);
+        else return wn_block(P.wn, v, hh, col);
+    };
     const float wi2 = ldc(P.wsc), wi3 = ldc(P.wsc + 1);
     // The tile loop is software-pipelined by one tile (round 4): the NEXT tile's neighbour index is requested at the top of the
     // CURRENT tile, the first half of its gathered rows (cv_rows_request<0>) right after layer 1, its direction and its two p1 slots
@@ -357,13 +480,17 @@ void cost_volume_split_kernel(const CvSplitParams P) {
             const float b0 = hh ? dy : dx, b1 = hh ? 0.f : dz;      // B[k = hh][col] of the two k-steps (k = 3: the zero column)
             cv_rows_read<0>(rows, col, hh, h);
             cv_rows_request<1>(P.p2, (int)nb, rows, lane);
-            cv_layer1_blocks<0, 4>(P, q0, q1, b0, b1, hh, col, kinf, h);
+            cv_layer1_blocks<0, 4, LDSC>(P, s_c, q0, q1, b0, b1, hh, col, kinf, h);
             // the WeightNet's hidden layers (3 -> 8 -> 8: ~100 VALU instructions on the direction only) HERE, where the wave would
             // otherwise wait for round 1 of the rows -- they used to open the output epilogue, exposed (8 registers across the layers)
-            wn_hidden(P.wn, dx, dy, dz, t2);
+#if CV_LDS_HIDDEN
+            if constexpr (LDSC && !SAVE) wn_hidden_lds(s_c, dx, dy, dz, t2);      // (the training forward with it: 25 registers spilled to scratch)
+            else
+#endif
+                wn_hidden(P.wn, dx, dy, dz, t2);
             __builtin_amdgcn_sched_barrier(0);      // (round 1's reads wait for the DMA: hipcc would hoist them, and the wait, above the four blocks)
             cv_rows_read<1>(rows, col, hh, h);
-            cv_layer1_blocks<4, 8>(P, q0, q1, b0, b1, hh, col, kinf, h);
+            cv_layer1_blocks<4, 8, LDSC>(P, s_c, q0, q1, b0, b1, hh, col, kinf, h);
         }
         const long nbn = (long)bn * P.n2 + knn_next;      // (no next tile: row 0 of the sample, requested and never read)
         // byte offset of this lane's first 16-byte slot in a (position, 256) row (one 32-bit VGPR on uniform base pointers)
@@ -381,9 +508,9 @@ void cost_volume_split_kernel(const CvSplitParams P) {
         LaneScale sc = lane_scale32(h);
         if (SAVE && P.amax) tensor_amax_update(P.amax, sc.mb);
         split_layer<0>(ws, h, sc.s, acc, SidePair<CvLayer2Side<SAVE>, BiasSide>{{StoreRowsSide{P.sv1, ro, valid}, CvRowsRequest(P.p2, rows, (int)nbn, 0, lane)},
-                                                                              BiasSide{P.bias2 + 4 * hh, bq}});
+                                                                              BiasSide{bias2, bq}});
         float c = sc.inv * wi2;
-        split_epilogue(acc, P.bias2 + 4 * hh, bq, [&](int e, f4 a, f4 b) { h[e] = leaky_med4(scale_bias4(a, c, b), kinf); });
+        split_epilogue(acc, bias2, bq, [&](int e, f4 a, f4 b) { h[e] = leaky_med4(scale_bias4(a, c, b), kinf); });
         if (SAVE && valid) {
             uint2 m[2];
             split_sign_masks(h, m);
@@ -392,25 +519,31 @@ void cost_volume_split_kernel(const CvSplitParams P) {
         }
         sc = lane_scale32(h);
         if (SAVE && P.amax) tensor_amax_update(P.amax + 1, sc.mb);
-        if (SAVE) split_layer<SPLIT_NF>(ws, h, sc.s, acc, SidePair<StoreRowsSide, BiasSide>{StoreRowsSide{P.sv2, ro, valid}, BiasSide{P.bias3 + 4 * hh, bq}});
-        else split_layer<SPLIT_NF>(ws, h, sc.s, acc, BiasSide{P.bias3 + 4 * hh, bq});
+        if (SAVE) split_layer<SPLIT_NF>(ws, h, sc.s, acc, SidePair<StoreRowsSide, BiasSide>{StoreRowsSide{P.sv2, ro, valid}, BiasSide{bias3, bq}});
+        else split_layer<SPLIT_NF>(ws, h, sc.s, acc, BiasSide{bias3, bq});
         ws.sync();                                                   // wrap the stream to chunk 0
         c = sc.inv * wi3;
-        split_epilogue(acc, P.bias3 + 4 * hh, bq, [&](int e, f4 a, f4 b) { h[e] = leaky_med4(scale_bias4(a, c, b), kinf); });      // a3
+        split_epilogue(acc, bias3, bq, [&](int e, f4 a, f4 b) { h[e] = leaky_med4(scale_bias4(a, c, b), kinf); });      // a3
         if (SAVE && valid) {
 #pragma unroll
             for (int e = 0; e < 32; ++e) *cv_at(P.sv3, ro + 32u * e) = h[e];
         }
-        WnBlock wk = wn_block(P.wn, 0, hh, col);
+        WnBlock wk = wnb(0);
         // out[i] = sum over the 16 neighbours of relu(Wc.t2 + bc) * a3, one 32-channel block at a time; block v + 1's four
         // dependent MFMAs (K = 8 in steps of 2) run under block v's VALU / DPP work, block v + 2's operands travel meanwhile
         float *o = P.out + i * P.out_pitch + 4 * hh;
         f16v wpre = wn_pre(wk, hh, t2);
-        wk = wn_block(P.wn, 1, hh, col);
+        constexpr bool ahead1 = LDSC && CV_WN_AHEAD == 1;
+        if constexpr (!ahead1) wk = wnb(1);
         auto out_block = [&](int v) {
             const f16v w = wpre;
+            if constexpr (ahead1) {
+                if (v + 1 < SPLIT_VB) wk = wnb(v + 1);
+            }
             if (v + 1 < SPLIT_VB) wpre = wn_pre(wk, hh, t2);
-            if (v + 2 < SPLIT_VB) wk = wn_block(P.wn, v + 2, hh, col);
+            if constexpr (!ahead1) {
+                if (v + 2 < SPLIT_VB) wk = wnb(v + 2);
+            }
             f4 r[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q)
@@ -790,7 +923,7 @@ static int cv_split_forward(const char *who, int samples, int n1, int n2, const 
                             const float *p1, const float *p2, const float *wd_packed, const void *split_images, const float *image_scales,
                             const float *bias2, const float *bias3, const rtk_layer_t *wn, float *out, int out_pitch, float *a1, float *a2,
                             float *a3, void *mask1, void *mask2, float *amax, int workgroups, rtk_stream_t stream,
-                            const float *sample_term = nullptr) {
+                            const float *sample_term = nullptr, bool global_consts = false) {
     CvSplitParams P;
     dim3 grid;
     if (cv_split_fill(who, P, samples, n1, n2, xyz1, xyz2, knn_idx, split_images, image_scales, wn, grid) != RTK_OK) return RTK_ERR_INVALID;
@@ -811,6 +944,7 @@ static int cv_split_forward(const char *who, int samples, int n1, int n2, const 
         grid = dim3(P.gx);
     }
     if (save) cost_volume_split_kernel<true><<<grid, 64 * SP_NW, 0, (hipStream_t)stream>>>(P);
+    else if (global_consts) cost_volume_split_kernel<false, false><<<grid, 64 * SP_NW, 0, (hipStream_t)stream>>>(P);
     else cost_volume_split_kernel<false><<<grid, 64 * SP_NW, 0, (hipStream_t)stream>>>(P);
     RTK_CHECK_LAUNCH(who);
     return RTK_OK;
@@ -831,6 +965,15 @@ extern "C" int rtk_cost_volume_split_shared(int samples, int n1, int n2, const f
     RTK_REQUIRE(workgroups >= 0, "cost_volume_split_shared: workgroups = %d", workgroups);
     return cv_split_forward("cost_volume_split_shared", samples, n1, n2, xyz1, xyz2, knn_idx, p1, p2, wd_packed, split_images, image_scales,
                             bias2, bias3, wn, out, out_pitch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workgroups, stream);
+}
+
+extern "C" int rtk_cost_volume_split_gconst(int samples, int n1, int n2, const float *xyz1, const float *xyz2, const int64_t *knn_idx,
+                                            const float *p1, const float *p2, const float *wd_packed, const void *split_images,
+                                            const float *image_scales, const float *bias2, const float *bias3, const rtk_layer_t *wn,
+                                            float *out, int out_pitch, int workgroups, rtk_stream_t stream) {
+    RTK_REQUIRE(workgroups >= 0, "cost_volume_split_gconst: workgroups = %d", workgroups);
+    return cv_split_forward("cost_volume_split_gconst", samples, n1, n2, xyz1, xyz2, knn_idx, p1, p2, wd_packed, split_images, image_scales,
+                            bias2, bias3, wn, out, out_pitch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workgroups, stream, nullptr, true);
 }
 
 extern "C" int rtk_cost_volume_split_term(int samples, int n1, int n2, const float *xyz1, const float *xyz2, const int64_t *knn_idx,

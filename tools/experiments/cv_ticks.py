@@ -38,14 +38,14 @@ PATCHES = [
      "    for (int t = t0; t < ntiles; t += tstep) {\n        asm volatile(\"\" ::: \"memory\");\n        CV_TICK(0)\n        // the next tile's neighbour index" % NT),
     ("        // byte offset of this lane's first 16-byte slot in a (position, 256) row (one 32-bit VGPR on uniform base pointers)\n        const long pos = i * 16 + j;",
      "        CV_TICK(1)\n        const long pos = i * 16 + j;"),
-    ("        LaneScale sc = lane_scale32(h);\n        split_layer<0>(ws, h, sc.s, acc, SidePair<CvLayer2Side<SAVE>",
-     "        LaneScale sc = lane_scale32(h);\n        CV_TICK(12)\n        split_layer<0>(ws, h, sc.s, acc, SidePair<CvLayer2Side<SAVE>"),
+    ("        if (SAVE && P.amax) tensor_amax_update(P.amax, sc.mb);\n        split_layer<0>(ws, h, sc.s, acc, SidePair<CvLayer2Side<SAVE>",
+     "        if (SAVE && P.amax) tensor_amax_update(P.amax, sc.mb);\n        CV_TICK(12)\n        split_layer<0>(ws, h, sc.s, acc, SidePair<CvLayer2Side<SAVE>"),
     ("        float c = sc.inv * wi2;\n", "        CV_TICK(2)\n        float c = sc.inv * wi2;\n"),
-    ("        sc = lane_scale32(h);\n        if (SAVE) split_layer<SPLIT_NF>", "        sc = lane_scale32(h);\n        CV_TICK(3)\n        if (SAVE) split_layer<SPLIT_NF>"),
+    ("        if (SAVE && P.amax) tensor_amax_update(P.amax + 1, sc.mb);\n        if (SAVE) split_layer<SPLIT_NF>",
+     "        if (SAVE && P.amax) tensor_amax_update(P.amax + 1, sc.mb);\n        CV_TICK(3)\n        if (SAVE) split_layer<SPLIT_NF>"),
     ("        ws.sync();                                                   // wrap the stream to chunk 0\n        c = sc.inv * wi3;\n",
      "        CV_TICK(4)\n        ws.sync();                                                   // wrap the stream to chunk 0\n        CV_TICK(5)\n        c = sc.inv * wi3;\n"),
-    ("        WnBlock wk = wn_block(P.wn, 0, hh, col);                     // block 0's operands travel during the hidden layers",
-     "        CV_TICK(13)\n        WnBlock wk = wn_block(P.wn, 0, hh, col);                     // block 0's operands travel during the hidden layers"),
+    ("        WnBlock wk = wnb(0);\n", "        CV_TICK(13)\n        WnBlock wk = wnb(0);\n"),
     ("        float *o = P.out + i * P.out_pitch + 4 * hh;\n        f16v wpre", "        CV_TICK(6)\n        float *o = P.out + i * P.out_pitch + 4 * hh;\n        f16v wpre"),
     ("        out_block(0);\n        out_block(1);\n", "        out_block(0);\n        CV_TICK(7)\n        out_block(1);\n        CV_TICK(8)\n"),
     ("#pragma unroll\n        for (int v = 2; v < SPLIT_VB; ++v) out_block(v);\n        pt = ptn;",
@@ -113,6 +113,9 @@ def main():
     ap.add_argument("--bwd", action="store_true", help="the backward kernel (cost_volume_bwd_split_kernel) instead of the forward one")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--so", default=SO, help="the instrumented library to run")
+    ap.add_argument("--variant", choices=("lds", "gconst"), default="lds", help="forward: the kernel with its constants in LDS (the product's) or "
+                    "in global memory (rtk_cost_volume_split_gconst); both through the entry point without the per-sample term, on p1 + term")
+    ap.add_argument("--workgroups", type=int, default=0, help="forward: workgroups of the launch (0: one per CU)")
     a = ap.parse_args()
     if a.build:
         return build(a.same_row, a.src, a.totals_only, os.path.abspath(a.out), [os.path.dirname(os.path.abspath(a.src))] if a.src else [], a.defs, a.bwd)
@@ -134,10 +137,11 @@ def main():
         with torch.no_grad():
             net.backbone(*t, None)
             eng = net._fused_engine()
-            eng.time_dominant_kernel(5)
-            ev = eng.time_dominant_kernel(30)
-        ms = sorted(s.elapsed_time(e) for s, e in ev)
-        print("cost volume forward B=%d alone (instrumented build): median %.1f us" % (a.batch, ms[len(ms) // 2] * 1e3))
+            from cv_consts_ab import variant_launcher, time_launches
+            go = variant_launcher(eng, a.variant, a.workgroups)
+            time_launches(go, 5)
+            ms = sorted(time_launches(go, 30))
+        print("cost volume forward B=%d alone, constants: %s (instrumented build): median %.1f us" % (a.batch, a.variant, ms[len(ms) // 2] * 1e3))
     buf = (ctypes.c_ulonglong * (1024 * 16))()
     rc = L.load().rtk_dbg_cv_ticks(buf)
     assert rc == 0, rc
@@ -147,8 +151,11 @@ def main():
     groups = 256 // 8
     gx = max(1, min(256 // a.batch, groups))
     tiles = groups / gx
+    if not a.bwd and a.batch % 8 == 0:      # the flat grid: `workgroups` (a multiple of 8, at most one per tile) over batch / 8 * groups tiles per XCD
+        per_xcd = max(1, min((a.workgroups or 256) // 8, a.batch // 8 * groups))
+        tiles = (a.batch // 8 * groups) / per_xcd
     names = ["loop top", "layer 1 (rows through LDS, Wd.d, leaky)", "layer 2 (64 group steps of 6 MFMAs)", "a2 = leaky(acc c + b), position scale",
-             "layer 3 (64 group steps)", "stream wrap sync", "epilogue: next index request, block 0 operands, WeightNet hidden layers",
+             "layer 3 (64 group steps)", "stream wrap sync", "epilogue: block 0's operands requested",
              "epilogue: output block 0", "epilogue: output block 1", "epilogue: next tile's coordinates requested", "epilogue: output blocks 2..7",
              "epilogue: next direction (waits for the coordinates)", "position scale of a1 (max scan + swap)", "a3 = leaky(acc c + b)"]
     tot, wall = tk[:, 14].mean(), tk[:, 15].mean()
