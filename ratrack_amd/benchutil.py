@@ -110,7 +110,7 @@ def irregular_ops(batch, n, dev, npoint=512, iters=20, pmc=None):
         add("ball_query_pair_kernel[l%d]" % (lvl + 1), 1, ms, S_ * (nsrc * 12 + U[lvl] * (12 + 4 * (n1 + n2))),
             "r=(%g,%g) ns=(%d,%d), %d source points" % (r1, r2, n1, n2, src.shape[1]))
     # ---- three nearest neighbours ----------------------------------------------------------------------------------------
-    for name, (u, k) in {"fp3": (2, 3), "fp2": (1, 2), "fp1": (0, 1)}.items():
+    for name, u, k in fused.INTERP_LEVELS:
         d2, ix, m = geo.nn[name]
         nu = geo.xyz[u].shape[1]
         mask = geo.nuniq[u - 1].data_ptr() if u > 0 else None

@@ -53,6 +53,10 @@ __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
     constexpr int VL = V3 ? V3 : V2;                 // width of the last layer
     constexpr int TILES = NS > 16 ? NS / 16 : 1;     // tiles per work unit (NS = 32: one centroid = 2 tiles)
     constexpr int CPT = NS >= 16 ? 1 : 16 / NS;      // centroids per tile
+    // The last tile may straddle dst_nuniq.  Its lanes past live_c are redirected to centroid live_c - 1 BEFORE the index load below, so
+    // this kernel reads no ball row >= live_c; were the load to precede the mask, the rows of the whole tile lie inside the zero tail
+    // that ball_query_pair_body writes after the last live centroid:
+    static_assert(RTK_BALL_TAIL_ROWS % CPT == 0, "a tile of CPT centroids must not reach past the ball tables' zero tail");
     __shared__ __attribute__((aligned(16))) f4 s_w[NF * 64];
     const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
     // A workgroup owns one sample and strides over its centroid groups -- the index arithmetic inside the loop is 32-bit and

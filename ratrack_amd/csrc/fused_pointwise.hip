@@ -155,6 +155,10 @@ __device__ __forceinline__ void load_interp(const PwParams &P, int p, int b, int
 }
 
 #define PW_NW 4    // waves per workgroup
+// A workgroup steps over groups of PW_NW * 16 rows, and load_interp reads the three-NN rows of the whole last group -- the rows past
+// row_nuniq too, clamped to the sample, masked only at the store.  The three-NN kernels write whole multiples of this group
+// (ops_pointnet2.hip asserts KV_QPW % RTK_INTERP_ROW_GROUP == 0), so those rows hold in-range indices even in an unfilled workspace.
+static_assert(PW_NW * 16 == RTK_INTERP_ROW_GROUP, "PW_NW: the row group the three-NN tables are written for");
 #ifndef PW_WGS_TARGET
 #define PW_WGS_TARGET 256      // workgroups per launch: about one per CU, the rest is looped.  Round 6, same box, alternating (ab_knobs.py):
                                // 512 (rounds 2-5): base; 448 / 384 / 320: +0.4 ... +0.5 %; 256: +0.9 % (B=64, N=256), +1.0 % (B=32, N=1024), +-0.1 %

@@ -777,6 +777,9 @@ struct SaSplitParams {
 template <int NS, int C1>
 __global__ __launch_bounds__(256, SA_SPLIT_WAVES) void sa_scale_split_kernel(const SaSplitParams P) {
     constexpr int KS = C1 / 16, VB1 = C1 / 32, NFR = KS * 2 * 2, CPT = 32 / NS;      // k-steps, 32-blocks of layer 1, fragments, centroids per tile
+    // (as in sa_scale_kernel, fused_group.hip: the lanes of the last tile past live_c are redirected to centroid live_c - 1 before the
+    // index load; the whole tile lies inside the zero tail ball_query_pair_body writes)
+    static_assert(RTK_BALL_TAIL_ROWS % CPT == 0, "a tile of CPT centroids must not reach past the ball tables' zero tail");
     const float kinf = rtk_hidden_inf();
     __shared__ __attribute__((aligned(16))) f4 s_img[NFR * 64];
     const int lane = threadIdx.x & 63, hh = lane >> 5, col = lane & 31, pp = col / NS, slot = col % NS;

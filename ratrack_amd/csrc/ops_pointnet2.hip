@@ -591,9 +591,10 @@ __device__ __forceinline__ void ball_query_pair_body(int bs, int chunk0, int chu
     const int n_full = n;
     if (src_nuniq) n = max(1, min(n, src_nuniq[bs]));
     if (chunk0 == 0) {
-        // rows [climit, next multiple of 32) read as zeros: a consumer's last tile of centroids may load the index rows of the (skipped)
-        // duplicates next to the live ones before it masks them, and the tables need not be zero-filled by the caller for that
-        const int z1 = min(m, (climit + 31) & ~31);
+        // rows [climit, next multiple of RTK_BALL_TAIL_ROWS) read as zeros, so that a consumer whose last tile of centroids loads the index
+        // rows of the (skipped) duplicates next to the live ones before it masks them finds valid indices in an unfilled table.  The SA
+        // kernels mask first and do not read these rows; they assert that their tile divides the tail (fused_group.hip, fused_split.hip)
+        const int z1 = min(m, (climit + RTK_BALL_TAIL_ROWS - 1) & ~(RTK_BALL_TAIL_ROWS - 1));
         int *za = idxa + ((size_t)bs * m + climit) * nsa, *zb = idxb + ((size_t)bs * m + climit) * nsb;
         for (int l = tid; l < (z1 - climit) * nsa; l += 64 * BQ_WAVES) za[l] = 0;
         for (int l = tid; l < (z1 - climit) * nsb; l += 64 * BQ_WAVES) zb[l] = 0;
@@ -920,6 +921,10 @@ __device__ __forceinline__ void kv_row_merge(unsigned (&d)[K], int (&i)[K]) {
 #define KV_LPQ 4
 #endif
 constexpr int KV_QPW = 256 / KV_LPQ;      // queries per 256-thread workgroup (= per chunk)
+// three_nn_body writes the rows of whole chunks, [0, min(n, roundup(nuniq, KV_QPW))); the per-point kernel that interpolates with the
+// table loads the rows [nuniq, min(n, roundup(nuniq, RTK_INTERP_ROW_GROUP))) of an UNFILLED workspace before it masks them: every
+// row group that holds a live row must lie inside a written chunk
+static_assert(KV_QPW % RTK_INTERP_ROW_GROUP == 0, "KV_LPQ: a three-NN chunk must be a whole number of the per-point kernels' row groups");
 
 // ------------------------------------------------------------------------------------------------
 // three_nn   (interpolate_gpu.cu:81-124)

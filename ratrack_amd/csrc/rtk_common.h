@@ -95,6 +95,18 @@ __device__ __forceinline__ double rtk_stat_read(const double *tagged, size_t gc2
 
 #define RTK_WAVE 64
 
+// Row granularities shared by the geometry kernels and the consumers of their index tables.  The eval path hands the geometry an index
+// workspace it has NOT filled (ratrack_amd/fused.py, Geometry), so a consumer that loads the index rows of its whole tile before it
+// masks the rows past the sample's last live one needs a producer that writes whole multiples of that tile.  The static_asserts next
+// to each producer and consumer state the divisibility.
+// The per-point kernels (fused_pointwise.hip) rely on it: their interpolation prologue loads the three-NN rows of a whole row group.
+constexpr int RTK_INTERP_ROW_GROUP = 64;
+// ball_query_pair_body zero-writes the rows from the last live centroid to the next multiple of this.  No kernel relies on it today (both
+// SA kernels redirect the lanes past the last live centroid before they load an index row); the tail and the asserts keep a tile that
+// loads first safe.
+constexpr int RTK_BALL_TAIL_ROWS = 32;
+static_assert((RTK_BALL_TAIL_ROWS & (RTK_BALL_TAIL_ROWS - 1)) == 0, "RTK_BALL_TAIL_ROWS: the tail is rounded up with a mask");
+
 void rtk_set_error(const char *fmt, ...);
 
 #define RTK_REQUIRE(cond, ...)            \

@@ -13,6 +13,7 @@ All results agree with the module path / CPU oracle within fp32 rounding (tests:
 """
 import ctypes
 import os
+import types
 
 import torch
 
@@ -368,8 +369,12 @@ class _PNHeadWeights:
 
 FUSED_GEOMETRY = True          # the geometry of a batch in two launches (rtk_geometry_front / rtk_geometry_tables); False (tests): the eleven
                                # launches of the separate entry points they replace -- the same tables bit for bit
-GEOMETRY_POISON = None         # tests: an int32 pattern for the (otherwise uninitialised) index workspace of the two-launch eval geometry
+GEOMETRY_POISON = None         # tests: an IN-RANGE index to fill the eval geometry's (otherwise uninitialised) index workspace with: no output bit may depend on it
 CHECK_FPS_RELEVEL = False      # debug: compare every re-levelling launch with the full selection (synchronises; tests set it)
+
+# The interpolation (feature propagation) levels in the order they run: (table name, level of the unknown rows, level of the known rows).
+# Level 0 = the cloud's own n points, level l > 0 = the npoint centroids of set-abstraction level l.
+INTERP_LEVELS = (("fp3", 2, 3), ("fp2", 1, 2), ("fp1", 0, 1))
 
 
 def check_fps_relevel(xyz1, idx, new_xyz, nuniq):
@@ -389,12 +394,38 @@ def check_fps_relevel(xyz1, idx, new_xyz, nuniq):
         src = out
 
 
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
+def _geometry_workspace(xyz, npoint, knn_frames, finite, zeros, fused_geo):
+    """Every buffer of one Geometry as named flat tensors, allocated on the CURRENT stream (the caller forks afterwards)."""
+    (S_, n, _), dev = xyz.shape, xyz.device
+    ball_sizes = [S_ * npoint * ns for row in _PNHeadWeights.NSAMPLES for ns in row]
+    nn_sizes = [S_ * (n if u == 0 else npoint) * 3 for _, u, _ in INTERP_LEVELS]
+    # one int32 workspace: 3 FPS index rows, 3 exhausted-cloud counters, the tie state, 6 ball-query tables (zero-initialised once: the
+    # caller-zero-inits contract of ball_query, lib/pointnet2_utils.py:246) and 3 three-NN index tables
+    sizes = [S_ * npoint] * 3 + [S_] * 3 + [S_, 2 * S_, S_] + ball_sizes + nn_sizes
+    # The two-launch geometry writes every entry a consumer reads (the skipped rows of duplicate centroids are read by nothing: every
+    # consumer takes the duplicate-row counters, and the three-NN rows its last row group loads past them are written too, see
+    # RTK_INTERP_ROW_GROUP in csrc/rtk_common.h), so the eval path's index workspace is not filled (a 9 MB fill per batch until round 6).
+    # Everything else -- the separate launches, `finite`, a caller's allocator -- gets zeros.
+    unfilled = fused_geo and not finite and zeros is None
+    alloc = zeros or (lambda n_, dtype, device: torch.zeros(n_, dtype=dtype, device=device))
+    if unfilled:
+        ints = torch.empty(sum(sizes), dtype=torch.int32, device=dev)
+        if GEOMETRY_POISON is not None:
+            ints.fill_(GEOMETRY_POISON)
+    else:
+        ints = alloc(sum(sizes), torch.int32, dev)
+    p = torch.split(ints, sizes)
+    w = types.SimpleNamespace(fps_idx=p[0:3], cnt=p[3:6], tie=p[6], tie23=p[7], first_tie=p[8], ball=p[9:15], nn_idx=p[15:18])
+    # level-1 min-distance state at the first tied round, by point index (written for tied clouds only); large clouds take the generic
+    # FPS instead (no tie information), whose distance state is temp
+    w.snap = torch.empty(S_ * n, dtype=torch.float32, device=dev) if n <= 2048 else None
+    w.temp = torch.full((S_, n), 1e10, dtype=torch.float32, device=dev) if n > 2048 else None
+    w.xyz_all = torch.empty(3, S_, npoint, 3, dtype=torch.float32, device=dev)
+    # finite: the three-NN distances of the skipped (duplicate) rows read as zeros
+    d2 = alloc(sum(nn_sizes), torch.float32, dev) if finite else torch.empty(sum(nn_sizes), dtype=torch.float32, device=dev)
+    w.nn_d2 = torch.split(d2, nn_sizes)
+    w.knn = [torch.empty(knn_frames, n, 16, dtype=torch.int64, device=dev) for _ in range(2)] if knn_frames else None
+    return w
 
 
 class Geometry:
@@ -403,183 +434,133 @@ class Geometry:
 
     def __init__(self, xyz, npoint, side=None, knn_frames=0, finite=False, n_valid=None, level_hook=None, tail_hook=None, zeros=None,
                  prepare=None, q1=None):
-        """xyz (S_,n,3).  prepare = (pc1, pc2, feature1, feature2, raw): xyz and raw (S_*n, 4) are OUTPUTS -- the API's channel-major
-        tensors of the two frames are converted on the way (rtk_prepare_inputs, inside rtk_geometry_front when the geometry is fused).
-        q1 = (w (C, 2) fp32, out (S_*n, C)) with prepare: out = w . (the two raw features of every point), written by the same launch when
-        the geometry is fused (self.q1_done says whether it was).  With `side` (a torch.cuda.Stream) every geometry kernel is enqueued on that stream, forked from
-        the current one, and consumers call wait(stage) -- the feature kernels overlap the latency-bound FPS chain.
+        """xyz (S_, n, 3): the clouds, point-major (an OUTPUT with `prepare`).
+        npoint: centroids per set-abstraction level.
+        side: a torch.cuda.Stream -- every geometry kernel is enqueued on it, forked from the current stream, and consumers call
+            wait(stage); the feature kernels overlap the latency-bound FPS chain.
         knn_frames = B > 0: also the two kNN tables of the cost volume, frame 1 = xyz[:B], frame 2 = xyz[B:].
-        finite: zero-fill the three-NN distances of the skipped (duplicate) rows instead of leaving them unwritten
-        (the training path computes -- and ignores -- those rows, so they must hold finite numbers).
-        n_valid (S_,) int32: padded batch (ratrack_amd/vod_gt.pad_frame_pairs) -- cloud s consists of its first n_valid[s]
-        points, the rest are copies of its point 0; FPS applies the unpadded cloud's tie rule and the kNN tables only
-        hold valid candidates, everything else is exact through the duplicate-of-point-0 property.
-        level_hook(geo, lvl) / tail_hook(geo): called (on the geometry stream) right after level lvl's ball query, before its
-        event is recorded / after the three-NN tables -- the training path enqueues its per-level tables there.
-        zeros(n, dtype, device): allocator of the zero-initialised workspaces (default torch.zeros; the training path passes its
-        step arena, whose one fill then covers these too)."""
-        zeros_given = zeros
-        zeros = zeros or (lambda n_, dtype, device: torch.zeros(n_, dtype=dtype, device=device))
+        finite: zero-fill the three-NN distances of the skipped (duplicate) rows instead of leaving them unwritten (the training path
+            computes -- and ignores -- those rows, so they must hold finite numbers).
+        n_valid (S_,) int32: padded batch (ratrack_amd/vod_gt.pad_frame_pairs) -- cloud s consists of its first n_valid[s] points, the
+            rest are copies of its point 0; FPS applies the unpadded cloud's tie rule and the kNN tables only hold valid candidates,
+            everything else is exact through the duplicate-of-point-0 property.
+        level_hook(geo, lvl) / tail_hook(geo): called on the geometry stream right after level lvl's ball query, before its event is
+            recorded / after the three-NN tables -- the training path enqueues its per-level tables there.
+        zeros(n, dtype, device): allocator of the zero-initialised workspaces (default torch.zeros; the training path passes its step
+            arena, whose one fill then covers these too).
+        prepare = (pc1, pc2, feature1, feature2, raw): the API's channel-major tensors of the two frames; xyz and raw (S_*n, 4) are
+            written from them (rtk_prepare_inputs, inside rtk_geometry_front when the geometry is fused).
+        q1 = (w (C, 2) fp32, out (S_*n, C)), with prepare: out = w . (the two raw features of every point), written by the same launch
+            when the geometry is fused (self.q1_done says whether it was)."""
         S_, n, _ = xyz.shape
         if n_valid is not None:
             assert n_valid.shape == (S_,) and n_valid.dtype == torch.int32 and n_valid.is_contiguous() and n <= 2048
-        nv = n_valid.data_ptr() if n_valid is not None else None
-        dev = xyz.device
-        self.n, self.samples, self.npoint = n, S_, npoint
-        self.xyz = [xyz]
-        self.nuniq = []
-        self.events = {}
-        # ---- all workspaces are allocated on the CURRENT stream, before the fork ------------------------------
-        # one int32 workspace for the 3 FPS index rows, the 3 exhausted-cloud counters, the 6 ball-query tables
-        # (zero-initialised once: the caller-zero-inits contract of ball_query, lib/pointnet2_utils.py:246)
-        # and the 3 three-NN index tables
-        ns_all = [ns for row in _PNHeadWeights.NSAMPLES for ns in row]
-        nn_rows = [npoint, npoint, n]
-        sizes = [S_ * npoint] * 3 + [S_] * 7 + [S_ * npoint * ns for ns in ns_all] + [S_ * r * 3 for r in nn_rows]
-        # The two-launch geometry writes every entry a consumer reads (the skipped rows of duplicate centroids are read by nothing:
-        # every consumer takes the duplicate-row counters), so the eval path's workspace is not filled (a 9 MB fill per batch until
-        # round 6); GEOMETRY_POISON (tests) fills it with an out-of-range index instead, which a stray read would turn into a fault.
-        fused_geo = (FUSED_GEOMETRY and n <= 2048 and npoint <= 512 and max(n, npoint) * 12 <= 64 * 1024 and
-                     (not knn_frames or (n >= 16 and S_ == 2 * knn_frames)) and (prepare is None or S_ % 2 == 0))
-        if fused_geo and zeros_given is None and not finite:
-            ws = torch.empty(sum(sizes), dtype=torch.int32, device=dev)
-            if GEOMETRY_POISON is not None:
-                ws.fill_(GEOMETRY_POISON)
-        else:
-            ws = zeros(sum(sizes), torch.int32, dev)
-        parts = list(torch.split(ws, sizes))
-        fps_idx, cnt, tie, tie23, first_tie, ball, nn_idx = parts[0:3], parts[3:6], parts[6], parts[7:9], parts[9], parts[10:16], parts[16:19]
-        # level-1 min-distance state at the first tied round, by point index (written for tied clouds only)
-        snap = torch.empty(S_ * n, dtype=torch.float32, device=dev) if n <= 2048 else None
-        self.fps_idx = [t.view(S_, npoint) for t in fps_idx]
-        self.tie = tie
-        xyz_all = torch.empty(3, S_, npoint, 3, dtype=torch.float32, device=dev)
-        new_xyz = [xyz_all[l] for l in range(3)]
-        d2_all = zeros(sum(nn_rows) * S_ * 3, torch.float32, dev) if finite else torch.empty(sum(nn_rows) * S_ * 3, dtype=torch.float32, device=dev)
-        d2_parts = torch.split(d2_all, [S_ * r * 3 for r in nn_rows])
-        B = knn_frames
-        self.knn = [torch.empty(B, n, 16, dtype=torch.int64, device=dev) for _ in range(2)] if B else None
-        big = n > 2048
-        temp = torch.full((S_, n), 1e10, dtype=torch.float32, device=dev) if big else None
+        self.n, self.samples, self.npoint, self.side = n, S_, npoint, side
+        self.events, self.q1_done = {}, False
+        self.fused_geometry = (FUSED_GEOMETRY and n <= 2048 and npoint <= 512 and max(n, npoint) * 12 <= 64 * 1024 and
+                               (not knn_frames or (n >= 16 and S_ == 2 * knn_frames)) and (prepare is None or S_ % 2 == 0))
+        ws = _geometry_workspace(xyz, npoint, knn_frames, finite, zeros, self.fused_geometry)
+        self._build_views(ws, xyz)
         # every operand a geometry kernel reads or writes through a raw pointer must live as long as this object -- the kernels run
         # asynchronously (on the side stream), and a buffer dropped at the end of __init__ goes back to the allocator's main-stream
         # pool, whose next tenant is then written WHILE the kernel still uses the bytes (round 3: a tie snapshot buffer freed this way
         # put one real frame pair in three off by 2e-3, only with warm allocator pools)
-        self._scratch = (snap, temp, n_valid, xyz)
+        self._scratch = (ws.snap, ws.temp, n_valid, xyz) + tuple(prepare or ())
+        if self.fused_geometry:
+            self._launch_fused(ws, n_valid, knn_frames, prepare, q1 if prepare is not None else None, level_hook, tail_hook)
+        else:
+            self._launch_separate(ws, n_valid, knn_frames, prepare, level_hook, tail_hook)
 
-        self.fused_geometry = fused_geo
-        self.q1_done = False
-        q1w = q1 is not None and prepare is not None
-        if prepare is not None and not fused_geo:      # on the caller's stream, before the fork: the feature kernels read raw there
+    def _build_views(self, ws, xyz):
+        """The public tables: views of the workspace, whichever kernels fill them."""
+        S_, npoint = self.samples, self.npoint
+        self.xyz = [xyz] + [ws.xyz_all[lvl] for lvl in range(3)]      # level 0 = the clouds, 1..3 = the levels' centroids
+        self.nuniq = list(ws.cnt)                                     # exhausted-cloud counters: unique centroids per sample and level
+        self.fps_idx, self.tie = [t.view(S_, npoint) for t in ws.fps_idx], ws.tie
+        self.ball = [[ws.ball[lvl * 2 + s].view(S_, npoint, _PNHeadWeights.NSAMPLES[lvl][s]) for s in range(2)] for lvl in range(3)]
+        self.nn, self.knn = {}, ws.knn
+        for i, (name, u, k) in enumerate(INTERP_LEVELS):      # (squared distances, indices, rows of the known level)
+            rows = self.xyz[u].shape[1]
+            self.nn[name] = (ws.nn_d2[i].view(S_, rows, 3), ws.nn_idx[i].view(S_, rows, 3), self.xyz[k].shape[1])
+
+    def _fork(self):
+        """Context of the geometry launches: the side stream (if any), made to wait for what the current stream holds so far."""
+        if self.side is not None:
+            self.side.wait_stream(torch.cuda.current_stream())
+        return torch.cuda.stream(self.side)
+
+    def _check_relevel(self, ws):
+        if CHECK_FPS_RELEVEL and not torch.cuda.is_current_stream_capturing():      # the check synchronises
+            check_fps_relevel(self.xyz[1], torch.stack(self.fps_idx[1:]), ws.xyz_all[1:], torch.stack(self.nuniq[1:3]))
+
+    def _launch_fused(self, ws, n_valid, B, prepare, q1, level_hook, tail_hook):
+        """The product path: rtk_geometry_front (layout conversion, q1, FPS levels 1-3, kNN) + rtk_geometry_tables."""
+        S_, n, npoint, xyz = self.samples, self.n, self.npoint, self.xyz[0]
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with self._fork():
+            b1 = S_ // 2 if (B or prepare is not None) else S_
+            if prepare is not None:
+                pc1, pc2, f1, f2, raw = prepare
+                fr = (pc1.data_ptr(), pc2.data_ptr(), 1, f1.data_ptr(), f2.data_ptr(), xyz.data_ptr(), raw.data_ptr())
+            else:
+                fr = (xyz.data_ptr(), xyz[b1:].data_ptr() if b1 < S_ else None, 0, None, None, None, None)
+            knn = self.knn or (None, None)
+            qw, qout = q1 or (None, None)
+            _lib.call("rtk_geometry_front", b1, S_, n, npoint, *fr, ws.fps_idx[0].data_ptr(), ws.xyz_all.data_ptr(), ws.cnt[0].data_ptr(),
+                      ws.tie.data_ptr(), ws.first_tie.data_ptr(), ws.snap.data_ptr(), ptr(n_valid), ptr(knn[0]), ptr(knn[1]), ptr(qw), ptr(qout),
+                      qout.shape[1] if q1 else 0, _stream())
+            self.q1_done = q1 is not None
+            self.record("front")        # xyz / raw (prepare), the kNN tables and the three levels of centroids
+            self._check_relevel(ws)
+            radii = (ctypes.c_float * 6)(*[float(r) for row in _PNHeadWeights.RADII for r in row])
+            nsam = (ctypes.c_int * 6)(*[ns for row in _PNHeadWeights.NSAMPLES for ns in row])
+            balls = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in ws.ball])
+            nni = (ctypes.c_void_p * 3)(*[self.nn[name][1].data_ptr() for name, _, _ in INTERP_LEVELS])
+            nnd = (ctypes.c_void_p * 3)(*[self.nn[name][0].data_ptr() for name, _, _ in INTERP_LEVELS])
+            _lib.call("rtk_geometry_tables", S_, n, npoint, xyz.data_ptr(), ws.xyz_all.data_ptr(), ws.cnt[0].data_ptr(), radii, nsam, balls, nni, nnd,
+                      _stream())
+            for lvl in range(3):
+                if level_hook is not None:
+                    level_hook(self, lvl)
+                self.record(lvl)
+            self.record("nn")
+            if B:
+                self.events["knn"] = self.events.get("front")
+            if tail_hook is not None:
+                tail_hook(self)
+
+    def _launch_separate(self, ws, n_valid, B, prepare, level_hook, tail_hook):
+        """The separate entry points (tests; clouds the fused kernels do not take): the same tables in eleven launches, q1 left to the caller."""
+        S_, n, npoint, xyz, nu = self.samples, self.n, self.npoint, self.xyz[0], self.nuniq
+        if prepare is not None:      # on the caller's stream, before the fork: the feature kernels read raw there
             pc1, pc2, f1, f2, raw = prepare
             _lib.call("rtk_prepare_inputs", S_ // 2, n, pc1.data_ptr(), pc2.data_ptr(), f1.data_ptr(), f2.data_ptr(), xyz.data_ptr(), raw.data_ptr(),
                       _stream())
-            self._scratch = self._scratch + (pc1, pc2, f1, f2, raw)
-        main = torch.cuda.current_stream()
-        if side is not None:
-            side.wait_stream(main)
-        ctx = torch.cuda.stream(side) if side is not None else _NullCtx()
-        self.ball = [[ball[lvl * 2 + s].view(S_, npoint, _PNHeadWeights.NSAMPLES[lvl][s]) for s in range(2)] for lvl in range(3)]
-        if fused_geo:
-            with ctx:
-                for lvl in range(3):
-                    self.xyz.append(new_xyz[lvl])
-                    self.nuniq.append(cnt[lvl])
-                b1 = S_ // 2 if (B or prepare is not None) else S_
-                if prepare is not None:
-                    pc1, pc2, f1, f2, raw = prepare
-                    fr = (pc1.data_ptr(), pc2.data_ptr(), 1, f1.data_ptr(), f2.data_ptr(), xyz.data_ptr(), raw.data_ptr())
-                    self._scratch = self._scratch + (pc1, pc2, f1, f2, raw)
-                else:
-                    fr = (xyz.data_ptr(), xyz[b1:].data_ptr() if b1 < S_ else None, 0, None, None, None, None)
-                _lib.call("rtk_geometry_front", b1, S_, n, npoint, *fr, fps_idx[0].data_ptr(), xyz_all.data_ptr(), cnt[0].data_ptr(),
-                          tie.data_ptr(), first_tie.data_ptr(), snap.data_ptr(), nv, self.knn[0].data_ptr() if B else None,
-                          self.knn[1].data_ptr() if B else None, q1[0].data_ptr() if q1w else None, q1[1].data_ptr() if q1w else None,
-                          q1[1].shape[1] if q1w else 0, _stream())
-                self.q1_done = q1w
-                self._record("front", side)        # xyz / raw (prepare), the kNN tables and the three levels of centroids
-                if CHECK_FPS_RELEVEL and not torch.cuda.is_current_stream_capturing():
-                    check_fps_relevel(new_xyz[0], torch.stack(self.fps_idx[1:]), xyz_all[1:], torch.stack(list(cnt[1:3])))
-                radii = (ctypes.c_float * 6)(*[float(r) for row in _PNHeadWeights.RADII for r in row])
-                nsam = (ctypes.c_int * 6)(*ns_all)
-                balls = (ctypes.c_void_p * 6)(*[t.data_ptr() for t in ball])
-                self.nn = {}
-                for i, (name, (u, k)) in enumerate({"fp3": (2, 3), "fp2": (1, 2), "fp1": (0, 1)}.items()):
-                    self.nn[name] = (d2_parts[i].view(S_, nn_rows[i], 3), nn_idx[i].view(S_, nn_rows[i], 3), self.xyz[k].shape[1])
-                nni = (ctypes.c_void_p * 3)(*[self.nn[k][1].data_ptr() for k in ("fp3", "fp2", "fp1")])
-                nnd = (ctypes.c_void_p * 3)(*[self.nn[k][0].data_ptr() for k in ("fp3", "fp2", "fp1")])
-                _lib.call("rtk_geometry_tables", S_, n, npoint, xyz.data_ptr(), xyz_all.data_ptr(), cnt[0].data_ptr(), radii, nsam, balls, nni, nnd,
-                          _stream())
-                for lvl in range(3):
-                    if level_hook is not None:
-                        level_hook(self, lvl)
-                    self._record(lvl, side)
-                self._record("nn", side)
-                if B:
-                    self.events["knn"] = self.events.get("front")
-                if tail_hook is not None:
-                    tail_hook(self)
-            return
-        with ctx:
-            # ---- level 1: the only full furthest-point selection on the common path ---------------------------
-            if not big:
-                _lib.call("rtk_fps_centroids", S_, n, npoint, xyz.data_ptr(), fps_idx[0].data_ptr(), new_xyz[0].data_ptr(),
-                          cnt[0].data_ptr(), tie.data_ptr(), nv, snap.data_ptr(), first_tie.data_ptr(), _stream())
-            else:   # large clouds: generic FPS + gather, no exhausted-cloud / tie information
-                _native.furthest_point_sampling_wrapper(S_, n, npoint, xyz, temp, self.fps_idx[0])
-                new_xyz[0].copy_(torch.gather(xyz, 1, self.fps_idx[0].long().unsqueeze(-1).expand(-1, -1, 3)))
-                cnt[0].fill_(npoint)
-                tie.fill_(npoint)       # unknown: levels 2, 3 run the full selection (no round can settle)
-
-            def relevel():
-                # ---- levels 2, 3: FPS of npoint out of the previous level's npoint centroids (model_utils.py:415-417).
-                # One launch per level, decided per cloud on the device (no host sync): a cloud whose previous level had no tie is
-                # provably the identity on the coordinates and is copied, a tied cloud runs the selection -- resumed at level 1's
-                # first tied round, stopped once its picked set is a prefix again (rtk_fps_relevel)
-                resume = (fps_idx[0].data_ptr(), snap.data_ptr(), n, first_tie.data_ptr()) if not big else (None, None, 0, None)
-                _lib.call("rtk_fps_relevel", S_, npoint, 2, new_xyz[0].data_ptr(), cnt[0].data_ptr(), tie.data_ptr(),
-                          fps_idx[1].data_ptr(), new_xyz[1].data_ptr(), cnt[1].data_ptr(), tie23[0].data_ptr(), *resume, _stream())
-                if CHECK_FPS_RELEVEL and not torch.cuda.is_current_stream_capturing():      # the check synchronises
-                    check_fps_relevel(new_xyz[0], torch.stack(self.fps_idx[1:]), xyz_all[1:], torch.stack(list(cnt[1:3])))
-            for lvl in range(3):
-                self.xyz.append(new_xyz[lvl])
-                self.nuniq.append(cnt[lvl])
-            self.ball = []
-            for lvl in range(3):
-                row = []
-                for s in range(2):
-                    ns, r = _PNHeadWeights.NSAMPLES[lvl][s], _PNHeadWeights.RADII[lvl][s]
-                    bidx = ball[lvl * 2 + s].view(S_, npoint, ns)
-                    row.append(bidx)
-                self.ball.append(row)
+        with self._fork():
+            self._fps_level1(ws, n_valid)
             # order on the side stream = order of first use: level-l tables right after level-l centroids
             for lvl in range(3):
                 (r1, r2), (n1, n2) = _PNHeadWeights.RADII[lvl], _PNHeadWeights.NSAMPLES[lvl]
-                nsrc = self.xyz[lvl].shape[1]
+                src, dst, ball = self.xyz[lvl], self.xyz[lvl + 1], self.ball[lvl]
+                nsrc = src.shape[1]
                 if nsrc * 12 <= 64 * 1024:      # both scales in one scan, duplicate centroids skipped
-                    _lib.call("rtk_ball_query_pair", S_, nsrc, npoint, float(r1), n1, float(r2), n2, self.xyz[lvl + 1].data_ptr(),
-                              self.xyz[lvl].data_ptr(), self.ball[lvl][0].data_ptr(), self.ball[lvl][1].data_ptr(),
-                              self.nuniq[lvl].data_ptr(), _stream())
+                    _lib.call("rtk_ball_query_pair", S_, nsrc, npoint, float(r1), n1, float(r2), n2, dst.data_ptr(), src.data_ptr(),
+                              ball[0].data_ptr(), ball[1].data_ptr(), nu[lvl].data_ptr(), _stream())
                 else:
-                    for s in range(2):
-                        _native.ball_query_wrapper(S_, nsrc, npoint, float(_PNHeadWeights.RADII[lvl][s]), _PNHeadWeights.NSAMPLES[lvl][s],
-                                                   self.xyz[lvl + 1], self.xyz[lvl], self.ball[lvl][s])
+                    _native.ball_query_wrapper(S_, nsrc, npoint, float(r1), n1, dst, src, ball[0])
+                    _native.ball_query_wrapper(S_, nsrc, npoint, float(r2), n2, dst, src, ball[1])
                 if level_hook is not None:
                     level_hook(self, lvl)
-                self._record(lvl, side)
+                self.record(lvl)
                 if lvl == 0:
-                    relevel()
-            self.nn = {}
-            for i, (name, (u, k)) in enumerate({"fp3": (2, 3), "fp2": (1, 2), "fp1": (0, 1)}.items()):
-                nu, m = self.xyz[u].shape[1], self.xyz[k].shape[1]
-                d2 = d2_parts[i].view(S_, nu, 3)
-                idx = nn_idx[i].view(S_, nu, 3)
+                    self._fps_relevel(ws)
+            for name, u, k in INTERP_LEVELS:
+                d2, idx, m = self.nn[name]
                 # unknown rows of fp3 / fp2 are level centroids: duplicates are never read downstream
-                mask = self.nuniq[u - 1].data_ptr() if u > 0 else None
-                _lib.call("rtk_three_nn_masked", S_, nu, m, self.xyz[u].data_ptr(), self.xyz[k].data_ptr(), d2.data_ptr(), idx.data_ptr(),
-                          mask, self.nuniq[k - 1].data_ptr(), _stream())      # known level k: duplicate centroids beyond nuniq
-                self.nn[name] = (d2, idx, m)
-            self._record("nn", side)
+                mask = nu[u - 1].data_ptr() if u > 0 else None
+                _lib.call("rtk_three_nn_masked", S_, d2.shape[1], m, self.xyz[u].data_ptr(), self.xyz[k].data_ptr(), d2.data_ptr(), idx.data_ptr(),
+                          mask, nu[k - 1].data_ptr(), _stream())      # known level k: duplicate centroids beyond nuniq
+            self.record("nn")
             if B:
                 x1, x2 = xyz[:B], xyz[B:]
                 if n_valid is None:
@@ -590,18 +571,41 @@ class Geometry:
                               n_valid[B:].data_ptr(), _stream())
                     _lib.call("rtk_knn_point_masked", B, n, n, 16, x1.data_ptr(), x1.data_ptr(), self.knn[1].data_ptr(),
                               n_valid[:B].data_ptr(), _stream())
-                self._record("knn", side)
+                self.record("knn")
             if tail_hook is not None:
                 tail_hook(self)
 
-    def _record(self, key, side):
-        if side is not None:
+    def _fps_level1(self, ws, n_valid):
+        """Level 1: the only full furthest-point selection on the common path."""
+        S_, n, npoint, xyz = self.samples, self.n, self.npoint, self.xyz[0]
+        if ws.temp is None:
+            _lib.call("rtk_fps_centroids", S_, n, npoint, xyz.data_ptr(), ws.fps_idx[0].data_ptr(), self.xyz[1].data_ptr(), ws.cnt[0].data_ptr(),
+                      ws.tie.data_ptr(), n_valid.data_ptr() if n_valid is not None else None, ws.snap.data_ptr(), ws.first_tie.data_ptr(), _stream())
+        else:   # large clouds: generic FPS + gather, no exhausted-cloud / tie information
+            _native.furthest_point_sampling_wrapper(S_, n, npoint, xyz, ws.temp, self.fps_idx[0])
+            self.xyz[1].copy_(torch.gather(xyz, 1, self.fps_idx[0].long().unsqueeze(-1).expand(-1, -1, 3)))
+            ws.cnt[0].fill_(npoint)
+            ws.tie.fill_(npoint)       # unknown: levels 2, 3 run the full selection (no round can settle)
+
+    def _fps_relevel(self, ws):
+        """Levels 2, 3: FPS of npoint out of the previous level's npoint centroids (model_utils.py:415-417).
+        One launch, decided per cloud and level on the device (no host sync): a cloud whose previous level had no tie is provably the
+        identity on the coordinates and is copied, a tied cloud runs the selection -- resumed at level 1's first tied round, stopped
+        once its picked set is a prefix again (rtk_fps_relevel)."""
+        resume = (ws.fps_idx[0].data_ptr(), ws.snap.data_ptr(), self.n, ws.first_tie.data_ptr()) if ws.snap is not None else (None, None, 0, None)
+        _lib.call("rtk_fps_relevel", self.samples, self.npoint, 2, self.xyz[1].data_ptr(), ws.cnt[0].data_ptr(), ws.tie.data_ptr(),
+                  ws.fps_idx[1].data_ptr(), self.xyz[2].data_ptr(), ws.cnt[1].data_ptr(), ws.tie23.data_ptr(), *resume, _stream())
+        self._check_relevel(ws)
+
+    def record(self, key):
+        """Record geometry stage `key` on the side stream (nothing without one: the kernels are on the caller's stream)."""
+        if self.side is not None:
             ev = torch.cuda.Event()
-            ev.record(side)
+            ev.record(self.side)
             self.events[key] = ev
 
     def wait(self, key):
-        """Make the current stream wait for geometry stage `key` (0,1,2 = levels, 'nn', 'knn')."""
+        """Make the current stream wait for geometry stage `key` ('front', 0,1,2 = levels, 'nn', 'knn', or a hook's own)."""
         ev = self.events.get(key)
         if ev is not None:
             torch.cuda.current_stream().wait_event(ev)
@@ -614,7 +618,7 @@ class Geometry:
         g.ball = [[b[:count] for b in row] for row in self.ball]
         g.nuniq = [c[:count] for c in self.nuniq]
         g.fps_idx, g.tie = [i[:count] for i in self.fps_idx], self.tie[:count]
-        g.events, g.knn = self.events, self.knn
+        g.events, g.knn, g.side = self.events, self.knn, self.side
         g.nn = {k: (d2[:count], idx[:count], m) for k, (d2, idx, m) in self.nn.items()}
         return g
 

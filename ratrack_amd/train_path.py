@@ -23,7 +23,8 @@ import torch.nn.functional as F
 from . import _lib
 from . import pointnet2_utils as PU
 from .abi import stream
-from .train_ops import bn_relu, conv1x1, cost_volume, patch_cost, pw_bn_relu, pw_linear, sa_chain, sa_chain_supported
+from .train_ops import (arena_zeros, bn_relu, conv1x1, cost_volume, group_inverse_index_multi, patch_cost, pw_bn_relu, pw_linear, sa_chain,
+                        sa_chain_supported)
 
 
 FUSED_SA_CHAIN = True      # False: one bn_relu + framework convolution per layer (reference structure, kept for tests)
@@ -72,35 +73,32 @@ class TrainGeometry:
                 row.append((i32(S_, n_src + 1), torch.empty(S_, U * ns, dtype=torch.int16, device=dev))
                            if U * ns <= 65536 and n_src <= 8192 and ns % 4 == 0 else None)
             self.inv.append(row)
-        self.interp = {name: (i32(S_, n if u == 0 else U, 3), f32(S_, n if u == 0 else U, 3))
-                       for name, (u, k) in {"fp3": (2, 3), "fp2": (1, 2), "fp1": (0, 1)}.items()}
+        self.interp = {name: (i32(S_, n if u == 0 else U, 3), f32(S_, n if u == 0 else U, 3)) for name, u, _ in fused.INTERP_LEVELS}
         # inverse tables of the interpolation indices (known point -> the (unknown point, slot) positions that use it): the
         # interpolation's backward is a gather as well
         limit = train_ops.INVERSE_TABLE_MAX_POINTS
         self.interp_inv = {name: (i32(S_, U + 1), torch.empty(S_, 3 * io.shape[1], dtype=torch.int16, device=dev))
                            if 3 * io.shape[1] <= 65536 and io.shape[1] <= limit else None for name, (io, _) in self.interp.items()}
-        st = stream
 
         def level_tables(geo, lvl):
             nu = geo.nuniq
-            _lib.call("rtk_train_row_weights", S_, U, npoint, nu[lvl].data_ptr(), self.row_w[lvl].data_ptr(), st())
+            _lib.call("rtk_train_row_weights", S_, U, npoint, nu[lvl].data_ptr(), self.row_w[lvl].data_ptr(), stream())
             src, dst = geo.xyz[lvl], geo.xyz[lvl + 1]             # (S_, n or npoint, 3), (S_, npoint, 3)
             for s in range(2):
                 # source rows the level tensor does not hold (>= U; level 0 holds all n) are copies of row 0: redirect; neighbour -
                 # centroid offsets (no gradient).  Rows in [nuniq, U) and a padded batch's padding rows exist as copies and are used.
                 _lib.call("rtk_train_group_geometry", S_, src.shape[1], npoint, U, NS[lvl][s], src.data_ptr(), dst.data_ptr(),
                           geo.ball[lvl][s].data_ptr(), U if lvl > 0 else n, nu[lvl].data_ptr(), self.ball[lvl][s].data_ptr(),
-                          self.dxyz[lvl][s].data_ptr(), st())
+                          self.dxyz[lvl][s].data_ptr(), stream())
 
         def tail_tables(geo):
-            from .train_ops import group_inverse_index_multi
             nu = geo.nuniq
             jobs = []
-            for name, (u, k) in {"fp3": (2, 3), "fp2": (1, 2), "fp1": (0, 1)}.items():
+            for name, u, k in fused.INTERP_LEVELS:
                 d2, idx, _ = geo.nn[name]
                 io, wo = self.interp[name]
                 _lib.call("rtk_train_interp_weights", S_, d2.shape[1], io.shape[1], d2.data_ptr(), idx.data_ptr(), nu[k - 1].data_ptr(),
-                          io.data_ptr(), wo.data_ptr(), st())
+                          io.data_ptr(), wo.data_ptr(), stream())
                 if self.interp_inv[name] is not None:              # the redirected indices point at rows < nuniq <= U
                     off, inv = self.interp_inv[name]
                     # fp3 / fp2: the unknown rows are level centroids, the duplicate ones (>= nuniq) are read by nothing downstream
@@ -108,7 +106,7 @@ class TrainGeometry:
                     # fp1 on padded clouds: the padding points are copies of point 0; their positions stay out as well and the
                     # backward folds their gradient into point 0's (three_interpolate(..., n_valid))
                     jobs.append((U, 3 * io.shape[1], io, off, inv, nu[u - 1] if u > 0 else self.n_valid, 3))
-            geo._record("interp", side)
+            geo.record("interp")
             for lvl in range(3):                                   # needed by the backward only
                 for s in range(2):
                     if self.inv[lvl][s] is not None:
@@ -116,9 +114,8 @@ class TrainGeometry:
                         jobs.append((n if lvl == 0 else U, U * NS[lvl][s], self.ball[lvl][s], off, inv))
             if jobs:                                               # all nine inverse tables: one launch
                 group_inverse_index_multi(S_, jobs)
-            geo._record("inv", side)
+            geo.record("inv")
 
-        from .train_ops import arena_zeros
         geo = fused.Geometry(xyz, npoint, side=side, knn_frames=0, finite=True, n_valid=n_valid, level_hook=level_tables, tail_hook=tail_tables,
                              zeros=arena_zeros)
         self.events, self.side = geo.events, side
@@ -127,9 +124,7 @@ class TrainGeometry:
 
     def wait(self, key):
         """Make the current stream wait for stage `key`: 0..2 (level tables), "interp", "inv"."""
-        ev = self.events.get(key)
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
+        self._geo.wait(key)
 
     def join(self):
         if self.side is not None:

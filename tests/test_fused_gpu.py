@@ -840,8 +840,8 @@ def _geometry_tables(geo):
 @pytest.mark.parametrize("case", ["synthetic_b4_n256", "lattice_ties", "n1024", "n2048", "n600", "padded", "odd_n", "tiny", "point_major_one_frame"])
 def test_two_launch_geometry_equals_the_separate_launches(case, monkeypatch):
     """rtk_geometry_front + rtk_geometry_tables (two launches, the product path since round 6) against the eleven launches of the ops' own
-    entry points (rtk_prepare_inputs, rtk_fps_centroids, rtk_fps_relevel x 2, rtk_ball_query_pair x 3, rtk_three_nn_masked x 3,
-    rtk_knn_point_masked x 2): every table bit for bit -- FPS indices / centroids / exhausted-cloud and tie counters of the three levels,
+    entry points (rtk_prepare_inputs, rtk_fps_centroids, rtk_fps_relevel -- one launch for levels 2 and 3 --, rtk_ball_query_pair x 3,
+    rtk_three_nn_masked x 3, rtk_knn_point or rtk_knn_point_masked x 2: 1 + 1 + 1 + 3 + 3 + 2 = 11): every table bit for bit -- FPS indices / centroids / exhausted-cloud and tie counters of the three levels,
     the six ball tables, the three three-NN tables (indices and squared distances), both kNN tables, xyz and raw.  Clouds with exact
     distance ties between distinct points (the tied levels resume and settle inside the one launch), duplicates, padded batches, odd
     sizes; with the layout conversion from the API's channel-major tensors and without (the training path hands over point-major clouds)."""
@@ -905,6 +905,100 @@ def test_two_launch_geometry_equals_the_separate_launches(case, monkeypatch):
             assert torch.equal(two[k], eleven[k]), k
     if case == "lattice_ties":
         assert int(two["tie"].sum()) > 0 and bool((two["xyz2"] != two["xyz1"]).any()), "the lattice must exercise the tied levels"
+
+
+_FRONT_TABLES = ["rtk_geometry_front", "rtk_geometry_tables"]
+_TRAIN_LEVEL = ["rtk_train_row_weights", "rtk_train_group_geometry", "rtk_train_group_geometry"]
+_TRAIN_TAIL = ["rtk_train_interp_weights"] * 3 + ["rtk_group_inverse_index_multi"]
+# configuration -> (launches and hook calls of the two-launch geometry, of the separate entry points), in stream order
+GEOMETRY_SEQUENCES = {
+    "pairs": (_FRONT_TABLES,
+              ["rtk_prepare_inputs", "rtk_fps_centroids", "rtk_ball_query_pair", "rtk_fps_relevel", "rtk_ball_query_pair", "rtk_ball_query_pair",
+               "rtk_three_nn_masked", "rtk_three_nn_masked", "rtk_three_nn_masked", "rtk_knn_point", "rtk_knn_point"]),
+    "padded_pairs": (_FRONT_TABLES,
+                     ["rtk_prepare_inputs", "rtk_fps_centroids", "rtk_ball_query_pair", "rtk_fps_relevel", "rtk_ball_query_pair", "rtk_ball_query_pair",
+                      "rtk_three_nn_masked", "rtk_three_nn_masked", "rtk_three_nn_masked", "rtk_knn_point_masked", "rtk_knn_point_masked"]),
+    "hooks": (_FRONT_TABLES + ["level_hook 0", "level_hook 1", "level_hook 2", "tail_hook"],
+              ["rtk_fps_centroids", "rtk_ball_query_pair", "level_hook 0", "rtk_fps_relevel", "rtk_ball_query_pair", "level_hook 1",
+               "rtk_ball_query_pair", "level_hook 2", "rtk_three_nn_masked", "rtk_three_nn_masked", "rtk_three_nn_masked", "tail_hook"]),
+    "train": (_FRONT_TABLES + 3 * _TRAIN_LEVEL + _TRAIN_TAIL,
+              ["rtk_fps_centroids", "rtk_ball_query_pair"] + _TRAIN_LEVEL + ["rtk_fps_relevel", "rtk_ball_query_pair"] + _TRAIN_LEVEL +
+              ["rtk_ball_query_pair"] + _TRAIN_LEVEL + ["rtk_three_nn_masked"] * 3 + _TRAIN_TAIL),
+}
+# the stages recorded on a side stream (two-launch geometry, separate entry points); without one only the two-launch geometry's alias
+# "knn" -> "front" exists (None)
+GEOMETRY_EVENTS = {
+    "pairs": ({"front", 0, 1, 2, "nn", "knn"}, {0, 1, 2, "nn", "knn"}),
+    "padded_pairs": ({"front", 0, 1, 2, "nn", "knn"}, {0, 1, 2, "nn", "knn"}),
+    "hooks": ({"front", 0, 1, 2, "nn"}, {0, 1, 2, "nn"}),
+    "train": ({"front", 0, 1, 2, "nn", "interp", "inv"}, {0, 1, 2, "nn", "interp", "inv"}),
+}
+# the stages already recorded when each hook runs: level l's hook comes before level l's event, the tail hook after "nn"
+HOOK_EVENTS = ([{"front"}, {"front", 0}, {"front", 0, 1}, {"front", 0, 1, 2, "nn"}], [set(), {0}, {0, 1}, {0, 1, 2, "nn"}])
+
+
+@pytest.mark.parametrize("with_side", [False, True])
+@pytest.mark.parametrize("config", ["pairs", "padded_pairs", "hooks", "train"])
+def test_geometry_launch_sequence_and_events(config, with_side, monkeypatch):
+    """The entry points a Geometry launches, in order, the stages it records on the side stream and the point at which the hooks run, for
+    the two-launch geometry and for the separate entry points (the lists above: the launch order of each path).  pairs: what backbone() passes (B = 2 frame pairs of N = 16 points, the smallest cloud
+    the fused kNN takes; npoint = 512 leaves 496 duplicate centroid rows per level), padded_pairs: the same with n_valid; hooks: the
+    training path's call (one frame, point-major, finite, no kNN) with two recording hooks; train: TrainGeometry, whose hooks launch."""
+    from ratrack_amd import _lib
+    from ratrack_amd.train_path import TrainGeometry
+    g = torch.Generator().manual_seed(5)
+    B, N = 2, 16
+    pc1, pc2 = torch.randn(B, 3, N, generator=g).to(DEV), torch.randn(B, 3, N, generator=g).to(DEV)
+    f1, f2 = torch.randn(B, 2, N, generator=g).to(DEV), torch.randn(B, 2, N, generator=g).to(DEV)
+    q1w = torch.randn(32, 2, generator=g).to(DEV)
+    nv = torch.tensor([[16, 9], [5, 16]], dtype=torch.int32, device=DEV).reshape(-1).contiguous() if config == "padded_pairs" else None
+    if nv is not None:       # padding = copies of the cloud's own point 0
+        for f, pc in enumerate((pc1, pc2)):
+            for b in range(B):
+                pc[b, :, int(nv[f * B + b]):] = pc[b, :, :1]
+    one_frame = pc1.permute(0, 2, 1).contiguous()
+    train_clouds = (torch.randn(6, 200, 3, generator=g) * 6).to(DEV)
+    side = torch.cuda.Stream() if with_side else None
+    seq, hook_events = [], []
+    real_call = _lib.call
+
+    def recording_call(name, *args):
+        seq.append(name)
+        return real_call(name, *args)
+
+    def hook(name):
+        def run(geo, *lvl):
+            assert side is None or torch.cuda.current_stream() == side, "hooks run on the geometry stream"
+            seq.append(" ".join([name] + [str(l) for l in lvl]))
+            hook_events.append(set(geo.events))
+        return run
+    monkeypatch.setattr(_lib, "call", recording_call)
+    for fused_on in (True, False):
+        monkeypatch.setattr(F, "FUSED_GEOMETRY", fused_on)
+        del seq[:], hook_events[:]
+        if config in ("pairs", "padded_pairs"):
+            xyz, raw, q1 = torch.empty(2 * B, N, 3, device=DEV), torch.empty(2 * B * N, 4, device=DEV), torch.empty(2 * B * N, 32, device=DEV)
+            geo = F.Geometry(xyz, 512, side=side, knn_frames=B, n_valid=nv, prepare=(pc1, pc2, f1, f2, raw), q1=(q1w, q1))
+        elif config == "hooks":
+            geo = F.Geometry(one_frame, 512, side=side, finite=True, level_hook=hook("level_hook"), tail_hook=hook("tail_hook"))
+        else:
+            tg = TrainGeometry(train_clouds, 512, side=side)
+            geo = tg._geo
+            assert tg.events is geo.events
+            tg.join()
+        if side is not None:
+            torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        which = 0 if fused_on else 1
+        assert geo.fused_geometry == fused_on
+        assert geo.q1_done == (fused_on and config in ("pairs", "padded_pairs"))
+        assert seq == GEOMETRY_SEQUENCES[config][which]
+        if side is not None:
+            assert set(geo.events) == GEOMETRY_EVENTS[config][which] and all(isinstance(e, torch.cuda.Event) for e in geo.events.values())
+            if config == "hooks":
+                assert hook_events == HOOK_EVENTS[which]
+        else:
+            assert geo.events == ({"knn": None} if fused_on and config in ("pairs", "padded_pairs") else {})
 
 
 @pytest.mark.parametrize("B,N", [(4, 256), (3, 242), (2, 1000), (5, 37)])
