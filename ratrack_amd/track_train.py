@@ -22,7 +22,7 @@ import torch
 
 from . import _lib, tracker as T
 from .abi import TrackFrame, ptr as _ptr, stream as _stream, view as _view
-from .track_score import TrackScorer
+from .track_score import GtObjects, TrackScorer
 from .train import Trainer
 
 DIMS = ((141, 564), (564, 282), (282, 70), (70, 35), (35, 1))
@@ -189,8 +189,8 @@ def check(out):
 class _TrainTracker(T.BatchedTracker):
     """BatchedTracker's state and `associate` behind a train-mode backbone that the trainer runs itself."""
 
-    def __init__(self, net, streams, max_objects):
-        super().__init__(net, streams, max_objects=max_objects, train_mode=True)
+    def __init__(self, net, streams, max_objects, static_state=False):
+        super().__init__(net, streams, max_objects=max_objects, train_mode=True, static_state=static_state)
 
     def step(self, *a, **k):
         raise RuntimeError("SequenceTrainer runs the train-mode backbone itself: use SequenceTrainer.step")
@@ -199,20 +199,29 @@ class _TrainTracker(T.BatchedTracker):
 class SequenceTrainer(Trainer):
     """`Trainer` with the tracking term: B sequences trained in lockstep, total = 0.5 L_sf + L_seg + 0.5 L_trk with L_trk the mean over
     the B streams of `affinity_term` (undefined streams count 0, the batch convention of `loss.backbone_loss`).  Owns the tracker
-    state (`.tracker`) and a `TrackScorer` (`.scorer`).  Eager steps only: the tracker's state is double-buffered by swapping
-    references, which a graph replay cannot do."""
+    state (`.tracker`) and a `TrackScorer` (`.scorer`).
+    graph=True (with `graph_warmup`, `split_graph`, ... of `Trainer`): after the warm-up steps of a key the whole step -- the h reset,
+    the train-mode backbone, the pack of the live Affinity weights, `associate`, `scorer.update`, both losses, the backward, the
+    gradient pack, the h keep of inactive streams and (one process) Adam -- is one hipGraph that every later step replays.  The tracker
+    then keeps its state in place (`BatchedTracker(static_state=True)`); it and the scorer's state are advanced by the replay.  reset
+    and active always live in static device buffers, so they never re-capture; h=None / a tensor, n_valid=None / a tensor, pretrain
+    and the shapes do.  `items`, `h`, `out` and `match` are the graph's static outputs, as with `Trainer(graph=True)`: the next step
+    overwrites them in place (`out` is a new wrapper every step, so its host-side accessors never answer from an earlier step)."""
+
+    N_GOBJ = ("slot", "label_id", "size", "count", "members", "centre", "n_valid")
 
     def __init__(self, model, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, max_pairs=None, **trainer_kw):
-        if trainer_kw.get("graph"):
-            raise ValueError("SequenceTrainer steps eagerly: graph=True is not supported (the tracker swaps its state buffers by reference)")
+        if trainer_kw.get("graph") and next(model.parameters()).device.type != "cuda":
+            raise ValueError("SequenceTrainer: graph=True captures the sequence step in a hipGraph and needs the model on the GPU")
         super().__init__(model, **trainer_kw)
         if self._dev.type != "cuda":
             raise ValueError("SequenceTrainer needs a model on the GPU (the tracker, the scorer and the tracking term are HIP only)")
         model.train()
-        self.tracker = _TrainTracker(model, streams, max_objects)
+        self.tracker = _TrainTracker(model, streams, max_objects, static_state=bool(self.graph))
         self.scorer = TrackScorer(streams=streams, max_objects=max_objects, max_boxes=max_boxes, max_gt_tracks=max_gt_tracks, device=self._dev)
         self.max_pairs = default_max_pairs(int(streams), int(max_objects)) if max_pairs is None else int(max_pairs)
         self.last = None
+        self._default_masks = None
 
     def _forward_backward_impl(self, pc1, pc2, feature1, feature2, gt_warp, gt_cls, gobj, h, n_valid, pretrain, reset, active):
         from . import train_ops
@@ -258,17 +267,54 @@ class SequenceTrainer(Trainer):
             raise ValueError("step(): expected %d streams, got %s" % (self.tracker.B, tuple(pc1.shape)))
         T.check_n_valid(n_valid, N)
         nv = None if n_valid is None else torch.as_tensor(n_valid).to(device=self._dev, dtype=torch.int32).reshape(2, B).contiguous()
-        reset_d, active_d = T._mask(reset, B, False, self._dev), T._mask(active, B, True, self._dev)
-        h_in = h
-        if h is not None and reset is not None:
-            h_in = torch.where((reset_d != 0).view(1, B, 1), 0.0, h)
+        if self.graph and self._default_masks is None:       # built once: the captured step only ever copies from them
+            self._default_masks = (T._mask(None, B, False, self._dev), T._mask(None, B, True, self._dev))
+        dm = self._default_masks
+        reset_d = dm[0] if (dm is not None and reset is None) else T._mask(reset, B, False, self._dev)
+        active_d = dm[1] if (dm is not None and active is None) else T._mask(active, B, True, self._dev)
+        if not self.graph:
+            h_in = h
+            if h is not None and reset is not None:
+                h_in = torch.where((reset_d != 0).view(1, B, 1), 0.0, h)
+            items, h_out, out, match = self._forward_backward(pc1, pc2, feature1, feature2, gt_warp, gt_cls, gobj, h_in, nv, pretrain,
+                                                               reset_d, active_d)
+            if active is not None:
+                h_out = torch.where((active_d != 0).view(1, B, 1), h_out, torch.zeros_like(h_out) if h_in is None else h_in)
+            self.reducer.all_reduce()
+            self._optimize()
+            return items, h_out, out, match
+        self._gobj_meta = (gobj.max_boxes, gobj.points)
+        flat = [pc1, pc2, feature1, feature2, gt_warp, gt_cls, h, nv] + [getattr(gobj, k) for k in self.N_GOBJ] + [reset_d, active_d]
+        return self._run(flat, pretrain)
+
+    # ---- the captured step (Trainer._run: warm-up, key, capture, replay) ----------------------------------------------------------
+    def _body(self, flat, pretrain):
+        """The step up to the all-reduce on the flat list of static tensors; the two masks are always tensors here, so the h reset
+        and the h keep are part of it (with no stream reset / every stream active they change no bit)."""
+        pc1, pc2, feature1, feature2, gt_warp, gt_cls, h, nv = flat[:8]
+        reset_d, active_d = flat[-2:]
+        B = pc1.shape[0]
+        gobj = GtObjects(max_boxes=self._gobj_meta[0], points=self._gobj_meta[1], flags=None, **dict(zip(self.N_GOBJ, flat[8:-2])))
+        h_in = None if h is None else torch.where((reset_d != 0).view(1, B, 1), 0.0, h)
         items, h_out, out, match = self._forward_backward(pc1, pc2, feature1, feature2, gt_warp, gt_cls, gobj, h_in, nv, pretrain, reset_d,
                                                            active_d)
-        if active is not None:
-            h_out = torch.where((active_d != 0).view(1, B, 1), h_out, torch.zeros_like(h_out) if h_in is None else h_in)
-        self.reducer.all_reduce()
-        self._optimize()
+        h_out = torch.where((active_d != 0).view(1, B, 1), h_out, torch.zeros_like(h_out) if h_in is None else h_in)
         return items, h_out, out, match
+
+    def _result(self, res):
+        items, h_out, out, match = res
+        out = T.StepResult(**dict(out.__dict__, _cache=None))
+        self.last = out
+        return items, h_out, out, match
+
+    @staticmethod
+    def _copy_statics(pairs):
+        from .fused import _copy_inputs
+        word = [p for p in pairs if p[0].element_size() == 4]          # one launch per eight 4-byte tensors
+        rest = [p for p in pairs if p[0].element_size() != 4]
+        _copy_inputs(word)
+        if rest:
+            torch._foreach_copy_([p[0] for p in rest], [p[1] for p in rest])
 
     def check(self, out=None):
         """Synchronises.  Raises RuntimeError naming the stream that overflowed max_objects, max_gt_tracks or max_pairs."""

@@ -7,7 +7,9 @@ Per stream, `step()` computes what `Track4D.forward` computes for that stream ru
 the fused engine for the whole batch, then detection and association as four HIP launches for the whole batch
 (csrc/track_batched.hip) -- no host synchronisation between the backbone and the track IDs.  State between steps (h, the previous
 objects' descriptors, IDs and count, the next-ID counter) lives on the device; this frame's descriptors and IDs become the previous
-ones by a buffer swap.
+ones by a buffer swap -- or, with `static_state=True`, by one device copy at the start of the next step, so that the state's
+addresses never change and the whole step can be captured in a hipGraph and replayed (`graph=True`; several independent groups of
+streams in flight at once: `TrackerPipeline`).
 
   * reset (B,) bool: the reference's is_new_seq (main_utils.py:70-74): the stream's h goes to zero and its previous objects are
     dropped; its ID counter keeps counting (the reference's max_id across clips).
@@ -72,7 +74,10 @@ class StepResult:
     """One step's outputs (device tensors): flow (B,3,N), cls (B,N), h (5,B,128), point_track_id (B,N) int32, num_objects (B,),
     object_ids / object_conf (B,K), aff (B,K,K) (only [:m_b, :n_b] meaningful), indices1() (B,K) int32 (-1: no match);
     descriptors / desc_prev (B,K,141): this frame's and the previous objects' descriptors (the tracker's own buffers: the next
-    step but one overwrites them)."""
+    step but one overwrites them; with `static_state=True` the NEXT step does, as it advances the state in place).
+    From a `BatchedTracker(graph=True)` every tensor here is a static output of the captured graph: the next step overwrites all of
+    them in place, so clone what must outlive it.  Each step hands back a new StepResult, so the host-side copy that `objects`,
+    `aff_mat`, `indices1(b)` and `check` keep belongs to that step alone."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -145,9 +150,22 @@ def raise_on_flags(flags, K, only=None):
 class BatchedTracker:
     """Tracks `streams` independent sequences in lockstep (see the module docstring)."""
 
-    def __init__(self, net, streams, max_objects=128, iters=500, alpha=0.9, eps=1.5, threshold=0.5, train_mode=False):
+    def __init__(self, net, streams, max_objects=128, iters=500, alpha=0.9, eps=1.5, threshold=0.5, train_mode=False,
+                 static_state=False, graph=False, graph_warmup=2, engine=None):
         """train_mode: accept a train-mode net -- for a caller that runs the backbone itself and uses `associate` and the state only
-        (track_train.SequenceTrainer); `step()` stays the eval-mode path."""
+        (track_train.SequenceTrainer); `step()` stays the eval-mode path.
+        static_state: this frame's objects are always written to slot 0 of `desc` / `ids` / `count` and the previous objects read
+        from slot 1; `associate` begins by copying slot 0 to slot 1 on the device (one rtk_copy_multi launch) instead of swapping
+        references afterwards, and `h` is updated in place.  Same results bit for bit; nothing is rebound, so a captured graph can
+        replay the step.  `StepResult.h`, `descriptors` and `desc_prev` are then valid until the next step only.
+        graph (implies static_state): the first `graph_warmup` steps of a key -- the shapes and dtypes of pc1, pc2, feature1,
+        feature2 and whether n_valid was given -- run eagerly (real steps: they advance the state); the next one captures the whole
+        step into one hipGraph, and it and every later step copy their inputs into static buffers and replay.  reset / active /
+        n_valid live in static device buffers (None: all streams active, none reset), so they never re-capture.  The outputs are the
+        graph's static tensors: the next step overwrites them in place.  A new key captures again.  The captured graph keeps the
+        weights it was captured with -- the backbone engine's packed images and the packed Affinity image -- as `fused.GraphPipeline`
+        does: build a new tracker after changing weights.
+        engine: the `fused.FusedBackbone` that `step()` runs (default: `net._fused_engine()`, looked up every step)."""
         if net.training and not train_mode:
             raise ValueError("BatchedTracker runs the eval-mode (fused) backbone: call net.eval() first")
         kmax = max_objects_limit()
@@ -162,13 +180,29 @@ class BatchedTracker:
         self.weights = pack_affinity(net.affinity).to(dev)
         B, K = self.B, self.K
         self.h = torch.zeros(5, B, 128, device=dev)
-        self.desc = torch.zeros(2, B, K, DESC, device=dev)          # double-buffered: [cur] written, [1 - cur] = previous objects
+        # double-buffered: [cur] written, [1 - cur] = previous objects (static_state: cur is always 0)
+        self.desc = torch.zeros(2, B, K, DESC, device=dev)
         self.ids = torch.full((2, B, K), -1, dtype=torch.int32, device=dev)
         self.count = torch.zeros(2, B, dtype=torch.int32, device=dev)
         self.counter = torch.zeros(B, dtype=torch.int32, device=dev)
         self.cur = 0
         self._work = None
         self.last = None
+        self.graph = bool(graph)
+        self.static_state = bool(static_state) or self.graph
+        self.engine = engine
+        self._warm = int(graph_warmup)
+        self._key, self._g, self._count, self._static, self._out, self._captured = None, None, 0, None, None, False
+        if self.graph:
+            self._reset_s = torch.zeros(B, dtype=torch.uint8, device=dev)
+            self._active_s = torch.ones(B, dtype=torch.uint8, device=dev)
+            self._nv_s = torch.zeros(2, B, dtype=torch.int32, device=dev)
+            self._reset_default = self._active_default = True       # the static masks hold their defaults: a None needs no copy
+
+    @property
+    def captured(self):
+        """Whether the last step() was the replay of a captured graph."""
+        return self._captured
 
     # ---- one frame --------------------------------------------------------------------------------
     def step(self, pc1, pc2, feature1, feature2, n_valid=None, reset=None, active=None):
@@ -177,33 +211,105 @@ class BatchedTracker:
             raise ValueError("step(): expected (%d,3,N) clouds of one padded size, got %s and %s" % (self.B, tuple(pc1.shape), tuple(pc2.shape)))
         check_n_valid(n_valid, N)
         dev = self.dev
-        reset_d, active_d = _mask(reset, B, False, dev), _mask(active, B, True, dev)
         nv = None if n_valid is None else torch.as_tensor(n_valid).to(device=dev, dtype=torch.int32).reshape(2, B).contiguous()
+        if self.graph:
+            return self._graph_step(pc1, pc2, feature1, feature2, nv, reset, active)
+        reset_d, active_d = _mask(reset, B, False, dev), _mask(active, B, True, dev)
+        return self._body(pc1, pc2, feature1, feature2, nv, reset_d, active_d)
+
+    def _body(self, pc1, pc2, feature1, feature2, nv, reset_d, active_d):
+        """Everything of a step that runs on the device: the h reset, the backbone, the h keep of inactive streams, `associate`."""
+        B = self.B
         keep = (active_d != 0).view(1, B, 1)
         h_in = torch.where((reset_d != 0).view(1, B, 1), 0.0, self.h)
+        eng = self.engine if self.engine is not None else self.net._fused_engine()
         with torch.no_grad():
-            flow, h_out, cls, _, _, _, prop = self.net._fused_engine().backbone(pc1, pc2, feature1, feature2, h_in, n_valid=nv)
-        self.h = torch.where(keep, h_out, self.h)
+            flow, h_out, cls, _, _, _, prop = eng.backbone(pc1, pc2, feature1, feature2, h_in, n_valid=nv)
+        if self.static_state:
+            self.h.copy_(torch.where(keep, h_out, self.h))
+        else:
+            self.h = torch.where(keep, h_out, self.h)
         return self.associate(pc1, feature1, flow, cls, prop, nv, reset_d, active_d)
 
+    def _set_mask(self, static, x, default, is_default):
+        """A step's reset / active into its static buffer; -> whether the buffer now holds the default."""
+        if x is None:
+            if not is_default:
+                static.fill_(int(default))
+            return True
+        static.copy_(_mask(x, self.B, default, self.dev))
+        return False
+
+    def _graph_step(self, pc1, pc2, feature1, feature2, nv, reset, active):
+        from .fused import _copy_inputs
+        args = [pc1, pc2, feature1, feature2]
+        key = tuple((tuple(t.shape), t.dtype) for t in args) + (nv is not None,)
+        if key != self._key:
+            self._key, self._g, self._out, self._static, self._count = key, None, None, None, 0
+        self._reset_default = self._set_mask(self._reset_s, reset, False, self._reset_default)
+        self._active_default = self._set_mask(self._active_s, active, True, self._active_default)
+        nv_s = None if nv is None else self._nv_s
+        if self._g is None and self._count < self._warm:      # eager warm-up: real steps on the caller's tensors
+            self._count += 1
+            self._captured = False
+            if nv is not None:
+                self._nv_s.copy_(nv)
+            out = self._body(pc1, pc2, feature1, feature2, nv_s, self._reset_s, self._active_s)
+            return self._fresh(out)
+        if self._g is None:
+            self._static = [t.contiguous().clone() for t in args]
+            self._workspace(pc1.shape[2])                      # the DBSCAN workspace of a large N: allocated before the capture
+            if self.engine is None:
+                self.net._fused_engine()                       # (folding and packing synchronise: not inside the capture either)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):                          # records the launches, executes nothing
+                self._out = self._body(*self._static, nv_s, self._reset_s, self._active_s)
+            self._g = g
+        pairs = list(zip(self._static, args))
+        if nv is not None:
+            pairs.append((self._nv_s, nv))
+        _copy_inputs(pairs)
+        self._g.replay()
+        self._captured = True
+        return self._fresh(self._out)
+
+    def _fresh(self, out):
+        """A new wrapper around the same tensors: the host-side cache of an earlier step never answers for this one."""
+        out = StepResult(**dict(out.__dict__, _cache=None))
+        self.last = out
+        return out
+
+    def _workspace(self, N):
+        """(address, bytes) of the workspace in which streams whose DBSCAN tables exceed the LDS cluster; (None, 0) for a small N."""
+        need = N * DBSCAN_POINT_BYTES
+        if need <= DBSCAN_LDS_BYTES:
+            return None, 0
+        if self._work is None or self._work.numel() < self.B * need:
+            self._work = torch.empty(self.B * need, dtype=torch.uint8, device=self.dev)
+        return self._work.data_ptr(), self._work.numel()
+
     def associate(self, pc1, feature1, flow, cls, prop, n_valid, reset, active):
-        """The post-backbone half of step(): four launches, the state swap; no host synchronisation.  reset / active (B,) uint8 and
-        n_valid (2,B) int32 (or None) are device tensors."""
+        """The post-backbone half of step(): four launches, the state swap (static_state: the state advance first, five launches);
+        no host synchronisation.  reset / active (B,) uint8 and n_valid (2,B) int32 (or None) are device tensors."""
         B, K = self.B, self.K
         N = pc1.shape[2]
         dev = self.dev
         st = stream()
-        cur, prev = self.cur, 1 - self.cur
+        if self.static_state:
+            # last frame's objects (slot 0) become the previous objects (slot 1).  Here and not at the end of the last step: its
+            # caller may still have read desc_prev (the training backward does).  An inactive stream's kernels carried slot 1 over
+            # into slot 0, so the copy leaves it as it was; a reset stream's previous objects are ignored.
+            from .fused import copy_multi
+            cur, prev = 0, 1
+            copy_multi([(self.desc[1], self.desc[0]), (self.ids[1], self.ids[0]), (self.count[1], self.count[0])])
+        else:
+            cur, prev = self.cur, 1 - self.cur
         i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
         labels, obj, num, flags = i32(B, N), i32(B, N), i32(B), i32(B)
         fr = TrackFrame(B, N, _view(pc1), _view(flow), _view(feature1), _view(prop), _view(cls),
                         None if n_valid is None else n_valid.data_ptr(), active.data_ptr())
-        need = N * DBSCAN_POINT_BYTES
-        work, work_bytes = None, 0
-        if need > DBSCAN_LDS_BYTES:        # a stream whose tables exceed the LDS clusters in its slice of this workspace
-            if self._work is None or self._work.numel() < B * need:
-                self._work = torch.empty(B * need, dtype=torch.uint8, device=dev)
-            work, work_bytes = self._work.data_ptr(), self._work.numel()
+        work, work_bytes = self._workspace(N)      # a stream whose tables exceed the LDS clusters in its slice of this workspace
         _lib.call("rtk_dbscan_batched", ctypes.addressof(fr), self.threshold, self.eps, self.min_samples, K, labels.data_ptr(),
                   obj.data_ptr(), num.data_ptr(), flags.data_ptr(), work, work_bytes, st)
         desc_prev, desc = self.desc[prev], self.desc[cur]
@@ -217,7 +323,8 @@ class BatchedTracker:
                   self.ids[prev].data_ptr(), self.count[prev].data_ptr(), self.alpha, self.iters, self.counter.data_ptr(),
                   self.ids[cur].data_ptr(), self.count[cur].data_ptr(), object_ids.data_ptr(), object_conf.data_ptr(), indices1.data_ptr(),
                   num_prev.data_ptr(), point_track_id.data_ptr(), None, st)
-        self.cur = prev                    # this frame's objects are the next frame's previous objects: a swap, not a copy
+        if not self.static_state:
+            self.cur = prev                # this frame's objects are the next frame's previous objects: a swap, not a copy
         out = StepResult(flow=flow, cls=cls, h=self.h, point_track_id=point_track_id, num_objects=num, object_ids=object_ids,
                          object_conf=object_conf, _indices1=indices1, aff=aff, num_prev=num_prev, flags=flags, labels=labels, obj=obj,
                          descriptors=desc, desc_prev=desc_prev, active=active, pc1=pc1, feature1=feature1, prop=prop, max_objects=K, _cache=None)
@@ -273,3 +380,61 @@ class BatchedTracker:
                     f.write(" ".join(parts) + "\n")
             paths.append(path)
         return paths
+
+
+class TrackerPipeline:
+    """`groups` independent groups of `streams` sequences each, every group a `BatchedTracker(graph=True)` on its own HIP stream:
+
+        pipe = TrackerPipeline(net, groups=2, streams=32)
+        out0 = pipe.submit(0, pc1, pc2, feature1, feature2, n_valid=None, reset=None, active=None)
+        out1 = pipe.submit(1, ...)
+        pipe.drain()
+
+    Three of the four association launches run one workgroup per stream and leave most of the device idle; replays of different
+    groups overlap them (and the backbones' latency-bound phases, as `fused.GraphPipeline` does for the backbone alone).  State is
+    sequential within a group: concurrency comes from different groups only.  Every group has its own copy of the backbone engine
+    (packed weights shared, per-engine state separate); beyond two groups the engines run their geometry kernels on their own
+    stream and the cost volume on a share of the CUs, as in `GraphPipeline`.  The weights are those at construction.
+    `submit` returns group g's `StepResult`, enqueued on group g's stream: its tensors and host accessors (`objects`, `aff_mat`,
+    `indices1(b)`, `check`, `write_results`) are valid after `drain()` or under `pipe.streams[g]`, and until group g's next submit.
+    Inputs are read on group g's stream after everything the current stream held at the time of the submit."""
+
+    MAX_GROUPS = 4
+
+    def __init__(self, net, groups, streams, max_objects=128, **tracker_kw):
+        import copy
+        groups = int(groups)
+        if not 1 <= groups <= self.MAX_GROUPS:
+            raise ValueError("TrackerPipeline: groups=%d outside [1, %d]: one group per hardware queue -- a fifth stream shares one of "
+                             "the four queues, the arrangement that cost 20-30 %% whenever it was measured (DESIGN.md: forked "
+                             "geometry streams beyond depth 2, forked MSG scales 102.6 -> 74-83 k pairs/s)" % (groups, self.MAX_GROUPS))
+        for k in ("graph", "static_state", "engine"):
+            if k in tracker_kw:
+                raise ValueError("TrackerPipeline sets %s itself" % k)
+        base = net._fused_engine()
+        self.engines = []
+        for _ in range(groups):
+            e = copy.copy(base)             # shallow: packed weights are shared, per-engine state is reset
+            e.side, e._last_cv, e.kernel_events, e.kernel_token = None, None, None, None
+            if groups > 2:
+                e.use_side_stream, e.cv_shared = False, True
+            self.engines.append(e)
+        self.trackers = [BatchedTracker(net, streams, max_objects=max_objects, graph=True, engine=e, **tracker_kw) for e in self.engines]
+        self.streams = [torch.cuda.Stream(device=self.trackers[0].dev) for _ in range(groups)]
+        self.groups = groups
+
+    def submit(self, g, pc1, pc2, feature1, feature2, n_valid=None, reset=None, active=None):
+        """Group g's next step on group g's stream -> its StepResult (see the class docstring for when it may be read)."""
+        s = self.streams[g]
+        s.wait_stream(torch.cuda.current_stream())
+        for t in (pc1, pc2, feature1, feature2, n_valid, reset, active):
+            if torch.is_tensor(t) and t.is_cuda:
+                t.record_stream(s)          # the caller may drop its inputs before group g's stream has read them
+        with torch.cuda.stream(s):
+            return self.trackers[g].step(pc1, pc2, feature1, feature2, n_valid=n_valid, reset=reset, active=active)
+
+    def drain(self):
+        """Join every group's stream into the current stream."""
+        cur = torch.cuda.current_stream()
+        for s in self.streams:
+            cur.wait_stream(s)

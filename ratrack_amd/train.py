@@ -63,6 +63,7 @@ class Trainer:
         self._g_opt = None
         self._static = None
         self._key = None
+        self.captured = False      # whether the last step was a graph replay
 
     def _forward_backward(self, *args):
         if self._dev.type != "cuda":
@@ -118,8 +119,28 @@ class Trainer:
         if inv is not None:
             inv()
 
-    def _step(self, *args):
-        out = self._forward_backward(*args)
+    # ---- what a subclass with more inputs supplies (track_train.SequenceTrainer) ------------------------
+    def _body(self, flat, pretrain):
+        """Forward, loss, backward and the gradient pack on the step's flat list of tensors (entries may be None) -- the part of a
+        step that a captured graph replays before the all-reduce.  A subclass rebuilds its structured arguments from `flat`."""
+        return self._forward_backward(*flat, pretrain)
+
+    def _result(self, out):
+        """What step() hands back for `_body`'s return value (the static outputs of a captured step)."""
+        return out
+
+    @staticmethod
+    def _copy_statics(pairs):
+        """[(static, new), ...]: a step's inputs into the captured graph's static buffers."""
+        same = [p for p in pairs if p[0].dtype == p[1].dtype]
+        if same:                               # ONE multi-tensor copy into the static buffers instead of seven device-to-device memcpys
+            torch._foreach_copy_([p[0] for p in same], [p[1] for p in same])
+        for dst, src in pairs:
+            if dst.dtype != src.dtype:
+                dst.copy_(src)
+
+    def _whole(self, flat, pretrain):
+        out = self._body(flat, pretrain)
         self.reducer.all_reduce()
         self._optimize()
         return out
@@ -144,34 +165,34 @@ class Trainer:
         self.model.train()
         if n_valid is not None:
             assert n_valid.is_cuda and n_valid.dtype == torch.int32 and tuple(n_valid.shape) == (2, pc1.shape[0])
-        args = [pc1, pc2, feature1, feature2, gt_warp, gt_cls, h, n_valid]
+        return self._run([pc1, pc2, feature1, feature2, gt_warp, gt_cls, h, n_valid], pretrain)
+
+    def _run(self, args, pretrain):
+        """One step on the flat argument list: eager, or warm-up / capture / replay keyed by the arguments' shapes and dtypes."""
         if not self.graph:
-            return self._step(*args, pretrain)
+            return self._result(self._whole(args, pretrain))
         key = tuple((tuple(t.shape), t.dtype) if t is not None else None for t in args) + (bool(pretrain),)
         if key != self._key:
             self._key, self._g, self._g_opt, self._count = key, None, None, 0
+        self.captured = False
         if self._g is None and self._count < self._warm:      # eager warm-up (MIOpen finds its kernels, the bucket is built)
             self._count += 1
-            return self._step(*args, pretrain)
+            return self._result(self._whole(args, pretrain))
         if self._g is None:
             self._static = [t.clone() if t is not None else None for t in args]
             torch.cuda.synchronize()
             self.opt.zero_grad(set_to_none=True)
             if self.split:
-                self._g, self._out = self._capture(lambda: self._forward_backward(*self._static, pretrain))
+                self._g, self._out = self._capture(lambda: self._body(self._static, pretrain))
                 self._g_opt, _ = self._capture(self._optimize)
             else:
-                self._g, self._out = self._capture(lambda: self._step(*self._static, pretrain))
+                self._g, self._out = self._capture(lambda: self._whole(self._static, pretrain))
         pairs = [(dst, src) for dst, src in zip(self._static, args) if dst is not None]
-        same = [p for p in pairs if p[0].dtype == p[1].dtype]
-        if same:                               # ONE multi-tensor copy into the static buffers instead of seven device-to-device memcpys
-            torch._foreach_copy_([p[0] for p in same], [p[1] for p in same])
-        for dst, src in pairs:
-            if dst.dtype != src.dtype:
-                dst.copy_(src)
+        self._copy_statics(pairs)
         self._g.replay()
         if self._g_opt is not None:
             self.reducer.all_reduce()
             self._g_opt.replay()
         self._invalidate_folded_engine()
-        return self._out
+        self.captured = True
+        return self._result(self._out)

@@ -1,15 +1,16 @@
 """What the tracking term adds to a train step (ratrack_amd/track_train.py) at B = 64, N = 256 with the reference weights.
 
     python tools/time_track_train.py [--streams 64] [--points 256] [--boxes 32] [--max-objects 128] [--iters 100] [--warmup 10]
-                                     [--out profiles/track_train_timing.json]
+                                     [--out profiles/track_train_timing.json] [--graph] [--repeats 1]
 
 One batch of B synthetic frame pairs (synth.make_frame_pairs) with K boxes per frame laid on the clouds' own points, the reference
 state dict with the segmentation head's bias raised by 0.09 so that every frame has moving points (tests/test_tracker_gpu.py), the
 learning rate 0 so that the timed steps all see the same weights.  Measured on the machine it runs on, device time between events,
 median of --iters after --warmup:
 
-  (a) `SequenceTrainer.step` (eager);
-  (b) `Trainer.step` on the same batch (eager, and captured in a hipGraph: what the sequence step cannot be yet);
+  (a) `SequenceTrainer.step` (eager; with --graph also captured in a hipGraph, `SequenceTrainer(graph=True)`, on a second net with
+      the same weights; --repeats R measures each of the two R times in turn and reports every median: the spread);
+  (b) `Trainer.step` on the same batch (eager, and captured in a hipGraph);
   (c) `BatchedTracker.associate` + `TrackScorer.update` on the same batch, and their launches (`_lib.TIMING`);
   (d) the three new entry points alone on that frame's `StepResult` / `MatchResult`, per entry point.
 
@@ -105,6 +106,8 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=os.path.join("profiles", "track_train_timing.json"))
+    ap.add_argument("--graph", action="store_true", help="also time the captured sequence step")
+    ap.add_argument("--repeats", type=int, default=1)
     a = ap.parse_args()
     dev = "cuda"
     B, N, K, KO = a.streams, a.points, a.boxes, a.max_objects
@@ -128,6 +131,21 @@ def main():
     tr.step(pc1, pc2, f1, f2, gt.gt_warp, gt.gt_cls, gobj, h0, reset=torch.ones(B, dtype=torch.bool))
     a_ms, a_launch = timed(seq_step, a.iters, a.warmup, per_launch=True)
     tr.check()
+    a_runs, g_runs, g_loss = [a_ms], [], None
+    if a.graph:
+        trg = TT.SequenceTrainer(reference_net(dev), streams=B, max_objects=KO, max_boxes=K, lr=0.0, graph=True)
+        gstate = {}
+
+        def graph_step():
+            gstate["items"] = trg.step(pc1, pc2, f1, f2, gt.gt_warp, gt.gt_cls, gobj, h0)[0]
+        trg.step(pc1, pc2, f1, f2, gt.gt_warp, gt.gt_cls, gobj, h0, reset=torch.ones(B, dtype=torch.bool))
+        g_runs.append(timed(graph_step, a.iters, a.warmup + 5)[0])
+        assert trg.captured
+        for _ in range(a.repeats - 1):          # alternating: eager, captured, eager, ...
+            a_runs.append(timed(seq_step, a.iters, 2)[0])
+            g_runs.append(timed(graph_step, a.iters, 2)[0])
+        trg.check()
+        g_loss = float(gstate["items"]["TrackingLoss"])
     out, match = state["out"], state["match"]
     pairs = int((out.num_prev.long() * out.num_objects.long() * match.aff_defined.long()).sum())
 
@@ -165,7 +183,9 @@ def main():
            "device": torch.cuda.get_device_name(0),
            "detected_objects": int(out.num_objects.sum()), "live_pairs_in_the_timed_step": pairs, "live_pairs_in_d": d_pairs,
            "tracking_loss": float(state["items"]["TrackingLoss"]),
-           "a_sequence_step_ms": a_ms, "a_new_entry_points_ms_inside_the_step": {k: a_launch.get(k) for k in NEW},
+           "a_sequence_step_ms": a_ms, "a_sequence_step_ms_runs": a_runs,
+           "a_sequence_step_graph_ms": statistics.median(g_runs) if g_runs else None, "a_sequence_step_graph_ms_runs": g_runs,
+           "tracking_loss_of_the_captured_step": g_loss, "a_new_entry_points_ms_inside_the_step": {k: a_launch.get(k) for k in NEW},
            "a_tracker_scorer_launches_ms_inside_the_step": {k: a_launch.get(k) for k in ASSOC},
            "b_trainer_step_eager_ms": b_ms["eager"], "b_trainer_step_graph_ms": b_ms["graph"],
            "c_associate_plus_update_ms": c_ms, "c_launch_ms": {k: c_launch.get(k) for k in ASSOC},
