@@ -925,6 +925,14 @@ class FusedBackbone:
                   self.flow_glob_b.data_ptr(), sbf.data_ptr(), sbf.shape[1], _stream())
         return y, h_out, sbf
 
+    def clone(self):
+        """A shallow copy: the packed weights are shared, the per-engine state (side stream, last cost-volume operands, event
+        recording) starts empty."""
+        import copy
+        e = copy.copy(self)
+        e.side, e._last_cv, e.kernel_events, e.kernel_token = None, None, None, None
+        return e
+
     def time_dominant_kernel(self, iters=20):
         """(start, stop) HIP-event pairs around `iters` launches of the cost-volume kernel on the current
         stream, on the operands of the last backbone() call."""
@@ -1059,20 +1067,15 @@ class GraphPipeline:
     ... p.drain().  Outputs of a submit stay valid until the same slot is reused, `depth` submits later."""
 
     def __init__(self, model_or_engine, example_inputs, depth=2, split_cost_volume=False):
-        import copy
         eng = model_or_engine if isinstance(model_or_engine, FusedBackbone) else FusedBackbone(model_or_engine)
         if depth > 2:
-            eng = copy.copy(eng)
-            eng.use_side_stream, eng.side = False, None
+            eng = eng.clone()
+            eng.use_side_stream = False
             # ... and the cost volume leaves a quarter of every XCD to the other batches: it keeps the CUs it runs on whole, and with
             # one workgroup per CU nothing else runs for a third of the step (B = 64: 74.1 -> 76.0 k pairs/s at 192 of 256 workgroups,
             # the kernel itself 0.33 -> 0.39 ms; 232: 73.2 k, 208: 74.4 k, 176: 74.9 k, 160: 75.7 k, 128: 75.5 k)
             eng.cv_shared = True
-        self.engines = [eng]
-        for _ in range(depth - 1):
-            e = copy.copy(eng)          # shallow: packed weights are shared, per-engine state is reset below
-            e.side, e._last_cv, e.kernel_events = None, None, None
-            self.engines.append(e)
+        self.engines = [eng] + [eng.clone() for _ in range(depth - 1)]
         self.depth = depth
         self._token = [None]
         for e in self.engines:

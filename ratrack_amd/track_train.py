@@ -265,8 +265,7 @@ class SequenceTrainer(Trainer):
         B, N = pc1.shape[0], pc1.shape[2]
         if B != self.tracker.B:
             raise ValueError("step(): expected %d streams, got %s" % (self.tracker.B, tuple(pc1.shape)))
-        T.check_n_valid(n_valid, N)
-        nv = None if n_valid is None else torch.as_tensor(n_valid).to(device=self._dev, dtype=torch.int32).reshape(2, B).contiguous()
+        nv = T.device_n_valid(n_valid, B, N, self._dev)
         if self.graph and self._default_masks is None:       # built once: the captured step only ever copies from them
             self._default_masks = (T._mask(None, B, False, self._dev), T._mask(None, B, True, self._dev))
         dm = self._default_masks
@@ -275,11 +274,11 @@ class SequenceTrainer(Trainer):
         if not self.graph:
             h_in = h
             if h is not None and reset is not None:
-                h_in = torch.where((reset_d != 0).view(1, B, 1), 0.0, h)
+                h_in = T.reset_h(h, reset_d)
             items, h_out, out, match = self._forward_backward(pc1, pc2, feature1, feature2, gt_warp, gt_cls, gobj, h_in, nv, pretrain,
                                                                reset_d, active_d)
             if active is not None:
-                h_out = torch.where((active_d != 0).view(1, B, 1), h_out, torch.zeros_like(h_out) if h_in is None else h_in)
+                h_out = T.keep_h(active_d, h_out, torch.zeros_like(h_out) if h_in is None else h_in)
             self.reducer.all_reduce()
             self._optimize()
             return items, h_out, out, match
@@ -293,18 +292,16 @@ class SequenceTrainer(Trainer):
         and the h keep are part of it (with no stream reset / every stream active they change no bit)."""
         pc1, pc2, feature1, feature2, gt_warp, gt_cls, h, nv = flat[:8]
         reset_d, active_d = flat[-2:]
-        B = pc1.shape[0]
         gobj = GtObjects(max_boxes=self._gobj_meta[0], points=self._gobj_meta[1], flags=None, **dict(zip(self.N_GOBJ, flat[8:-2])))
-        h_in = None if h is None else torch.where((reset_d != 0).view(1, B, 1), 0.0, h)
+        h_in = None if h is None else T.reset_h(h, reset_d)
         items, h_out, out, match = self._forward_backward(pc1, pc2, feature1, feature2, gt_warp, gt_cls, gobj, h_in, nv, pretrain, reset_d,
                                                            active_d)
-        h_out = torch.where((active_d != 0).view(1, B, 1), h_out, torch.zeros_like(h_out) if h_in is None else h_in)
+        h_out = T.keep_h(active_d, h_out, torch.zeros_like(h_out) if h_in is None else h_in)
         return items, h_out, out, match
 
     def _result(self, res):
         items, h_out, out, match = res
-        out = T.StepResult(**dict(out.__dict__, _cache=None))
-        self.last = out
+        self.last = out = out.fresh()
         return items, h_out, out, match
 
     @staticmethod

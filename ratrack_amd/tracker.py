@@ -26,6 +26,7 @@ import os
 import torch
 
 from . import _lib
+from .captured import CapturedStep, capture_graph, signature
 from .abi import TrackFrame, View as _View, stream, view as _view  # noqa: F401  (_View: tests and tools take it from here)
 
 DESC = 141
@@ -70,6 +71,22 @@ def check_n_valid(n_valid, N):
             raise ValueError("n_valid %s outside [0, N=%d]" % (nv.tolist(), N))
 
 
+def device_n_valid(n_valid, B, N, dev):
+    """`check_n_valid`, then n_valid as a contiguous (2,B) int32 tensor on `dev` (None stays None)."""
+    check_n_valid(n_valid, N)
+    return None if n_valid is None else torch.as_tensor(n_valid).to(device=dev, dtype=torch.int32).reshape(2, B).contiguous()
+
+
+def reset_h(h, reset):
+    """h (5,B,128) with the state of the streams that `reset` (B,) marks zeroed."""
+    return torch.where((reset != 0).view(1, -1, 1), 0.0, h)
+
+
+def keep_h(active, h_new, h_old):
+    """The new h of the streams that `active` (B,) marks, the old h of those that sit the frame out."""
+    return torch.where((active != 0).view(1, -1, 1), h_new, h_old)
+
+
 class StepResult:
     """One step's outputs (device tensors): flow (B,3,N), cls (B,N), h (5,B,128), point_track_id (B,N) int32, num_objects (B,),
     object_ids / object_conf (B,K), aff (B,K,K) (only [:m_b, :n_b] meaningful), indices1() (B,K) int32 (-1: no match);
@@ -81,6 +98,10 @@ class StepResult:
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
+
+    def fresh(self):
+        """A new wrapper around the same tensors: the host-side cache of an earlier step never answers for this one."""
+        return StepResult(**dict(self.__dict__, _cache=None))
 
     def indices1(self, b=None):
         """b None: the (B,K) int32 device tensor.  b: the reference's indices1 of stream b, (1,n_b) int64, or None when there was
@@ -191,27 +212,25 @@ class BatchedTracker:
         self.graph = bool(graph)
         self.static_state = bool(static_state) or self.graph
         self.engine = engine
-        self._warm = int(graph_warmup)
-        self._key, self._g, self._count, self._static, self._out, self._captured = None, None, 0, None, None, False
         if self.graph:
+            from .fused import _copy_inputs
+            self._graphed = CapturedStep(graph_warmup, _copy_inputs)     # the inputs and n_valid: ONE rtk_copy_multi launch
             self._reset_s = torch.zeros(B, dtype=torch.uint8, device=dev)
             self._active_s = torch.ones(B, dtype=torch.uint8, device=dev)
-            self._nv_s = torch.zeros(2, B, dtype=torch.int32, device=dev)
             self._reset_default = self._active_default = True       # the static masks hold their defaults: a None needs no copy
 
     @property
     def captured(self):
         """Whether the last step() was the replay of a captured graph."""
-        return self._captured
+        return self.graph and self._graphed.captured
 
     # ---- one frame --------------------------------------------------------------------------------
     def step(self, pc1, pc2, feature1, feature2, n_valid=None, reset=None, active=None):
         B, _, N = pc1.shape
         if B != self.B or pc2.shape[2] != N:
             raise ValueError("step(): expected (%d,3,N) clouds of one padded size, got %s and %s" % (self.B, tuple(pc1.shape), tuple(pc2.shape)))
-        check_n_valid(n_valid, N)
         dev = self.dev
-        nv = None if n_valid is None else torch.as_tensor(n_valid).to(device=dev, dtype=torch.int32).reshape(2, B).contiguous()
+        nv = device_n_valid(n_valid, B, N, dev)
         if self.graph:
             return self._graph_step(pc1, pc2, feature1, feature2, nv, reset, active)
         reset_d, active_d = _mask(reset, B, False, dev), _mask(active, B, True, dev)
@@ -219,16 +238,14 @@ class BatchedTracker:
 
     def _body(self, pc1, pc2, feature1, feature2, nv, reset_d, active_d):
         """Everything of a step that runs on the device: the h reset, the backbone, the h keep of inactive streams, `associate`."""
-        B = self.B
-        keep = (active_d != 0).view(1, B, 1)
-        h_in = torch.where((reset_d != 0).view(1, B, 1), 0.0, self.h)
+        h_in = reset_h(self.h, reset_d)
         eng = self.engine if self.engine is not None else self.net._fused_engine()
         with torch.no_grad():
             flow, h_out, cls, _, _, _, prop = eng.backbone(pc1, pc2, feature1, feature2, h_in, n_valid=nv)
         if self.static_state:
-            self.h.copy_(torch.where(keep, h_out, self.h))
+            self.h.copy_(keep_h(active_d, h_out, self.h))
         else:
-            self.h = torch.where(keep, h_out, self.h)
+            self.h = keep_h(active_d, h_out, self.h)
         return self.associate(pc1, feature1, flow, cls, prop, nv, reset_d, active_d)
 
     def _set_mask(self, static, x, default, is_default):
@@ -241,44 +258,21 @@ class BatchedTracker:
         return False
 
     def _graph_step(self, pc1, pc2, feature1, feature2, nv, reset, active):
-        from .fused import _copy_inputs
-        args = [pc1, pc2, feature1, feature2]
-        key = tuple((tuple(t.shape), t.dtype) for t in args) + (nv is not None,)
-        if key != self._key:
-            self._key, self._g, self._out, self._static, self._count = key, None, None, None, 0
+        """Warm-up / capture / replay (captured.CapturedStep) keyed by the shapes and dtypes of the inputs and of nv (or its absence)."""
+        args = [pc1, pc2, feature1, feature2, nv]
         self._reset_default = self._set_mask(self._reset_s, reset, False, self._reset_default)
         self._active_default = self._set_mask(self._active_s, active, True, self._active_default)
-        nv_s = None if nv is None else self._nv_s
-        if self._g is None and self._count < self._warm:      # eager warm-up: real steps on the caller's tensors
-            self._count += 1
-            self._captured = False
-            if nv is not None:
-                self._nv_s.copy_(nv)
-            out = self._body(pc1, pc2, feature1, feature2, nv_s, self._reset_s, self._active_s)
-            return self._fresh(out)
-        if self._g is None:
-            self._static = [t.contiguous().clone() for t in args]
-            self._workspace(pc1.shape[2])                      # the DBSCAN workspace of a large N: allocated before the capture
-            if self.engine is None:
-                self.net._fused_engine()                       # (folding and packing synchronise: not inside the capture either)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):                          # records the launches, executes nothing
-                self._out = self._body(*self._static, nv_s, self._reset_s, self._active_s)
-            self._g = g
-        pairs = list(zip(self._static, args))
-        if nv is not None:
-            pairs.append((self._nv_s, nv))
-        _copy_inputs(pairs)
-        self._g.replay()
-        self._captured = True
-        return self._fresh(self._out)
-
-    def _fresh(self, out):
-        """A new wrapper around the same tensors: the host-side cache of an earlier step never answers for this one."""
-        out = StepResult(**dict(out.__dict__, _cache=None))
-        self.last = out
+        out = self._graphed(signature(args), args, lambda a: self._body(*a, self._reset_s, self._active_s), self._capture_step)
+        self.last = out = out.fresh()
         return out
+
+    def _capture_step(self, static):
+        self._workspace(static[0].shape[2])                # the DBSCAN workspace of a large N: allocated before the capture
+        if self.engine is None:
+            self.net._fused_engine()                       # (folding and packing synchronise: not inside the capture either)
+        torch.cuda.synchronize()
+        g, out = capture_graph(lambda: self._body(*static, self._reset_s, self._active_s))      # records the launches, executes nothing
+        return out, g.replay
 
     def _workspace(self, N):
         """(address, bytes) of the workspace in which streams whose DBSCAN tables exceed the LDS cluster; (None, 0) for a small N."""
@@ -402,7 +396,6 @@ class TrackerPipeline:
     MAX_GROUPS = 4
 
     def __init__(self, net, groups, streams, max_objects=128, **tracker_kw):
-        import copy
         groups = int(groups)
         if not 1 <= groups <= self.MAX_GROUPS:
             raise ValueError("TrackerPipeline: groups=%d outside [1, %d]: one group per hardware queue -- a fifth stream shares one of "
@@ -414,8 +407,7 @@ class TrackerPipeline:
         base = net._fused_engine()
         self.engines = []
         for _ in range(groups):
-            e = copy.copy(base)             # shallow: packed weights are shared, per-engine state is reset
-            e.side, e._last_cv, e.kernel_events, e.kernel_token = None, None, None, None
+            e = base.clone()                # packed weights shared, per-engine state its own
             if groups > 2:
                 e.use_side_stream, e.cv_shared = False, True
             self.engines.append(e)

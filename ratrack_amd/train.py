@@ -5,6 +5,7 @@ loss, backward, gradient all-reduce across ranks, optimizer step -- optionally t
 import torch
 
 from . import loss as L
+from .captured import CapturedStep, capture_graph, signature
 from .ddp import FlatGradAllReducer
 
 
@@ -58,11 +59,8 @@ class Trainer:
         self.graph = graph
         # split_graph: None = automatic (split when there is a collective that is not to be captured)
         self.split = (self.reducer.world > 1 and not graph_collective) if split_graph is None else bool(split_graph)
-        self._warm = graph_warmup
-        self._g = None
-        self._g_opt = None
-        self._static = None
-        self._key = None
+        self._graphed = CapturedStep(graph_warmup, self._copy_statics)       # warm-up / capture / replay of the graphed step
+        self._g_opt = None         # the optimizer's own graph when the captured step is split
         self.captured = False      # whether the last step was a graph replay
 
     def _forward_backward(self, *args):
@@ -145,17 +143,6 @@ class Trainer:
         self._optimize()
         return out
 
-    @staticmethod
-    def _capture(fn):
-        g = torch.cuda.CUDAGraph()
-        import torch.distributed as dist
-        # with a process group alive, its watchdog thread polls events while we capture: only this thread's calls may
-        # invalidate the capture
-        mode = "thread_local" if dist.is_available() and dist.is_initialized() else "global"
-        with torch.cuda.graph(g, capture_error_mode=mode):
-            out = fn()
-        return g, out
-
     def step(self, pc1, pc2, feature1, feature2, gt_warp, gt_cls, h=None, pretrain=False, n_valid=None):
         """One optimisation step on this rank's shard.  Returns the loss items (python floats are NOT taken here:
         no device->host sync inside the step).
@@ -168,31 +155,33 @@ class Trainer:
         return self._run([pc1, pc2, feature1, feature2, gt_warp, gt_cls, h, n_valid], pretrain)
 
     def _run(self, args, pretrain):
-        """One step on the flat argument list: eager, or warm-up / capture / replay keyed by the arguments' shapes and dtypes."""
+        """One step on the flat argument list: eager, or warm-up / capture / replay (captured.CapturedStep) keyed by the arguments'
+        shapes and dtypes and by pretrain."""
+        self.captured = False
         if not self.graph:
             return self._result(self._whole(args, pretrain))
-        key = tuple((tuple(t.shape), t.dtype) if t is not None else None for t in args) + (bool(pretrain),)
-        if key != self._key:
-            self._key, self._g, self._g_opt, self._count = key, None, None, 0
-        self.captured = False
-        if self._g is None and self._count < self._warm:      # eager warm-up (MIOpen finds its kernels, the bucket is built)
-            self._count += 1
-            return self._result(self._whole(args, pretrain))
-        if self._g is None:
-            self._static = [t.clone() if t is not None else None for t in args]
-            torch.cuda.synchronize()
-            self.opt.zero_grad(set_to_none=True)
-            if self.split:
-                self._g, self._out = self._capture(lambda: self._body(self._static, pretrain))
-                self._g_opt, _ = self._capture(self._optimize)
-            else:
-                self._g, self._out = self._capture(lambda: self._whole(self._static, pretrain))
-        pairs = [(dst, src) for dst, src in zip(self._static, args) if dst is not None]
-        self._copy_statics(pairs)
-        self._g.replay()
-        if self._g_opt is not None:
-            self.reducer.all_reduce()
-            self._g_opt.replay()
-        self._invalidate_folded_engine()
-        self.captured = True
-        return self._result(self._out)
+        # (the warm-up steps are eager: MIOpen finds its kernels, the bucket is built)
+        out = self._graphed(signature(args) + (bool(pretrain),), args, lambda a: self._whole(a, pretrain),
+                            lambda static: self._capture_step(static, pretrain))
+        self.captured = self._graphed.captured
+        return self._result(out)
+
+    def _capture_step(self, static, pretrain):
+        """-> (the static outputs, replay): ONE graph of the whole step, or (split) the body and the optimizer as two graphs with the
+        all-reduce issued eagerly between their replays."""
+        torch.cuda.synchronize()
+        self.opt.zero_grad(set_to_none=True)
+        if self.split:
+            g, out = capture_graph(lambda: self._body(static, pretrain))
+            g_opt, _ = capture_graph(self._optimize)
+        else:
+            (g, out), g_opt = capture_graph(lambda: self._whole(static, pretrain)), None
+        self._g_opt = g_opt
+
+        def replay():
+            g.replay()
+            if g_opt is not None:
+                self.reducer.all_reduce()
+                g_opt.replay()
+            self._invalidate_folded_engine()
+        return out, replay

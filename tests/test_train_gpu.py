@@ -377,6 +377,42 @@ def test_graphed_trainer_matches_eager():
     np.testing.assert_allclose(ld[:3], lc[:3], rtol=1e-3)          # the eager warm-up steps
 
 
+def test_an_eager_step_between_replays_keeps_the_captured_graph():
+    """What bench.py --mode train does to count the step's kernels: `tr.graph = False` for one step of a trainer that has captured,
+    then back.  The eager step reports captured = False, the graph survives it (`ready` never drops, so nothing is captured twice)
+    and the steps after it replay; all six losses equal the eager trainer's (lr = 0; rtol as above: float atomics)."""
+    from ratrack_amd.train import Trainer
+    B, N = 2, 256
+    batches = []
+    for i in range(6):
+        d = synth.make_frame_pairs(B, N, 20 + i)
+        batches.append({k: torch.from_numpy(v).to(DEV) for k, v in d.items()})
+    h = torch.zeros(5, B, 128, device=DEV)
+
+    def make(**kw):
+        net = Track4D(Args()).to(DEV)
+        net.load_state_dict(reference_state_dict(DEV), strict=True)
+        return Trainer(net, lr=0.0, **kw)
+
+    def one(tr, t):
+        items, _ = tr.step(t["pc1"], t["pc2"], t["feature1"], t["feature2"], t["gt_warp"], t["gt_cls"], h)
+        return float(items["Loss"])
+
+    eager = make()
+    want = [one(eager, t) for t in batches]
+    tr = make(graph=True, graph_warmup=1)
+    got, captured, ready = [], [], []
+    for i, t in enumerate(batches):
+        tr.graph = i != 3                     # step 4 runs eagerly
+        got.append(one(tr, t))
+        captured.append(tr.captured)
+        ready.append(tr._graphed.ready)
+    assert captured == [False, True, True, False, True, True], captured
+    assert ready == [False, True, True, True, True, True], ready
+    assert tr._graphed.warmups == 1
+    np.testing.assert_allclose(got, want, rtol=1e-5)
+
+
 def test_data_parallel_step_structure_on_one_gpu():
     """The world > 1 step structure, exercised on ONE GPU through a 1-rank RCCL process group: gradients packed into the flat
     bucket, a real RCCL all-reduce, Adam on gradients aliasing the bucket --
@@ -473,13 +509,13 @@ def test_captured_collective_survives_twenty_replays():
         got = []
         for i in range(24):                                              # 3 eager warm-ups, the capture (+ its replay), 20 more replays
             got.append(one(tr, batches[i % 5]))
-            if tr._g is not None:
+            if tr._graphed.ready:
                 assert tr._g_opt is None
                 R = tr.reducer
                 guard = R._buf[R.flat.numel():].cpu()
                 assert torch.equal(guard, R._guard_host * dist.get_world_size()), (i, guard.tolist(), R._guard_host.tolist())
                 assert float(guard[4]) == float(len(R._live)) and len(R._live) > 100
-        assert tr._g is not None and tr._count >= 3
+        assert tr._graphed.ready and tr._graphed.warmups >= 3
         np.testing.assert_allclose(got, want, rtol=1e-5)
         assert tr.reducer.payload_bytes == 4 * 1058196
     finally:

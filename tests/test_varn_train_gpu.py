@@ -184,7 +184,7 @@ def test_padded_pair_equals_unpadded_and_one_graph_serves_all_sizes():
         keys = [str(k) for k in sub["loss_keys"]]
         got = [float(items[k]) for k in keys]
         np.testing.assert_allclose(got, sub["loss_vals"], rtol=2e-4, atol=1e-6, err_msg="step %d (pair %d)" % (step, ci))
-    assert tr._g is not None, "the step was never captured"
+    assert tr._graphed.ready, "the step was never captured"
 
 
 @pytest.mark.parametrize("B", [2, 8])
