@@ -86,6 +86,16 @@ RTK_EXPORT int rtk_pointwise_mlp_tap(int rows, int rows_per_sample, const rtk_in
                                      int out_pitch, float *colmax, const rtk_layer_t *proj, int frame_split, float *proj_out,
                                      int proj_pitch, rtk_stream_t stream);
 
+/* Two chains that read the same rows, in one launch: chain A (one split layer, 25 -> 2 blocks of 16 channels) on the whole input
+ * vector srcs[0] || srcs[1] ... (25 slots) with its optional sample_bias, written point-major to out_a (rows, out_a_pitch); chain B
+ * (four split layers, 16 -> 8 -> 4 -> 2 -> 1 blocks) on the last source alone (256 channels), written channel-major to out_b
+ * (samples, out_b_channels, rows_per_sample).  The images lie in one blob, chain A's first: layers_b[0].w_packed follows layer_a's
+ * image, and so on.  Every row is live.  Both outputs are bit for bit what rtk_pointwise_mlp gives for each chain on its own (the
+ * decoder front: the sa1 projections of [raw | f1 | cor] and the class head on cor). */
+RTK_EXPORT int rtk_pointwise_mlp_pair(int rows, int rows_per_sample, int nsrc, const rtk_src_t *srcs, const float *sample_bias,
+                                      const rtk_layer_t *layer_a, float *out_a, int out_a_pitch, int out_a_channels, int nlayers_b,
+                                      const rtk_layer_t *layers_b, float *out_b, int out_b_channels, rtk_stream_t stream);
+
 /* One scale of a set-abstraction level.  q (samples*n, q_pitch): per-point layer-1 projection of the
  * features (BN scale folded); layer 1 = relu(q[idx] + Wx.(xyz[idx] - centroid) + b1) with
  * w1xyz_packed the [1][c1_16][64][4] image of [Wx | b1]; then nlayers more packed layers; the last

@@ -157,6 +157,7 @@ SIGNATURES = {
     # ---- include/rtk_fused.h
     "rtk_pointwise_mlp": [_i, _i, P(Interp), _i, P(Src), _p, _i, P(Layer), _p, _i, _i, _i, _p, _p, _p],
     "rtk_pointwise_mlp_tap": [_i, _i, P(Interp), P(Layer), _p, _i, _p, P(Layer), _i, _p, _i, _p],
+    "rtk_pointwise_mlp_pair": [_i, _i, _i, P(Src), _p, P(Layer), _p, _i, _i, _i, P(Layer), _p, _i, _p],
     "rtk_sa_scale": [_i] * 4 + [_p] * 4 + [_i, _i, _p, _i, P(Layer), _p, _i, _i, _p, _p, _p],
     "rtk_cost_volume": [_i] * 3 + [_p] * 6 + [P(Layer), P(Layer), _p, _i, _p],
     "rtk_patch_cost": [_i] * 2 + [_p] * 3 + [_i, P(Layer), _p, _i, _i, _p],

@@ -341,9 +341,10 @@ extern "C" int rtk_pointwise_mlp(int rows, int rows_per_sample, const rtk_interp
         PW_CASE(1, 2, 0, 0, 0)     // raw (RCS, v_r) -> sa1 layer-1 projections (2 scales x 16)
         PW_CASE(4, 6, 0, 0, 0)     // sa1 out 64 -> linear1 (32) || sa2 projections (32+32)
         PW_CASE(6, 12, 0, 0, 0)    // sa2 out 96 -> linear2 (64) || sa3 projections (64+64)
-        PW_CASE(8, 4, 0, 0, 0)     // sa3 out 128 -> linear3 (64)
-        PW_CASE(8, 8, 0, 0, 0)     // fp3 (interp 64 || skip 64), fp1 (interp 128) -> 128
+        PW_CASE(8, 4, 0, 0, 0)     // sa3 out 128 -> linear3 (64): a launch of its own only on the comparison path (fused.FOLD_LIN3 off)
+        PW_CASE(8, 8, 0, 0, 0)     // fp1 (interp 128) -> 128; fp3 (interp 64 || skip 64) on linear3's output (comparison path)
         PW_CASE(10, 8, 0, 0, 0)    // fp2 (interp 128 || skip 32) -> 128
+        PW_CASE(12, 8, 0, 0, 0)    // fp3 with linear3 composed in (interp of sa3's 128 || skip 64) -> 128
         PW_CASE(8, 16, 0, 0, 0)    // local features 128 -> cost-volume layer-1 projection 256
         PW_CASE(16, 8, 4, 2, 1)    // cls head 256 -> 128 -> 64 -> 32 -> 1
         PW_CASE(8, 8, 4, 2, 1)     // flow head (prop 128 + per-sample GRU term) -> 128 -> 64 -> 32 -> 3
@@ -530,5 +531,151 @@ extern "C" int rtk_pointwise_mlp_tap(int rows, int rows_per_sample, const rtk_in
     const dim3 blocks = P.gx ? dim3(gx * samples) : dim3(gx, samples);
     pointwise_tap_kernel<8, 8, 16><<<blocks, 64 * PW_NW, 0, (hipStream_t)stream>>>(T);
     RTK_CHECK_LAUNCH("pointwise_mlp_tap");
+    return RTK_OK;
+}
+
+// ---- rtk_pointwise_mlp_pair --------------------------------------------------------------------------------------------
+// Two chains that read the same wide rows in one launch (the decoder front: the sa1 projection of [raw | f1 | cor] and the class
+// head on cor): the tile's 25 input slots are loaded once, chain A (25 -> 2 blocks, one layer) runs on all of them and is stored,
+// then chain B (16 -> 8 -> 4 -> 2 -> 1) runs on the last 16 slots of the same registers.  Each chain does pw_layer's split
+// arithmetic with its own position scale (chain B's from its 16 slots only), images, inverse scales and bias: both outputs are
+// rtk_pointwise_mlp's bit for bit.  One weight stream over one blob: chain A's fragments first, then chain B's.
+struct PairParams {
+    PwParams pw;                  // the sources, chain A (layer[0], sample_bias, out: row-major), the grid
+    rtk_layer_t lb[4];            // chain B
+    float *out_b;                 // (samples, out_b_channels, rows_per_sample) channel-major
+    int out_b_channels;
+};
+
+template <int U, int VA, int UB, int V1, int V2, int V3, int V4>
+__global__ __launch_bounds__(64 * PW_NW, 2) void pointwise_pair_kernel(const PairParams T) {
+    __shared__ __attribute__((aligned(16))) f4 s_w[2 * PW_F * 64];
+    const PwParams &P = T.pw;
+    const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
+    const int wave_in_wg = threadIdx.x >> 6;
+    int b, bx, nbx;
+    rtk_decode_block(P.gx, b, bx, nbx);
+    const int rps = P.rows_per_sample;
+    const int groups = (rps + PW_NW * 16 - 1) / (PW_NW * 16);
+    if (bx >= groups) return;
+    constexpr int FA = split16_nf(U, VA), F1 = split16_nf(UB, V1), F2 = split16_nf(V1, V2), F3 = split16_nf(V2, V3), F4 = split16_nf(V3, V4);
+    WStream<PW_NW, PW_F, FA + F1 + F2 + F3 + F4> ws;
+    ws.start_deferred(reinterpret_cast<const f4 *>(P.layer[0].w_packed), s_w, wave_in_wg, lane);
+
+    int ustart[RTK_MAX_SRC + 1];
+    ustart[0] = 0;
+#pragma unroll
+    for (int s = 0; s < RTK_MAX_SRC; ++s) ustart[s + 1] = ustart[s] + (s < P.nsrc ? (P.src[s].channels + 15) >> 4 : 0);
+    const int uend = ustart[RTK_MAX_SRC];
+
+    for (int G = bx; G < groups; G += nbx) {
+        asm volatile("" ::: "memory");
+        const int r = G * (PW_NW * 16) + wave_in_wg * 16 + j;
+        const bool valid = r < rps;
+        const int p = b * rps + (valid ? r : rps - 1);
+        // ---- the input slots, as pointwise_mlp_kernel loads them ---------------------------------------
+        f4 h[U];
+        const float *rowp[RTK_MAX_SRC];
+        const float *dummy = reinterpret_cast<const float *>(P.layer[0].w_packed);
+#pragma unroll
+        for (int q = 0; q < RTK_MAX_SRC; ++q)
+            rowp[q] = q < P.nsrc ? P.src[q].ptr + (P.src[q].per_sample ? (size_t)b : (size_t)p) * P.src[q].pitch + 4 * g : nullptr;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float *rp = rowp[0];
+            int us = ustart[0], ch = P.src[0].channels;
+#pragma unroll
+            for (int q = 1; q < RTK_MAX_SRC; ++q)
+                if (q < P.nsrc && u >= ustart[q]) { rp = rowp[q]; us = ustart[q]; ch = P.src[q].channels; }
+            const int c = 16 * (u - us);
+            const bool ok = u < uend && c + 4 * g < ch;
+            const f4 v = *reinterpret_cast<const f4 *>(ok ? rp + c : dummy);
+            h[u] = ok ? v : f4_zero();
+        }
+        // ---- chain A on every slot; its accumulators are stored before chain B starts --------------------
+        {
+            f4 a[VA];
+            pw_layer<true, U, VA, 0>(ws, h, a, P.layer[0], g, P.sample_bias ? P.sample_bias + (size_t)b * 16 * VA : nullptr, true);
+            store_tile<VA>(P, a, p, b, g, valid);
+        }
+        // ---- chain B on the last UB slots ------------------------------------------------------------------
+        f4 hb[UB];
+#pragma unroll
+        for (int u = 0; u < UB; ++u) hb[u] = h[U - UB + u];
+        f4 a1[V1], a2[V2], a3[V3], a4[V4];
+        pw_layer<true, UB, V1, FA>(ws, hb, a1, T.lb[0], g, nullptr, false);
+        pw_layer<true, V1, V2, FA + F1>(ws, a1, a2, T.lb[1], g, nullptr, false);
+        pw_layer<true, V2, V3, FA + F1 + F2>(ws, a2, a3, T.lb[2], g, nullptr, false);
+        pw_layer<true, V3, V4, FA + F1 + F2 + F3>(ws, a3, a4, T.lb[3], g, nullptr, false);
+        if (valid) {
+            float *o = T.out_b + (size_t)b * T.out_b_channels * rps + (p - b * rps);
+#pragma unroll
+            for (int v = 0; v < V4; ++v) {
+                const int c = 16 * v + 4 * g;
+                if (c + 0 < T.out_b_channels) o[(size_t)(c + 0) * rps] = a4[v].x;
+                if (c + 1 < T.out_b_channels) o[(size_t)(c + 1) * rps] = a4[v].y;
+                if (c + 2 < T.out_b_channels) o[(size_t)(c + 2) * rps] = a4[v].z;
+                if (c + 3 < T.out_b_channels) o[(size_t)(c + 3) * rps] = a4[v].w;
+            }
+        }
+    }
+    ws.finish();
+}
+
+extern "C" int rtk_pointwise_mlp_pair(int rows, int rows_per_sample, int nsrc, const rtk_src_t *srcs, const float *sample_bias,
+                                      const rtk_layer_t *layer_a, float *out_a, int out_a_pitch, int out_a_channels, int nlayers_b,
+                                      const rtk_layer_t *layers_b, float *out_b, int out_b_channels, rtk_stream_t stream) {
+    RTK_REQUIRE(rows > 0 && rows_per_sample > 0 && rows % rows_per_sample == 0 && rows / rows_per_sample <= 65535,
+                "pointwise_mlp_pair: bad row counts (%d, %d)", rows, rows_per_sample);
+    RTK_REQUIRE(nsrc >= 1 && nsrc <= RTK_MAX_SRC && srcs && layer_a && layers_b && out_a && out_b, "pointwise_mlp_pair: nsrc=%d", nsrc);
+    PairParams T;
+    memset(&T, 0, sizeof(T));
+    PwParams &P = T.pw;
+    P.rows = rows;
+    P.rows_per_sample = rows_per_sample;
+    P.nsrc = nsrc;
+    int U = 0;
+    for (int s = 0; s < nsrc; ++s) {
+        RTK_REQUIRE(srcs[s].ptr && srcs[s].pitch % 4 == 0 && srcs[s].channels > 0 && srcs[s].pitch >= ((srcs[s].channels + 3) / 4) * 4,
+                    "pointwise_mlp_pair: bad source %d (pitch %d, channels %d)", s, srcs[s].pitch, srcs[s].channels);
+        P.src[s] = srcs[s];
+        U += (srcs[s].channels + 15) / 16;
+    }
+    // the one instance: [.. | 256 channels] -> 32 next to 256 -> 128 -> 64 -> 32 -> 16 on the last source, split images in one blob
+    const int UB = (srcs[nsrc - 1].channels + 15) / 16;
+    RTK_REQUIRE(U == 25 && UB == 16 && nlayers_b == 4, "pointwise_mlp_pair: no kernel instance for U=%d UB=%d, %d layers", U, UB, nlayers_b);
+    RTK_REQUIRE(layer_a->w_packed && layer_a->bias && (layer_a->act & RTK_LAYER_SPLIT) && layer_a->cin16 == 25 && layer_a->cout16 == 2,
+                "pointwise_mlp_pair: chain A must be one split 25 -> 2 block layer");
+    static const int vb[5] = {16, 8, 4, 2, 1};
+    const float *w = layer_a->w_packed + (size_t)split16_nf(25, 2) * 256;
+    for (int l = 0; l < 4; ++l) {
+        RTK_REQUIRE(layers_b[l].bias && (layers_b[l].act & RTK_LAYER_SPLIT) && layers_b[l].cin16 == vb[l] && layers_b[l].cout16 == vb[l + 1],
+                    "pointwise_mlp_pair: chain B layer %d must be a split %d -> %d block layer", l, vb[l], vb[l + 1]);
+        RTK_REQUIRE(layers_b[l].w_packed == w, "pointwise_mlp_pair: the images must be contiguous, chain A's first (chain B layer %d)", l);
+        w += (size_t)split16_nf(vb[l], vb[l + 1]) * 256;
+        T.lb[l] = layers_b[l];
+        T.lb[l].act = layers_b[l].act & 0xff;
+    }
+    P.layer[0] = *layer_a;
+    P.layer[0].act = layer_a->act & 0xff;
+    P.sample_bias = sample_bias;
+    P.out = out_a;
+    P.out_pitch = out_a_pitch;
+    P.out_channels = out_a_channels;
+    RTK_REQUIRE(out_a_channels > 0 && out_a_channels <= 32 && out_a_pitch % 4 == 0 && out_a_pitch >= out_a_channels,
+                "pointwise_mlp_pair: bad output A (%d channels, pitch %d)", out_a_channels, out_a_pitch);
+    RTK_REQUIRE(out_b_channels > 0 && out_b_channels <= 16, "pointwise_mlp_pair: out_b_channels=%d", out_b_channels);
+    T.out_b = out_b;
+    T.out_b_channels = out_b_channels;
+    // the grid of launch_pw
+    const int samples = rows / rows_per_sample;
+    const int groups = (rows_per_sample + PW_NW * 16 - 1) / (PW_NW * 16);
+    int gx = PW_WGS_TARGET / samples;
+    if (gx < 1) gx = 1;
+    if (gx > groups) gx = groups;
+    P.gx = samples % 8 == 0 ? gx : 0;
+    const dim3 blocks = P.gx ? dim3(gx * samples) : dim3(gx, samples);
+    pointwise_pair_kernel<25, 2, 16, 8, 4, 2, 1><<<blocks, 64 * PW_NW, 0, (hipStream_t)stream>>>(T);
+    RTK_CHECK_LAUNCH("pointwise_mlp_pair");
     return RTK_OK;
 }

@@ -198,6 +198,24 @@ class Chain:
             self._split = (arr, blob)
         return self._split[0]
 
+    def split_pair(self, other):
+        """(this chain's split layers, other's) with the images in ONE blob, this chain's first (rtk_pointwise_mlp_pair streams both);
+        biases and inverse scales are those of split_arr().  Built on first use, per partner."""
+        got = self._pairs.get(id(other))
+        if got is None:
+            mine, theirs = self.split_arr(), other.split_arr()
+            blob = torch.cat([self._split[1], other._split[1]]).contiguous()
+            arrs, off = [], 0
+            for src in (mine, theirs):
+                arr = (_Layer * len(src))()
+                for i, l in enumerate(src):
+                    arr[i].w_packed, arr[i].bias = blob.data_ptr() + 2 * off, l.bias
+                    arr[i].cin16, arr[i].cout16, arr[i].act, arr[i].inv_scale = l.cin16, l.cout16, l.act, l.inv_scale
+                    off += ((l.cin16 + 1) // 2) * l.cout16 * 2 * 512
+                arrs.append(arr)
+            got = self._pairs[id(other)] = (arrs[0], arrs[1], blob, other)      # (other: keeps the id, and its biases, alive)
+        return got[0], got[1]
+
     def __init__(self, layers, device):
         """layers: list of (W (Cout,Cin) float64/32 tensor, bias (Cout,), act)."""
         packs, biases, meta = [], [], []
@@ -210,6 +228,7 @@ class Chain:
         self.blob = torch.cat(packs).contiguous()
         self.bias = torch.cat(biases).contiguous()
         self._layers, self._device, self._split = [(w, act) for w, _, act in layers], device, None
+        self._pairs = {}
         arr = (_Layer * len(layers))()
         woff = boff = 0
         for i, (u, v, act) in enumerate(meta):
@@ -281,6 +300,25 @@ def pointwise_tap(rows, rows_per_sample, chain, out, colmax, interp, proj, frame
     _lib.call("rtk_pointwise_mlp_tap", rows, rows_per_sample, ip, chain.split_arr(), optr, opitch, colmax.data_ptr(), pa, frame_split,
               pptr, ppitch, _stream())
     return out, proj_out
+
+
+def pointwise_pair(rows, rows_per_sample, srcs, chain_a, out_a, sample_bias, chain_b, out_b, out_b_channels):
+    """rtk_pointwise_mlp_pair: pointwise(rows, rows_per_sample, srcs, chain_a, out_a, sample_bias=sample_bias) and
+    pointwise(rows, rows_per_sample, srcs[-1:], chain_b, out_b, out_channels=out_b_channels, channel_major=True) in one launch that
+    loads the rows once; chain_a: one layer on 25 input slots -> 32, chain_b: four layers on the last source's 256 channels."""
+    assert PW_SPLIT and chain_a.n == 1 and chain_b.n == 4
+    arr = (_Src * len(srcs))()
+    for i, (t, ch, per) in enumerate(srcs):
+        ptr, pitch = _colptr(t)
+        arr[i].ptr, arr[i].pitch, arr[i].channels, arr[i].per_sample = ptr, pitch, ch, int(per)
+    if _TRACE is not None:
+        _TRACE.append(("pointwise", rows, sum(co * ci for co, ci in chain_b.dims)))
+        _TRACE.append(("pointwise", rows, sum(co * ci for co, ci in chain_a.dims)))
+    la, lb = chain_a.split_pair(chain_b)
+    optr, opitch = _colptr(out_a)
+    _lib.call("rtk_pointwise_mlp_pair", rows, rows_per_sample, len(srcs), arr, sample_bias.data_ptr() if sample_bias is not None else None,
+              la, optr, opitch, chain_a.cout, chain_b.n, lb, out_b.data_ptr(), out_b_channels, _stream())
+    return out_a, out_b
 
 
 def offset_image(w4, device):
@@ -365,8 +403,15 @@ class _PNHeadWeights:
         for name in ("fp3", "fp2", "fp1"):
             w, b = fold_bn(sd[prefix + name + ".mlp.layer0.conv.weight"], prefix + name + ".mlp.layer0.bn.bn", sd)
             self.fp[name] = Chain([(w, b, ACT_RELU)], device)
+            if name == "fp3":
+                # linear3 composed into fp3: three-NN interpolation is linear and its weights sum to one, so
+                # W_i interp(W3 x + b3) = (W_i W3) interp(x) + W_i b3 -- fp3 interpolates sa3's 128 channels itself (FOLD_LIN3)
+                wl, bl = d("linear3.weight"), d("linear3.bias")
+                self.fp3c = Chain([(torch.cat([w[:, :64] @ wl, w[:, 64:]], 1), b + w[:, :64] @ bl, ACT_RELU)], device)
 
 
+FOLD_LIN3 = True               # run_pnhead: fp3 on the composed image (_PNHeadWeights.fp3c), no linear3 launch; False: linear3, then fp3 on its
+                               # output (the tests' comparison)
 FUSED_GEOMETRY = True          # the geometry of a batch in two launches (rtk_geometry_front / rtk_geometry_tables); False (tests): the eleven
                                # launches of the separate entry points they replace -- the same tables bit for bit
 GEOMETRY_POISON = None         # tests: an IN-RANGE index to fill the eval geometry's (otherwise uninitialised) index workspace with: no output bit may depend on it
@@ -688,11 +733,13 @@ def run_pnhead(W, geo, q1, out=None, gmax=None, tap=None):
     geo.wait(2)
     sa_scale(geo, W, 2, 0, t2, 64, sa3, 0)
     sa_scale(geo, W, 2, 1, t2, 128, sa3, 64)
-    l3 = pointwise(S_ * S, S, [(sa3, 128, False)], W.lin3, new(S_ * S, 64), row_nuniq=nu[2])
+    if not FOLD_LIN3:
+        l3 = pointwise(S_ * S, S, [(sa3, 128, False)], W.lin3, new(S_ * S, 64), row_nuniq=nu[2])
     geo.wait("nn")
     d2, idx, m = geo.nn["fp3"]
-    f3 = pointwise(S_ * S, S, [(t2[:, 0:64], 64, False)], W.fp["fp3"], new(S_ * S, 128), row_nuniq=nu[1],
-                   interp=(l3, 64, m, idx.reshape(-1, 3), d2.reshape(-1, 3), nu[2]))
+    known, known_ch, chain = (sa3, 128, W.fp3c) if FOLD_LIN3 else (l3, 64, W.fp["fp3"])
+    f3 = pointwise(S_ * S, S, [(t2[:, 0:64], 64, False)], chain, new(S_ * S, 128), row_nuniq=nu[1],
+                   interp=(known, known_ch, m, idx.reshape(-1, 3), d2.reshape(-1, 3), nu[2]))
     d2, idx, m = geo.nn["fp2"]
     f2 = pointwise(S_ * S, S, [(t1[:, 0:32], 32, False)], W.fp["fp2"], new(S_ * S, 128), row_nuniq=nu[0],
                    interp=(f3, 128, m, idx.reshape(-1, 3), d2.reshape(-1, 3), nu[1]))
@@ -729,6 +776,8 @@ class FusedBackbone:
         self.cv_shared = False                          # the cost volume on a share of the CUs (GraphPipeline sets it from depth 3)
         self.proj_tap = True                            # split path: the encoder's last layer also writes the cost volume's projections
                                                         # (False: the standalone launch sequence, the tests' comparison)
+        self.pair_readers = True                        # split path: the two readers of cor (class head, decoder sa1 projections) in one
+                                                        # launch (False: the two standalone launches, the tests' comparison)
         self._last_cv = None
         self.enc = _PNHeadWeights(sd, "pn_head.", dev)
         self.dec = _PNHeadWeights(sd, "fd_layer.mse.", dev)
@@ -868,9 +917,12 @@ class FusedBackbone:
                   _stream())
         # ---- decoder -------------------------------------------------------------------------------------
         cls = torch.empty(B, N, dtype=torch.float32, device=dev)
-        pointwise(B * N, N, [(cor, 256, False)], self.cls_head, cls, out_channels=1, channel_major=True)
-        q1d = pointwise(B * N, N, [(raw[:B * N], 2, False), (f1, 128, False), (cor, 256, False)], self.dec_q1, new(B * N, 32),
-                        sample_bias=sbq)
+        dsrc = [(raw[:B * N], 2, False), (f1, 128, False), (cor, 256, False)]
+        if self.pair_readers and PW_SPLIT:
+            q1d, _ = pointwise_pair(B * N, N, dsrc, self.dec_q1, new(B * N, 32), sbq, self.cls_head, cls, 1)
+        else:
+            pointwise(B * N, N, [(cor, 256, False)], self.cls_head, cls, out_channels=1, channel_major=True)
+            q1d = pointwise(B * N, N, dsrc, self.dec_q1, new(B * N, 32), sample_bias=sbq)
         prop, gfeat = run_pnhead(self.dec, geo.head(B), q1d, gmax=gmax[2 * B:])           # (B*N,128), (B,128)
         if h is None:
             h = torch.zeros(5, B, 128, device=dev, dtype=torch.float32)

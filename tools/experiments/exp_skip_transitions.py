@@ -19,6 +19,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--one":
     with torch.no_grad():
         net.backbone(*batches[0])
         eng = net._fused
+        fused.FOLD_LIN3, eng.pair_readers = False, False      # the standalone launches: what the skipped chains below are launches of
         skip = set()
         if mode in ("transitions", "both"):
             for W in (eng.enc, eng.dec):
