@@ -34,7 +34,9 @@ extern "C" {
 typedef struct {
     const float *ptr;  /* (rows, pitch) point-major, or (samples, pitch) when per_sample != 0 */
     int pitch;         /* floats per row, multiple of 4, buffer readable up to ceil4(channels) */
-    int channels;      /* valid channels; the segment occupies ceil16(channels) input slots */
+    int channels;      /* valid channels; the segment occupies ceil16(channels) input slots.  Columns channels .. ceil4(channels) are
+                        * loaded with the last valid ones and enter the arithmetic (on the split path the position's scale too): they
+                        * must hold ZERO, which is what rtk_prepare_inputs supplies for the raw (RCS, v_r, 0, 0) rows */
     int per_sample;    /* 1: row index = sample (broadcast over the sample's points) */
 } rtk_src_t;
 
@@ -67,7 +69,9 @@ typedef struct {
  * when out_channel_major != 0; only out_channels channels are written.
  * row_nuniq (optional, (samples)): rows r >= row_nuniq[b] of sample b are duplicates of the sample's row 0
  * (centroids picked after furthest-point sampling exhausted the cloud, see rtk_fps_centroids); they are
- * neither read nor written -- consumers alias them to row 0.
+ * never written and never influence a result -- consumers alias them to row 0.  The kernel does load the source rows and the
+ * interp.idx / interp.dist2 rows of such rows up to the end of the last live group of 64 rows (masked at the store): those buffers
+ * must be readable for all `rows` rows, and the index rows must hold IN-RANGE indices (the three-NN kernels write whole groups).
  * colmax (optional, (samples, 16*last.cout16), ZERO-INITIALISED by the caller): per-sample maximum over the rows of
  * every output channel (torch.max(features, -1), models/track4d.py:89-92), accumulated with atomic max on the float
  * bits -- only valid when the last activation is non-negative (ReLU / sigmoid). */

@@ -5,8 +5,10 @@ own images, inverse scales, bias and position scale (chain B's from the 16 slots
 
 Shapes, the smallest at which the tile logic can go wrong:
   B = 3,   N = 80    2-D grid; the second row group has one live wave and three wholly invalid ones
+  B = 3,   N = 77    ... holds 13 live rows: one partial tile and two wholly invalid waves
   B = 8,   N = 243   XCD-aware 1-D grid; partial last tile
   B = 136, N = 128   one workgroup per sample: every workgroup loops over two groups and the weight stream wraps
+  B = 264, N = 130   ... over three groups, the last with 2 live rows
   B = 1,   N = 1024  one sample, 16 groups"""
 import pytest
 import torch
@@ -15,7 +17,7 @@ from ratrack_amd import fused as F
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-SHAPES = [(3, 80), (8, 243), (136, 128), (1, 1024)]
+SHAPES = [(3, 80), (3, 77), (8, 243), (136, 128), (264, 130), (1, 1024)]
 
 
 def _chains(seed, plain_b=False):

@@ -9,7 +9,7 @@ from ratrack_amd import _lib
 from ratrack_amd import fused as F
 from ratrack_amd import pointnet2_utils as PU
 
-from _stage_f64 import cost_volume_f64, patch_cost_f64, sa_scale_f64
+from _stage_f64 import _gather, cost_volume_f64, patch_cost_f64, sa_scale_f64, weight_net
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -258,13 +258,15 @@ def _cv_operands(B, N, seed):
     return x1, x2, p1, p2, knn
 
 
-def _cv_launch(eng, variant, B, N, x1, x2, knn, p1, p2):
+def _cv_launch(eng, variant, B, N, x1, x2, knn, p1, p2, crafted=None):
+    """crafted: (split images, inverse scales, fp32 biases (2, 256), packed chain) of _cv_crafted in place of the engine's."""
+    images, scales, bias23, chain = crafted if crafted is not None else (eng.cv_images, eng.cv_scales, eng.cv_bias23, eng.cv_layers)
     out = torch.full((B * N + 4, PITCH), SENT, device=DEV)
     a = (B, N, N, x1.data_ptr(), x2.data_ptr(), knn.data_ptr(), p1.data_ptr(), p2.data_ptr(), eng.cv_wd.data_ptr())
-    split = (eng.cv_images.data_ptr(), eng.cv_scales.data_ptr(), eng.cv_bias23[0].data_ptr(), eng.cv_bias23[1].data_ptr(), eng.wn1.arr,
+    split = (images.data_ptr(), scales.data_ptr(), bias23[0].data_ptr(), bias23[1].data_ptr(), eng.wn1.arr,
              out.data_ptr(), PITCH)
     if variant == "plain":
-        _lib.call("rtk_cost_volume", *a, eng.cv_layers.arr, eng.wn1.arr, out.data_ptr(), PITCH, F._stream())
+        _lib.call("rtk_cost_volume", *a, chain.arr, eng.wn1.arr, out.data_ptr(), PITCH, F._stream())
     elif variant == "split":
         _lib.call("rtk_cost_volume_split", *a, *split, F._stream())
     else:
@@ -273,8 +275,9 @@ def _cv_launch(eng, variant, B, N, x1, x2, knn, p1, p2):
     return out
 
 
-def _cv_reference(eng, dtype, B, N, x1, x2, knn, p1, p2):
-    wd, layers, wn1, _ = _cv_weights(eng)
+def _cv_reference(eng, dtype, B, N, x1, x2, knn, p1, p2, layers=None):
+    wd, own, wn1, _ = _cv_weights(eng)
+    layers = own if layers is None else layers
     c = lambda t: t.to(dtype)
     return cost_volume_f64(c(x1), c(x2), knn, c(p1).view(B, N, 256), c(p2).view(B, N, 256), c(wd), [(c(w), c(b)) for w, b in layers],
                            [(c(w), c(b)) for w, b in wn1]).reshape(B * N, 256)
@@ -325,6 +328,106 @@ def test_patch_cost_matches_float64(eng, B, N):
     _check("patch cost point-major B %d N %d" % (B, N), out[:B * N, :256], r64, r32)
     got_cm = cm[:B * 256 * N].view(B, 256, N).permute(0, 2, 1).reshape(B * N, 256)
     _check("patch cost channel-major B %d N %d" % (B, N), got_cm, r64, r32)
+
+
+# ---- cost volume: crafted inner layers ---------------------------------------------------------------------------------------------
+CV_CRAFTED_SHAPES = [(3, 243), (16, 64)]
+
+
+def _cv_crafted(layers):
+    """[(W2, b2), (W3, b3)] float64 -> what the launches take: the two split images and inverse scales back to back
+    (rtk_pack_split_layer, as FusedBackbone.__init__ builds them), the fp32 biases, and the packed chain of rtk_cost_volume."""
+    images = torch.empty(2 * F.SPLIT_IMAGE_256, dtype=torch.int16, device=DEV)
+    scales = torch.empty(2, dtype=torch.float32, device=DEV)
+    ws = [w.float().contiguous() for w, _ in layers]
+    for l, w in enumerate(ws):
+        _lib.call("rtk_pack_split_layer", 256, 256, w.data_ptr(), 0, images[l * F.SPLIT_IMAGE_256:].data_ptr(), scales[l:].data_ptr(),
+                  F._stream())
+    torch.cuda.synchronize()
+    bias = torch.stack([b.float() for _, b in layers]).contiguous()
+    return images, scales, bias, F.Chain([(w, b, F.ACT_LEAKY) for w, b in layers], DEV)
+
+
+def _cv_random_layers(seed, bias=0.1):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    rn = lambda *s: torch.randn(*s, generator=g, device=DEV).double()
+    return [[rn(256, 256) / 16, rn(256) * bias] for _ in range(2)]
+
+
+def _cv_inner(eng, x1, x2, knn, p1, p2, layers, B, N):
+    """float64: (the input of the last crafted layer (B, N, 16, 256), its output feat, the WeightNet's weights (B, N, 16, 256))."""
+    lk = lambda t: torch.nn.functional.leaky_relu(t, 0.1)
+    wd, _, wn1, _ = _cv_weights(eng)
+    d = _gather(x2.double(), knn) - x1.double()[:, :, None, :]
+    h = lk(p1.double().view(B, N, 256)[:, :, None, :] + _gather(p2.double().view(B, N, 256), knn) + d @ wd.T)
+    (w2, b2), (w3, b3) = layers
+    h2 = lk(h @ w2.T + b2)
+    return h2, lk(h2 @ w3.T + b3), weight_net(d, wn1)
+
+
+@pytest.mark.parametrize("B,N", CV_CRAFTED_SHAPES)
+@pytest.mark.parametrize("which", [0, 1])
+def test_cost_volume_weight_rows_spanning_24_binades(eng, which, B, N):
+    """Rows of W2 (which = 0), then of W3 (1), at 2^0 .. 2^-24 of the matrix maximum, the bias scaled alike, on rtk_cost_volume,
+    _split and _split_shared.  Per output channel c (= row c of W3), as test_sa_scale_weight_rows_spanning_24_binades, with the
+    magnitude of the channel's sums mag_c = max_i sum_k wn_kc (|b3_c| + |W3_c| . |h2_k|): rows of W3 within 2^-16 of the maximum
+    carry the full relative bound, smaller ones 2e-6 mag + 4 floor with floor = 2^-39 max|W3| max sum|h2| (times the point's sum
+    of WeightNet weights); the fp32-input kernel the full bound on every row.  Scaled rows of W2 leave every row of W3 at full size.
+    Measured (MI355X): rows within 2^-16 at most 1.9e-6 split / 1.1e-6 fp32-input -- W2 scaled at (3, 243), a channel whose WeightNet
+    weight is nearly dead at every point, so that mag_c is small against the WeightNet's own rounding; 3.7e-7 elsewhere --, smaller
+    rows 7.8e-6 of their magnitude split (inside the floor), 9.5e-7 fp32-input."""
+    layers = _cv_random_layers(77 + which)
+    f = 2.0 ** -torch.linspace(0, 24, 256, device=DEV, dtype=torch.float64).round()
+    layers[which] = [layers[which][0] * f[:, None], layers[which][1] * f]
+    layers = [[w.float().double(), b.float().double()] for w, b in layers]
+    x1, x2, p1, p2, knn = _cv_operands(B, N, seed=B + N + which)
+    crafted = _cv_crafted(layers)
+    r64 = _cv_reference(eng, torch.float64, B, N, x1, x2, knn, p1, p2, layers=layers)
+    h2, _, wn = _cv_inner(eng, x1, x2, knn, p1, p2, layers, B, N)
+    (_, _), (w3, b3) = layers
+    wsum = wn.sum(2)                                                        # (B, N, 256): the WeightNet's outputs are >= 0
+    mag = ((wn * (h2.abs() @ w3.abs().T + b3.abs())).sum(2)).amax((0, 1))
+    floor = 2.0 ** -39 * float(w3.abs().max()) * float(h2.abs().sum(-1).max()) * wsum.amax((0, 1))
+    big = f >= 2.0 ** -16 if which == 1 else torch.ones(256, dtype=torch.bool, device=DEV)
+    for variant in ["plain", "split", "shared%d" % F.cv_shared_workgroups(B, N, DEV)]:
+        out = _cv_launch(eng, variant, B, N, x1, x2, knn, p1, p2, crafted=crafted)
+        assert (out[B * N:] == SENT).all() and (out[:, 256:] == SENT).all(), variant
+        err = (out[:B * N, :256].double() - r64).abs().amax(0)
+        rel = err / mag.clamp_min(1e-300)               # (a channel the WeightNet's ReLU leaves at 0 everywhere: mag = err = 0)
+        small = float(rel[~big].max()) if bool((~big).any()) else 0.0
+        print("\ncost volume rows of W%d 2^0..2^-24 %s B %d N %d: rel err rows >= 2^-16 %.2e, rows < 2^-16 %.2e" % (
+            which + 2, variant, B, N, float(rel[big].max()), small))
+        assert float(rel[big].max()) <= 2e-6, variant
+        if variant == "plain":
+            assert float(rel.max()) <= 2e-6
+        else:
+            assert bool((err[~big] <= 2e-6 * mag[~big] + 4 * floor[~big]).all()), variant
+
+
+@pytest.mark.parametrize("B,N", CV_CRAFTED_SHAPES)
+def test_cost_volume_positions_of_any_magnitude(eng, B, N):
+    """The p1 row of point i and the p2 row of point j scaled by 10^e, e cycling through -6, 6, -3, 3, 0 over the points, b2 = b3 = 0:
+    the 16 (point, neighbour) positions of one output row differ by up to twelve decades.  Each output row's error is measured
+    against its own float64 magnitude max_c sum_k |wn_kc feat_kc|, and accepted on _check's rule with that denominator.
+    Measured (MI355X): worst row 1.2e-6 split, 1.1e-6 fp32-input, torch fp32 1.1e-6."""
+    layers = [[w.float().double(), b.float().double()] for w, b in _cv_random_layers(91, bias=0.0)]
+    x1, x2, p1, p2, knn = _cv_operands(B, N, seed=B * 3 + N)
+    s = (10.0 ** torch.tensor([-6.0, 6.0, -3.0, 3.0, 0.0], device=DEV))[torch.arange(N, device=DEV) % 5].repeat(B)
+    p1, p2 = (p1 * s[:, None]).contiguous(), (p2 * s.roll(2)[:, None]).contiguous()
+    crafted = _cv_crafted(layers)
+    r64 = _cv_reference(eng, torch.float64, B, N, x1, x2, knn, p1, p2, layers=layers)
+    r32 = _cv_reference(eng, torch.float32, B, N, x1, x2, knn, p1, p2, layers=layers)
+    _, feat, wn = _cv_inner(eng, x1, x2, knn, p1, p2, layers, B, N)
+    den = (wn * feat).abs().sum(2).amax(-1).reshape(B * N)
+    assert bool((den > 0).all())
+    e32 = float(((r32.double() - r64).abs().amax(1) / den).max())
+    for variant in ["plain", "split", "shared%d" % F.cv_shared_workgroups(B, N, DEV)]:
+        out = _cv_launch(eng, variant, B, N, x1, x2, knn, p1, p2, crafted=crafted)
+        assert (out[B * N:] == SENT).all() and (out[:, 256:] == SENT).all(), variant
+        assert torch.isfinite(out[:B * N, :256]).all()
+        e = float(((out[:B * N, :256].double() - r64).abs().amax(1) / den).max())
+        print("\ncost volume magnitudes %s B %d N %d: worst row kernel %.2e  torch fp32 %.2e" % (variant, B, N, e, e32))
+        assert e <= 2e-6 and e <= 3 * e32 + 2e-7, (variant, e, e32)
 
 
 # ---- non-finite inputs ------------------------------------------------------------------------------------------------------------
