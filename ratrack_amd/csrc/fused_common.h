@@ -107,6 +107,12 @@ __device__ __forceinline__ void rtk_decode_block(int gx, int &b, int &bx, int &n
         nbx = gridDim.x;
     }
 }
+// Host side, the inverse of rtk_decode_block: the grid of `samples` samples with `wgs` workgroups each, and the params' gx field that
+// tells the kernel which of the two it runs in.  How many workgroups a sample gets is every launcher's own rule.
+static inline dim3 rtk_xcd_grid(int samples, int wgs, int &gx) {
+    gx = samples % 8 == 0 ? wgs : 0;
+    return gx ? dim3(wgs * samples) : dim3(wgs, samples);
+}
 
 // ---- LDS weight stream ----------------------------------------------------------------------------
 // The packed weights of a whole layer chain form one blob of NF fragments (1 fragment = one (u, v)

@@ -166,8 +166,7 @@ extern "C" int rtk_sa_scale(int samples, int n, int npoint, int nsample, const f
     const int groups = (npoint + cpt - 1) / cpt;
     int bx = (groups + 3) / 4;                 // one unit per wave per pass ...
     while ((long)bx * samples > SA_MAX_WGS && bx > 1) bx = (bx + 1) / 2;   // few, fat workgroups: the LDS weight fill is paid per workgroup
-    P.gx = samples % 8 == 0 ? bx : 0;
-    const dim3 blocks = P.gx ? dim3(bx * samples) : dim3(bx, samples);
+    const dim3 blocks = rtk_xcd_grid(samples, bx, P.gx);
     const long key = (((long)nsample * 32 + v1) * 32 + v2) * 32 + v3;
 #define SA_CASE(ns, a, b, c)                                              \
     case (((long)(ns) * 32 + (a)) * 32 + (b)) * 32 + (c):                 \
@@ -395,8 +394,7 @@ static int cost_volume_launch(const char *who, int samples, int n1, int n2, cons
     int gx = 256 * CV_WGS_PER_CU / samples;           // resident workgroups; the rest is looped
     if (gx < 1) gx = 1;
     if (gx > groups) gx = groups;
-    P.gx = samples % 8 == 0 ? gx : 0;
-    const dim3 grid = P.gx ? dim3(gx * samples) : dim3(gx, samples);
+    const dim3 grid = rtk_xcd_grid(samples, gx, P.gx);
     if (save) cost_volume_kernel<true><<<grid, 64 * CV_NW, 0, (hipStream_t)stream>>>(P);
     else cost_volume_kernel<false><<<grid, 64 * CV_NW, 0, (hipStream_t)stream>>>(P);
     RTK_CHECK_LAUNCH(who);
@@ -594,8 +592,7 @@ extern "C" int rtk_cost_volume_bwd(int samples, int n1, int n2, const float *xyz
     int gx = 256 * CV_WGS_PER_CU / samples;
     if (gx < 1) gx = 1;
     if (gx > groups) gx = groups;
-    P.gx = samples % 8 == 0 ? gx : 0;
-    const dim3 grid = P.gx ? dim3(gx * samples) : dim3(gx, samples);
+    const dim3 grid = rtk_xcd_grid(samples, gx, P.gx);
     cost_volume_bwd_kernel<<<grid, 64 * CV_NW, 0, (hipStream_t)stream>>>(Q);
     RTK_CHECK_LAUNCH("cost_volume_bwd");
     return RTK_OK;
@@ -799,8 +796,8 @@ extern "C" int rtk_patch_cost_wave16(int samples, int n, const float *xyz, const
     RTK_REQUIRE(samples <= 65535, "patch_cost: too many samples");
     int gx = (n + 3) / 4;
     while ((long)gx * samples > PC_WGS_TARGET && gx > 1) gx = (gx + 1) / 2;
-    P.gx = samples % 8 == 0 ? gx : 0;
-    patch_cost_kernel<<<P.gx ? dim3(gx * samples) : dim3(gx, samples), 256, 0, (hipStream_t)stream>>>(P);
+    const dim3 grid = rtk_xcd_grid(samples, gx, P.gx);
+    patch_cost_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(P);
     RTK_CHECK_LAUNCH("patch_cost");
     return RTK_OK;
 }
@@ -877,8 +874,8 @@ extern "C" int rtk_patch_cost_bwd(int samples, int n, const float *xyz, const in
     RTK_REQUIRE(samples <= 65535, "patch_cost_bwd: too many samples");
     int gx = (n + 3) / 4;
     while ((long)gx * samples > 4096 && gx > 1) gx = (gx + 1) / 2;
-    P.gx = samples % 8 == 0 ? gx : 0;
-    patch_cost_bwd_kernel<<<P.gx ? dim3(gx * samples) : dim3(gx, samples), 256, 0, (hipStream_t)stream>>>(Q);
+    const dim3 grid = rtk_xcd_grid(samples, gx, P.gx);
+    patch_cost_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(Q);
     RTK_CHECK_LAUNCH("patch_cost_bwd");
     return RTK_OK;
 }

@@ -169,8 +169,8 @@ extern "C" int rtk_patch_cost(int samples, int n, const float *xyz, const int64_
     P.out = out; P.out_pitch = out_pitch;
     int gx = (n + PT_PPW - 1) / PT_PPW;                                       // one tile per wave ...
     while ((long)gx * samples > PT_WGS_TARGET && gx > 1) gx = (gx + 1) / 2;   // ... halved until the launch has at most PT_WGS_TARGET workgroups
-    P.gx = samples % 8 == 0 ? gx : 0;
-    patch_cost_tile_kernel<<<P.gx ? dim3(gx * samples) : dim3(gx, samples), 64 * PT_NW, 0, (hipStream_t)stream>>>(P);
+    const dim3 grid = rtk_xcd_grid(samples, gx, P.gx);
+    patch_cost_tile_kernel<<<grid, 64 * PT_NW, 0, (hipStream_t)stream>>>(P);
     RTK_CHECK_LAUNCH("patch_cost");
     return RTK_OK;
 }

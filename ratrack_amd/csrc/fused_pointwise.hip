@@ -8,6 +8,10 @@
 //
 // Structure: see fused_common.h.  A wave owns 16 points; all layers run back to back on the MFMA
 // pipe with activations held in registers; HBM sees each input row once and each output row once.
+//
+// Three entry points: rtk_pointwise_mlp (the chain), rtk_pointwise_mlp_tap (the encoder's last layer and the cost volume's projection
+// of its output on the same tile) and rtk_pointwise_mlp_pair (two chains on the same rows).  They share one host launch layer -- the
+// pw_* validators and pw_grid, after the first kernel -- and each adds the fields, the instance and the launch that only it has.
 #include <string.h>
 
 #include "rtk_common.h"
@@ -262,16 +266,84 @@ __global__ __launch_bounds__(64 * PW_NW, 2) void pointwise_mlp_kernel(const PwPa
     ws.finish();
 }
 
+// ---- the host launch layer of the three entry points --------------------------------------------------------------------------
+// `who` is the entry point's name, for the messages.  Every helper returns a count >= 0 or, after rtk_set_error, RTK_ERR_INVALID.
+static int pw_rows(const char *who, PwParams &P, int rows, int rows_per_sample) {
+    RTK_REQUIRE(rows > 0 && rows_per_sample > 0 && rows % rows_per_sample == 0 && rows / rows_per_sample <= 65535,
+                "%s: bad row counts (%d, %d)", who, rows, rows_per_sample);
+    P.rows = rows; P.rows_per_sample = rows_per_sample;
+    return RTK_OK;
+}
+
+// P.src, P.nsrc -> the 16-channel input slots the sources take
+static int pw_sources(const char *who, PwParams &P, int nsrc, const rtk_src_t *srcs) {
+    RTK_REQUIRE(nsrc >= 0 && nsrc <= RTK_MAX_SRC && (nsrc == 0 || srcs), "%s: nsrc=%d", who, nsrc);
+    int U = 0;
+    for (int s = 0; s < nsrc; ++s) {
+        RTK_REQUIRE(srcs[s].ptr && srcs[s].pitch % 4 == 0 && srcs[s].channels > 0 && srcs[s].pitch >= ((srcs[s].channels + 3) / 4) * 4,
+                    "%s: bad source %d (pitch %d, channels %d)", who, s, srcs[s].pitch, srcs[s].channels);
+        P.src[s] = srcs[s];
+        U += (srcs[s].channels + 15) / 16;
+    }
+    P.nsrc = nsrc;
+    return U;
+}
+
+// P.interp -> the slots the interpolation segment takes, which must be `slots` of them unless that is 0
+static int pw_interp(const char *who, PwParams &P, const rtk_interp_t *interp, int slots) {
+    RTK_REQUIRE(interp && interp->known_feats && interp->idx && interp->dist2 && interp->pitch % 4 == 0 && interp->channels % 4 == 0 &&
+                (slots == 0 || (interp->channels + 15) / 16 == slots), "%s: bad interp segment (%d slots of 16 channels; 0: any)", who, slots);
+    P.interp = *interp;
+    return (interp->channels + 15) / 16;
+}
+
+// A chain of n layers, copied to dst with the image flag stripped from act.  All of its images are split images or all fp32 ones
+// (`split`); layer l takes want[l] blocks of 16 channels and gives want[l + 1] (<= 0: any number); every image lies where the one
+// before it ends, because the kernels stream a chain as one blob.  *next (optional): in, where the first image must lie unless null;
+// out, where the last one ends.
+static int pw_chain(const char *who, const char *what, int n, const rtk_layer_t *layers, bool split, const int *want, const float **next,
+                    rtk_layer_t *dst) {
+    RTK_REQUIRE(n >= 1 && n <= RTK_MAX_LAYERS && layers, "%s: %s: %d layers", who, what, n);
+    const float *w = next ? *next : nullptr;
+    int cin = want[0];
+    for (int l = 0; l < n; ++l) {
+        const rtk_layer_t &L = layers[l];
+        RTK_REQUIRE(L.w_packed && L.bias && L.cin16 == cin && L.cout16 > 0 && (want[l + 1] <= 0 || L.cout16 == want[l + 1]),
+                    "%s: %s: layer %d expects cin16=%d, cout16=%d (0: any), got %d, %d", who, what, l, cin, want[l + 1], L.cin16, L.cout16);
+        RTK_REQUIRE(((L.act & RTK_LAYER_SPLIT) != 0) == split, "%s: %s: layer %d must be %s image like the rest of the chain", who, what, l,
+                    split ? "a split" : "an fp32");
+        RTK_REQUIRE(!w || L.w_packed == w, "%s: %s: the packed weights of a chain must be contiguous (layer %d)", who, what, l);
+        w = L.w_packed + (size_t)(split ? split16_nf(L.cin16, L.cout16) : L.cin16 * L.cout16) * 256;
+        dst[l] = L;
+        dst[l].act = L.act & 0xff;
+        cin = L.cout16;
+    }
+    if (next) *next = w;
+    return RTK_OK;
+}
+
+// An output of `channels` <= max_channels channels; a row-major one has a pitch
+static int pw_out(const char *who, const char *what, const float *out, int channels, int max_channels, bool row_major, int pitch) {
+    RTK_REQUIRE(out && channels > 0 && channels <= max_channels, "%s: %s: %d channels (at most %d)", who, what, channels, max_channels);
+    RTK_REQUIRE(!row_major || (pitch % 4 == 0 && pitch >= channels), "%s: %s: bad pitch %d for %d channels", who, what, pitch, channels);
+    return RTK_OK;
+}
+
+// The family's grid: a workgroup owns one sample and strides over its groups of PW_NW * 16 rows; about wgs_target workgroups per
+// launch, the rest is looped (1024: 5 % slower end to end)
+static dim3 pw_grid(PwParams &P, int wgs_target) {
+    const int samples = P.rows / P.rows_per_sample;
+    const int groups = (P.rows_per_sample + PW_NW * 16 - 1) / (PW_NW * 16);
+    int gx = wgs_target / samples;
+    if (gx < 1) gx = 1;
+    if (gx > groups) gx = groups;
+    return rtk_xcd_grid(samples, gx, P.gx);
+}
+
 template <int U, int V1, int V2, int V3, int V4>
 static int launch_pw(const PwParams &P0, bool interp, bool split, hipStream_t s) {
     PwParams P = P0;
-    const int samples = P.rows / P.rows_per_sample;
-    const int groups = (P.rows_per_sample + PW_NW * 16 - 1) / (PW_NW * 16);
-    int gx = PW_WGS_TARGET / samples;           // (1024: 5 % slower end to end)
-    if (gx < 1) gx = 1;
-    if (gx > groups) gx = groups;
-    P.gx = samples % 8 == 0 ? gx : 0;
-    const dim3 blocks = P.gx ? dim3(gx * samples) : dim3(gx, samples);
+    const dim3 blocks = pw_grid(P, PW_WGS_TARGET);
     if (interp && split) pointwise_mlp_kernel<U, V1, V2, V3, V4, true, true><<<blocks, 256, 0, s>>>(P);
     else if (interp) pointwise_mlp_kernel<U, V1, V2, V3, V4, true, false><<<blocks, 256, 0, s>>>(P);
     else if (split) pointwise_mlp_kernel<U, V1, V2, V3, V4, false, true><<<blocks, 256, 0, s>>>(P);
@@ -283,53 +355,20 @@ extern "C" int rtk_pointwise_mlp(int rows, int rows_per_sample, const rtk_interp
                                  const rtk_src_t *srcs, const float *sample_bias, int nlayers,
                                  const rtk_layer_t *layers, float *out, int out_pitch, int out_channels,
                                  int out_channel_major, const int *row_nuniq, float *colmax, rtk_stream_t stream) {
-    RTK_REQUIRE(rows > 0 && rows_per_sample > 0 && rows % rows_per_sample == 0 && rows / rows_per_sample <= 65535,
-                "pointwise_mlp: bad row counts (%d, %d)", rows, rows_per_sample);
-    RTK_REQUIRE(nsrc >= 0 && nsrc <= RTK_MAX_SRC && (nsrc == 0 || srcs), "pointwise_mlp: nsrc=%d", nsrc);
-    RTK_REQUIRE(nlayers >= 1 && nlayers <= RTK_MAX_LAYERS && layers && out, "pointwise_mlp: nlayers=%d", nlayers);
+    static const char who[] = "pointwise_mlp";
     PwParams P;
     memset(&P, 0, sizeof(P));
-    P.rows = rows;
-    P.rows_per_sample = rows_per_sample;
-    int U = 0;
-    if (interp) {
-        RTK_REQUIRE(interp->known_feats && interp->idx && interp->dist2 && interp->pitch % 4 == 0 && interp->channels % 4 == 0,
-                    "pointwise_mlp: bad interp segment");
-        P.interp = *interp;
-        U += (interp->channels + 15) / 16;
-    }
-    P.nsrc = nsrc;
-    for (int s = 0; s < nsrc; ++s) {
-        RTK_REQUIRE(srcs[s].ptr && srcs[s].pitch % 4 == 0 && srcs[s].channels > 0 && srcs[s].pitch >= ((srcs[s].channels + 3) / 4) * 4,
-                    "pointwise_mlp: bad source %d (pitch %d, channels %d)", s, srcs[s].pitch, srcs[s].channels);
-        P.src[s] = srcs[s];
-        U += (srcs[s].channels + 15) / 16;
-    }
-    P.sample_bias = sample_bias;
+    if (pw_rows(who, P, rows, rows_per_sample) < 0) return RTK_ERR_INVALID;
+    const int ui = interp ? pw_interp(who, P, interp, 0) : 0, us = pw_sources(who, P, nsrc, srcs);
+    if (ui < 0 || us < 0) return RTK_ERR_INVALID;
+    const int U = ui + us, want[RTK_MAX_LAYERS + 1] = {U, 0, 0, 0, 0};
+    const bool split = nlayers >= 1 && layers && (layers[0].act & RTK_LAYER_SPLIT) != 0;      // the chain's images are split images (rtk_fused.h)
+    if (pw_chain(who, "chain", nlayers, layers, split, want, nullptr, P.layer) < 0) return RTK_ERR_INVALID;
     int V[RTK_MAX_LAYERS] = {0, 0, 0, 0};
-    int cin = U;
-    const bool split = (layers[0].act & RTK_LAYER_SPLIT) != 0;      // the chain's images are split images (rtk_fused.h)
-    for (int l = 0; l < nlayers; ++l) {
-        RTK_REQUIRE(layers[l].w_packed && layers[l].bias && layers[l].cin16 == cin && layers[l].cout16 > 0,
-                    "pointwise_mlp: layer %d expects cin16=%d, got %d (cout16=%d)", l, cin, layers[l].cin16, layers[l].cout16);
-        RTK_REQUIRE(((layers[l].act & RTK_LAYER_SPLIT) != 0) == split, "pointwise_mlp: split and fp32 images in one chain (layer %d)", l);
-        const size_t prev_floats = l == 0 ? 0 : (split ? (size_t)split16_nf(layers[l - 1].cin16, layers[l - 1].cout16) * 256
-                                                        : (size_t)layers[l - 1].cin16 * layers[l - 1].cout16 * 256);
-        RTK_REQUIRE(l == 0 || layers[l].w_packed == layers[l - 1].w_packed + prev_floats,
-                    "pointwise_mlp: the packed weights of a chain must be contiguous (layer %d)", l);
-        P.layer[l] = layers[l];
-        P.layer[l].act = layers[l].act & 0xff;
-        V[l] = layers[l].cout16;
-        cin = V[l];
-    }
-    P.out = out;
-    P.out_pitch = out_pitch;
-    P.out_channels = out_channels;
-    P.out_cm = out_channel_major;
-    P.row_nuniq = row_nuniq;
-    P.colmax = colmax;
-    RTK_REQUIRE(out_channels > 0 && out_channels <= 16 * cin, "pointwise_mlp: out_channels=%d", out_channels);
-    RTK_REQUIRE(out_channel_major || (out_pitch % 4 == 0 && out_pitch >= out_channels), "pointwise_mlp: bad out_pitch %d", out_pitch);
+    for (int l = 0; l < nlayers; ++l) V[l] = P.layer[l].cout16;
+    if (pw_out(who, "out", out, out_channels, 16 * V[nlayers - 1], !out_channel_major, out_pitch) < 0) return RTK_ERR_INVALID;
+    P.sample_bias = sample_bias; P.row_nuniq = row_nuniq; P.colmax = colmax;
+    P.out = out; P.out_pitch = out_pitch; P.out_channels = out_channels; P.out_cm = out_channel_major;
     hipStream_t s = (hipStream_t)stream;
     const bool it = interp != nullptr;
     const long key = ((((long)U * 32 + V[0]) * 32 + V[1]) * 32 + V[2]) * 32 + V[3];
@@ -490,45 +529,25 @@ __global__ __launch_bounds__(64 * PW_NW, 2) void pointwise_tap_kernel(const TapP
 extern "C" int rtk_pointwise_mlp_tap(int rows, int rows_per_sample, const rtk_interp_t *interp, const rtk_layer_t *layer, float *out,
                                      int out_pitch, float *colmax, const rtk_layer_t *proj, int frame_split, float *proj_out, int proj_pitch,
                                      rtk_stream_t stream) {
-    RTK_REQUIRE(rows > 0 && rows_per_sample > 0 && rows % rows_per_sample == 0 && rows / rows_per_sample <= 65535,
-                "pointwise_mlp_tap: bad row counts (%d, %d)", rows, rows_per_sample);
-    RTK_REQUIRE(interp && interp->known_feats && interp->idx && interp->dist2 && interp->pitch % 4 == 0 && interp->channels % 4 == 0 &&
-                (interp->channels + 15) / 16 == 8, "pointwise_mlp_tap: bad interp segment (128 channels)");
-    RTK_REQUIRE(layer && layer->w_packed && layer->bias && layer->cin16 == 8 && layer->cout16 == 8 && (layer->act & RTK_LAYER_SPLIT),
-                "pointwise_mlp_tap: the layer must be a split 128 -> 128 image");
-    RTK_REQUIRE(proj && frame_split >= 0 && proj_out && proj_pitch % 4 == 0 && proj_pitch >= 256, "pointwise_mlp_tap: bad projection output");
-    for (int k = 0; k < 2; ++k)
-        RTK_REQUIRE(proj[k].w_packed && proj[k].bias && proj[k].cin16 == 8 && proj[k].cout16 == 16 && (proj[k].act & RTK_LAYER_SPLIT) &&
-                    (proj[k].act & 0xff) == 0, "pointwise_mlp_tap: projection %d must be a split 128 -> 256 image without activation", k);
-    RTK_REQUIRE(out && out_pitch % 4 == 0 && out_pitch >= 128, "pointwise_mlp_tap: bad out_pitch %d", out_pitch);
+    static const char who[] = "pointwise_mlp_tap";
+    static const int layer_blocks[2] = {8, 8}, proj_blocks[2] = {8, 16};
     TapParams T;
     memset(&T, 0, sizeof(T));
     PwParams &P = T.pw;
-    P.rows = rows;
-    P.rows_per_sample = rows_per_sample;
-    P.interp = *interp;
-    P.layer[0] = *layer;
-    P.layer[0].act = layer->act & 0xff;
-    P.out = out;
-    P.out_pitch = out_pitch;
-    P.out_channels = 128;
-    P.colmax = colmax;
+    if (pw_rows(who, P, rows, rows_per_sample) < 0 || pw_interp(who, P, interp, 8) < 0 ||
+        pw_chain(who, "the split 128 -> 128 layer", 1, layer, true, layer_blocks, nullptr, P.layer) < 0 ||
+        pw_out(who, "out", out, 128, 128, true, out_pitch) < 0 || pw_out(who, "proj_out", proj_out, 256, 256, true, proj_pitch) < 0)
+        return RTK_ERR_INVALID;
+    RTK_REQUIRE(proj && frame_split >= 0, "%s: bad projection (frame_split %d)", who, frame_split);
     for (int k = 0; k < 2; ++k) {
-        T.proj_w[k] = proj[k].w_packed;
-        T.proj_b[k] = proj[k].bias;
-        T.proj_inv[k] = proj[k].inv_scale;
+        rtk_layer_t L;
+        if (pw_chain(who, "a split 128 -> 256 projection", 1, proj + k, true, proj_blocks, nullptr, &L) < 0) return RTK_ERR_INVALID;
+        RTK_REQUIRE(L.act == 0, "%s: projection %d must have no activation", who, k);
+        T.proj_w[k] = L.w_packed; T.proj_b[k] = L.bias; T.proj_inv[k] = L.inv_scale;
     }
-    T.frame_split = frame_split;
-    T.pout = proj_out;
-    T.pout_pitch = proj_pitch;
-    // the grid of launch_pw
-    const int samples = rows / rows_per_sample;
-    const int groups = (rows_per_sample + PW_NW * 16 - 1) / (PW_NW * 16);
-    int gx = PW_WGS_TARGET / samples;
-    if (gx < 1) gx = 1;
-    if (gx > groups) gx = groups;
-    P.gx = samples % 8 == 0 ? gx : 0;
-    const dim3 blocks = P.gx ? dim3(gx * samples) : dim3(gx, samples);
+    P.out = out; P.out_pitch = out_pitch; P.out_channels = 128; P.colmax = colmax;
+    T.frame_split = frame_split; T.pout = proj_out; T.pout_pitch = proj_pitch;
+    const dim3 blocks = pw_grid(P, PW_WGS_TARGET);
     pointwise_tap_kernel<8, 8, 16><<<blocks, 64 * PW_NW, 0, (hipStream_t)stream>>>(T);
     RTK_CHECK_LAUNCH("pointwise_mlp_tap");
     return RTK_OK;
@@ -625,56 +644,24 @@ __global__ __launch_bounds__(64 * PW_NW, 2) void pointwise_pair_kernel(const Pai
 extern "C" int rtk_pointwise_mlp_pair(int rows, int rows_per_sample, int nsrc, const rtk_src_t *srcs, const float *sample_bias,
                                       const rtk_layer_t *layer_a, float *out_a, int out_a_pitch, int out_a_channels, int nlayers_b,
                                       const rtk_layer_t *layers_b, float *out_b, int out_b_channels, rtk_stream_t stream) {
-    RTK_REQUIRE(rows > 0 && rows_per_sample > 0 && rows % rows_per_sample == 0 && rows / rows_per_sample <= 65535,
-                "pointwise_mlp_pair: bad row counts (%d, %d)", rows, rows_per_sample);
-    RTK_REQUIRE(nsrc >= 1 && nsrc <= RTK_MAX_SRC && srcs && layer_a && layers_b && out_a && out_b, "pointwise_mlp_pair: nsrc=%d", nsrc);
+    static const char who[] = "pointwise_mlp_pair";
+    static const int a_blocks[2] = {25, 2}, b_blocks[5] = {16, 8, 4, 2, 1};
     PairParams T;
     memset(&T, 0, sizeof(T));
     PwParams &P = T.pw;
-    P.rows = rows;
-    P.rows_per_sample = rows_per_sample;
-    P.nsrc = nsrc;
-    int U = 0;
-    for (int s = 0; s < nsrc; ++s) {
-        RTK_REQUIRE(srcs[s].ptr && srcs[s].pitch % 4 == 0 && srcs[s].channels > 0 && srcs[s].pitch >= ((srcs[s].channels + 3) / 4) * 4,
-                    "pointwise_mlp_pair: bad source %d (pitch %d, channels %d)", s, srcs[s].pitch, srcs[s].channels);
-        P.src[s] = srcs[s];
-        U += (srcs[s].channels + 15) / 16;
-    }
+    if (pw_rows(who, P, rows, rows_per_sample) < 0) return RTK_ERR_INVALID;
+    const int U = pw_sources(who, P, nsrc, srcs);
+    if (U < 0) return RTK_ERR_INVALID;
     // the one instance: [.. | 256 channels] -> 32 next to 256 -> 128 -> 64 -> 32 -> 16 on the last source, split images in one blob
-    const int UB = (srcs[nsrc - 1].channels + 15) / 16;
-    RTK_REQUIRE(U == 25 && UB == 16 && nlayers_b == 4, "pointwise_mlp_pair: no kernel instance for U=%d UB=%d, %d layers", U, UB, nlayers_b);
-    RTK_REQUIRE(layer_a->w_packed && layer_a->bias && (layer_a->act & RTK_LAYER_SPLIT) && layer_a->cin16 == 25 && layer_a->cout16 == 2,
-                "pointwise_mlp_pair: chain A must be one split 25 -> 2 block layer");
-    static const int vb[5] = {16, 8, 4, 2, 1};
-    const float *w = layer_a->w_packed + (size_t)split16_nf(25, 2) * 256;
-    for (int l = 0; l < 4; ++l) {
-        RTK_REQUIRE(layers_b[l].bias && (layers_b[l].act & RTK_LAYER_SPLIT) && layers_b[l].cin16 == vb[l] && layers_b[l].cout16 == vb[l + 1],
-                    "pointwise_mlp_pair: chain B layer %d must be a split %d -> %d block layer", l, vb[l], vb[l + 1]);
-        RTK_REQUIRE(layers_b[l].w_packed == w, "pointwise_mlp_pair: the images must be contiguous, chain A's first (chain B layer %d)", l);
-        w += (size_t)split16_nf(vb[l], vb[l + 1]) * 256;
-        T.lb[l] = layers_b[l];
-        T.lb[l].act = layers_b[l].act & 0xff;
-    }
-    P.layer[0] = *layer_a;
-    P.layer[0].act = layer_a->act & 0xff;
-    P.sample_bias = sample_bias;
-    P.out = out_a;
-    P.out_pitch = out_a_pitch;
-    P.out_channels = out_a_channels;
-    RTK_REQUIRE(out_a_channels > 0 && out_a_channels <= 32 && out_a_pitch % 4 == 0 && out_a_pitch >= out_a_channels,
-                "pointwise_mlp_pair: bad output A (%d channels, pitch %d)", out_a_channels, out_a_pitch);
-    RTK_REQUIRE(out_b_channels > 0 && out_b_channels <= 16, "pointwise_mlp_pair: out_b_channels=%d", out_b_channels);
-    T.out_b = out_b;
-    T.out_b_channels = out_b_channels;
-    // the grid of launch_pw
-    const int samples = rows / rows_per_sample;
-    const int groups = (rows_per_sample + PW_NW * 16 - 1) / (PW_NW * 16);
-    int gx = PW_WGS_TARGET / samples;
-    if (gx < 1) gx = 1;
-    if (gx > groups) gx = groups;
-    P.gx = samples % 8 == 0 ? gx : 0;
-    const dim3 blocks = P.gx ? dim3(gx * samples) : dim3(gx, samples);
+    const int UB = nsrc >= 1 ? (srcs[nsrc - 1].channels + 15) / 16 : 0;
+    RTK_REQUIRE(U == 25 && UB == 16 && nlayers_b == 4, "%s: no kernel instance for U=%d UB=%d, %d layers", who, U, UB, nlayers_b);
+    const float *w = nullptr;
+    if (pw_chain(who, "chain A", 1, layer_a, true, a_blocks, &w, P.layer) < 0 || pw_chain(who, "chain B", 4, layers_b, true, b_blocks, &w, T.lb) < 0 ||
+        pw_out(who, "out_a", out_a, out_a_channels, 32, true, out_a_pitch) < 0 || pw_out(who, "out_b", out_b, out_b_channels, 16, false, 0) < 0)
+        return RTK_ERR_INVALID;
+    P.sample_bias = sample_bias; P.out = out_a; P.out_pitch = out_a_pitch; P.out_channels = out_a_channels;
+    T.out_b = out_b; T.out_b_channels = out_b_channels;
+    const dim3 blocks = pw_grid(P, PW_WGS_TARGET);
     pointwise_pair_kernel<25, 2, 16, 8, 4, 2, 1><<<blocks, 64 * PW_NW, 0, (hipStream_t)stream>>>(T);
     RTK_CHECK_LAUNCH("pointwise_mlp_pair");
     return RTK_OK;

@@ -910,8 +910,7 @@ static int cv_split_fill(const char *who, CvSplitParams &P, int samples, int n1,
     int gx = 256 / samples;
     if (gx < 1) gx = 1;
     if (gx > groups) gx = groups;
-    P.gx = samples % 8 == 0 ? gx : 0;
-    grid = P.gx ? dim3(gx * samples) : dim3(gx, samples);
+    grid = rtk_xcd_grid(samples, gx, P.gx);
     return RTK_OK;
 }
 
@@ -1037,8 +1036,7 @@ extern "C" int rtk_sa_scale_split(int samples, int n, int npoint, int nsample, c
     const int units = (npoint + 32 / nsample - 1) / (32 / nsample);
     int bx = (units + 3) / 4;
     while ((long)bx * samples > SA_WGS_TARGET && bx > 1) bx = (bx + 1) / 2;      // few, fat workgroups: the LDS image fill is paid per workgroup
-    P.gx = samples % 8 == 0 ? bx : 0;
-    const dim3 blocks = P.gx ? dim3(bx * samples) : dim3(bx, samples);
+    const dim3 blocks = rtk_xcd_grid(samples, bx, P.gx);
     hipStream_t s = (hipStream_t)stream;
     if (nsample == 32 && c1 == 64) sa_scale_split_kernel<32, 64><<<blocks, 256, 0, s>>>(P);
     else if (nsample == 16 && c1 == 64) sa_scale_split_kernel<16, 64><<<blocks, 256, 0, s>>>(P);

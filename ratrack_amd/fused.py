@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from . import pointnet2_hip as _native
-from .abi import CopyJob as _CopyJob, GtermJob as _GtJob, Interp as _Interp, Layer as _Layer, Src as _Src, stream as _stream
+from .abi import CopyJob as _CopyJob, GtermJob as _GtJob, Interp as _Interp, Layer as _Layer, Src as _Src, ptr as _ptr, stream as _stream
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
 
@@ -177,24 +177,37 @@ def pad_bias(b, cout):
     return out
 
 
+PW_FRAGMENT_FLOATS = 256           # an fp32 fragment (pack_layer): 64 lanes x 4 floats, one per (input block, output block)
+SPLIT_FRAGMENT_INT16 = 512         # a split fragment (pack_layer_split16): 64 lanes x 8 fp16, ...
+SPLIT_PIECES = 2                   # ... one per (PAIR of input blocks, output block, piece h / l)
+
+
+_fp32_image = lambda u, v: u * v * PW_FRAGMENT_FLOATS                                     # floats in the image of a layer from u to v blocks of 16 channels
+_split_image = lambda u, v: ((u + 1) // 2) * v * SPLIT_PIECES * SPLIT_FRAGMENT_INT16      # int16 elements in its split image
+
+
 class Chain:
     """A chain of packed layers living in ONE contiguous device blob (the kernels stream it through LDS)."""
+
+    @staticmethod
+    def _layer_arr(base, elem_size, image_elems, bias, layers):
+        """layers: (cin16, cout16, act, inv_scale) each -> (the _Layer array whose images lie back to back from address `base` and
+        whose padded biases lie back to back from address `bias`, the address where the images end); image_elems(cin16, cout16):
+        elements of elem_size bytes in one layer's image.  The array holds raw addresses: whoever keeps it keeps the tensors too."""
+        arr = (_Layer * len(layers))()
+        for i, (u, v, act, inv) in enumerate(layers):
+            arr[i].w_packed, arr[i].bias = base, bias
+            arr[i].cin16, arr[i].cout16, arr[i].act, arr[i].inv_scale = u, v, act, inv
+            base, bias = base + elem_size * image_elems(u, v), bias + 4 * 16 * v
+        return arr, base
 
     def split_arr(self):
         """The same chain as split images (rtk_pointwise_mlp with RTK_LAYER_SPLIT), built on first use."""
         if self._split is None:
             packed = [pack_layer_split16(w.to(self._device)) for w, _ in self._layers]
             blob = torch.cat([im for im, _ in packed]).contiguous()
-            arr = (_Layer * len(self._layers))()
-            off = boff = 0
-            for i, (w, act) in enumerate(self._layers):
-                cout, cin = w.shape
-                u, v = ceil16(cin) // 16, ceil16(cout) // 16
-                arr[i].w_packed = blob.data_ptr() + 2 * off
-                arr[i].bias = self.bias.data_ptr() + 4 * boff
-                arr[i].cin16, arr[i].cout16, arr[i].act, arr[i].inv_scale = u, v, act | LAYER_SPLIT, packed[i][1]
-                off += ((u + 1) // 2) * v * 2 * 512      # int16 elements per fragment: 64 lanes x 8
-                boff += v * 16
+            arr, _ = self._layer_arr(blob.data_ptr(), 2, _split_image, self.bias.data_ptr(),
+                                     [(l.cin16, l.cout16, l.act | LAYER_SPLIT, inv) for l, (_, inv) in zip(self.arr, packed)])
             self._split = (arr, blob)
         return self._split[0]
 
@@ -205,21 +218,17 @@ class Chain:
         if got is None:
             mine, theirs = self.split_arr(), other.split_arr()
             blob = torch.cat([self._split[1], other._split[1]]).contiguous()
-            arrs, off = [], 0
-            for src in (mine, theirs):
-                arr = (_Layer * len(src))()
-                for i, l in enumerate(src):
-                    arr[i].w_packed, arr[i].bias = blob.data_ptr() + 2 * off, l.bias
-                    arr[i].cin16, arr[i].cout16, arr[i].act, arr[i].inv_scale = l.cin16, l.cout16, l.act, l.inv_scale
-                    off += ((l.cin16 + 1) // 2) * l.cout16 * 2 * 512
-                arrs.append(arr)
-            got = self._pairs[id(other)] = (arrs[0], arrs[1], blob, other)      # (other: keeps the id, and its biases, alive)
+            fields = lambda arr: [(l.cin16, l.cout16, l.act, l.inv_scale) for l in arr]
+            a, end = self._layer_arr(blob.data_ptr(), 2, _split_image, self.bias.data_ptr(), fields(mine))
+            b, _ = self._layer_arr(end, 2, _split_image, other.bias.data_ptr(), fields(theirs))
+            got = self._pairs[id(other)] = (a, b, blob, other)      # (other: keeps the id, and its biases, alive)
         return got[0], got[1]
 
     def __init__(self, layers, device):
         """layers: list of (W (Cout,Cin) float64/32 tensor, bias (Cout,), act)."""
         packs, biases, meta = [], [], []
         self.dims = [tuple(w.shape) for w, _, _ in layers]          # true (Cout, Cin) per layer, for the work counter
+        self.macs = sum(co * ci for co, ci in self.dims)            # multiply-adds per row
         for w, b, act in layers:
             cout, cin = w.shape
             packs.append(pack_layer(w.to(device)))
@@ -229,15 +238,7 @@ class Chain:
         self.bias = torch.cat(biases).contiguous()
         self._layers, self._device, self._split = [(w, act) for w, _, act in layers], device, None
         self._pairs = {}
-        arr = (_Layer * len(layers))()
-        woff = boff = 0
-        for i, (u, v, act) in enumerate(meta):
-            arr[i].w_packed = self.blob.data_ptr() + 4 * woff
-            arr[i].bias = self.bias.data_ptr() + 4 * boff
-            arr[i].cin16, arr[i].cout16, arr[i].act = u, v, act
-            woff += u * v * 256
-            boff += v * 16
-        self.arr = arr
+        self.arr, _ = self._layer_arr(self.blob.data_ptr(), 4, _fp32_image, self.bias.data_ptr(), [(u, v, act, 0.0) for u, v, act in meta])
         self.n = len(layers)
         self.cout = layers[-1][0].shape[0]
         self.cout16 = meta[-1][1]
@@ -249,33 +250,37 @@ def _colptr(t, col=0):
     return t.data_ptr() + 4 * col, t.stride(0)
 
 
-def pointwise(rows, rows_per_sample, srcs, chain, out, out_channels=None, sample_bias=None, interp=None, channel_major=False,
-              row_nuniq=None, colmax=None):
-    """srcs: list of (2-D tensor or column-sliced view, channels, per_sample).  out: (rows, pitch) point-major (may be a
-    column-sliced view) or (samples, C, n) channel-major.  interp: (known_feats (samples*m, pitch), channels, m,
-    idx (rows,3) int32, dist2 (rows,3)[, nuniq (samples) int32]).  row_nuniq: per-sample count of non-duplicate rows."""
+def _src_array(srcs):
+    """srcs: list of (2-D tensor or column-sliced view, channels, per_sample) -> the rtk_src_t array (one unused element for none)."""
     arr = (_Src * max(len(srcs), 1))()
     for i, (t, ch, per) in enumerate(srcs):
         ptr, pitch = _colptr(t)
         arr[i].ptr, arr[i].pitch, arr[i].channels, arr[i].per_sample = ptr, pitch, ch, int(per)
-    ip = None
-    if interp is not None:
-        kf, ch, m, idx, d2 = interp[:5]
-        nu = interp[5] if len(interp) > 5 else None
-        ptr, pitch = _colptr(kf)
-        ip = ctypes.pointer(_Interp(ptr, pitch, ch, m, idx.data_ptr(), d2.data_ptr(), nu.data_ptr() if nu is not None else None))
+    return arr
+
+
+def _interp_ptr(interp):
+    """interp: None or (known_feats (samples*m, pitch), channels, m, idx (rows,3) int32, dist2 (rows,3)[, nuniq (samples) int32]) ->
+    None or a pointer to the rtk_interp_t."""
+    if interp is None:
+        return None
+    kf, ch, m, idx, d2 = interp[:5]
+    nu = interp[5] if len(interp) > 5 else None
+    ptr, pitch = _colptr(kf)
+    return ctypes.pointer(_Interp(ptr, pitch, ch, m, idx.data_ptr(), d2.data_ptr(), _ptr(nu)))
+
+
+def pointwise(rows, rows_per_sample, srcs, chain, out, out_channels=None, sample_bias=None, interp=None, channel_major=False,
+              row_nuniq=None, colmax=None):
+    """srcs: see _src_array.  out: (rows, pitch) point-major (may be a column-sliced view) or (samples, C, n) channel-major.
+    interp: see _interp_ptr.  row_nuniq: per-sample count of non-duplicate rows."""
     oc = out_channels if out_channels is not None else chain.cout
     if _TRACE is not None:
-        macs = sum(co * ci for co, ci in chain.dims) + (3 * interp[1] if interp is not None else 0)
+        macs = chain.macs + (3 * interp[1] if interp is not None else 0)
         _TRACE.append(("pointwise", _live_rows(row_nuniq, rows_per_sample, rows // rows_per_sample), macs))
-    if channel_major:
-        optr, opitch = out.data_ptr(), 0
-    else:
-        optr, opitch = _colptr(out)
-    _lib.call("rtk_pointwise_mlp", rows, rows_per_sample, ip, len(srcs), arr,
-              sample_bias.data_ptr() if sample_bias is not None else None, chain.n, chain.split_arr() if PW_SPLIT else chain.arr, optr, opitch, oc,
-              int(channel_major), row_nuniq.data_ptr() if row_nuniq is not None else None,
-              colmax.data_ptr() if colmax is not None else None, _stream())
+    optr, opitch = (out.data_ptr(), 0) if channel_major else _colptr(out)
+    _lib.call("rtk_pointwise_mlp", rows, rows_per_sample, _interp_ptr(interp), len(srcs), _src_array(srcs), _ptr(sample_bias), chain.n,
+              chain.split_arr() if PW_SPLIT else chain.arr, optr, opitch, oc, int(channel_major), _ptr(row_nuniq), _ptr(colmax), _stream())
     return out
 
 
@@ -287,18 +292,12 @@ def pointwise_tap(rows, rows_per_sample, chain, out, colmax, interp, proj, frame
     on a 128-channel interpolation segment, and on the same tiles proj_out (rows, 256) = proj[0] (samples < frame_split) or proj[1]
     (the others) applied to its output; proj: two one-layer 128 -> 256 chains without activation."""
     assert PW_SPLIT and chain.n == 1 and all(c.n == 1 for c in proj)
-    kf, ch, m, idx, d2 = interp[:5]
-    nu = interp[5] if len(interp) > 5 else None
-    ptr, pitch = _colptr(kf)
-    ip = ctypes.pointer(_Interp(ptr, pitch, ch, m, idx.data_ptr(), d2.data_ptr(), nu.data_ptr() if nu is not None else None))
     if _TRACE is not None:
-        _TRACE.append(("pointwise", rows, sum(co * ci for co, ci in chain.dims) + 3 * ch))
-        _TRACE.append(("pointwise", rows, sum(co * ci for co, ci in proj[0].dims)))
+        _TRACE.append(("pointwise", rows, chain.macs + 3 * interp[1]))
+        _TRACE.append(("pointwise", rows, proj[0].macs))
     pa = (_Layer * 2)(proj[0].split_arr()[0], proj[1].split_arr()[0])
-    optr, opitch = _colptr(out)
-    pptr, ppitch = _colptr(proj_out)
-    _lib.call("rtk_pointwise_mlp_tap", rows, rows_per_sample, ip, chain.split_arr(), optr, opitch, colmax.data_ptr(), pa, frame_split,
-              pptr, ppitch, _stream())
+    _lib.call("rtk_pointwise_mlp_tap", rows, rows_per_sample, _interp_ptr(interp), chain.split_arr(), *_colptr(out), colmax.data_ptr(), pa,
+              frame_split, *_colptr(proj_out), _stream())
     return out, proj_out
 
 
@@ -307,17 +306,12 @@ def pointwise_pair(rows, rows_per_sample, srcs, chain_a, out_a, sample_bias, cha
     pointwise(rows, rows_per_sample, srcs[-1:], chain_b, out_b, out_channels=out_b_channels, channel_major=True) in one launch that
     loads the rows once; chain_a: one layer on 25 input slots -> 32, chain_b: four layers on the last source's 256 channels."""
     assert PW_SPLIT and chain_a.n == 1 and chain_b.n == 4
-    arr = (_Src * len(srcs))()
-    for i, (t, ch, per) in enumerate(srcs):
-        ptr, pitch = _colptr(t)
-        arr[i].ptr, arr[i].pitch, arr[i].channels, arr[i].per_sample = ptr, pitch, ch, int(per)
     if _TRACE is not None:
-        _TRACE.append(("pointwise", rows, sum(co * ci for co, ci in chain_b.dims)))
-        _TRACE.append(("pointwise", rows, sum(co * ci for co, ci in chain_a.dims)))
+        _TRACE.append(("pointwise", rows, chain_b.macs))
+        _TRACE.append(("pointwise", rows, chain_a.macs))
     la, lb = chain_a.split_pair(chain_b)
-    optr, opitch = _colptr(out_a)
-    _lib.call("rtk_pointwise_mlp_pair", rows, rows_per_sample, len(srcs), arr, sample_bias.data_ptr() if sample_bias is not None else None,
-              la, optr, opitch, chain_a.cout, chain_b.n, lb, out_b.data_ptr(), out_b_channels, _stream())
+    _lib.call("rtk_pointwise_mlp_pair", rows, rows_per_sample, len(srcs), _src_array(srcs), _ptr(sample_bias), la, *_colptr(out_a), chain_a.cout,
+              chain_b.n, lb, out_b.data_ptr(), out_b_channels, _stream())
     return out_a, out_b
 
 
@@ -695,7 +689,7 @@ def sa_scale(geo, W, lvl, s, q, qcol, out, out_offset):
     src, dst = geo.xyz[lvl], geo.xyz[lvl + 1]
     src_nu = geo.nuniq[lvl - 1].data_ptr() if lvl > 0 else None     # level-0 source rows are the original points
     if _TRACE is not None:      # per (centroid, neighbour) pair: offset layer (3 + bias) x C1, then the resident chain
-        macs = sc.nsample * (4 * sc.c1 + sum(co * ci for co, ci in sc.chain.dims))
+        macs = sc.nsample * (4 * sc.c1 + sc.chain.macs)
         _TRACE.append(("sa_scale", _live_rows(geo.nuniq[lvl], geo.npoint, geo.samples), macs))
     if sc.split_image is not None:
         _lib.call("rtk_sa_scale_split", geo.samples, src.shape[1], geo.npoint, sc.nsample, src.data_ptr(), dst.data_ptr(),
