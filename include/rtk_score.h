@@ -2,7 +2,8 @@
  * rtk_score.h -- C ABI of the device-side ground-truth objects and tracking score of librtk_hip.so (csrc/track_score.hip,
  * ratrack_amd/track_score.py).
  *
- * Two entry points, one launch each, one workgroup per stream of a batch of B frames:
+ * Two per-frame entry points, one launch each, one workgroup per stream of a batch of B frames (and the confidence sweep over a
+ * log of such frames, at the end of this file):
  *
  *   rtk_gt_objects    the reference's objs_combined: per-box point sets, the rider merge and the minimum object size
  *                     (models/utils/track4d_utils.py:105-176 filter_object_points, elements 7 to 9 of its tuple)
@@ -33,6 +34,8 @@ extern "C" {
 #define RTK_SCORE_FLAG_NVALID 2      /* an n_valid outside [0, N] (clamped) */
 #define RTK_SCORE_FLAG_TRACKS 4      /* rtk_track_score: more label ids in a clip than the track table holds */
 #define RTK_SCORE_FLAG_OBJECTS 8     /* rtk_track_score: a num_objects outside [0, Kobj] (clamped) */
+#define RTK_SCORE_FLAG_LOG 16        /* rtk_track_score_logged: a frame did not fit the stream's log and was not logged at all */
+#define RTK_SCORE_FLAG_SWEEP 32      /* rtk_score_track_means: more track ids in one clip than RTK_SCORE_SWEEP_TRACKS (no score written) */
 
 /* LDS bytes of one workgroup for these sizes (host functions: no device is touched). */
 RTK_EXPORT int rtk_gt_objects_lds_bytes(int K, int N);
@@ -122,6 +125,70 @@ typedef struct {
  * every run. */
 RTK_EXPORT int rtk_track_score(const rtk_track_score_in_t *in, const rtk_track_score_state_t *state, const rtk_track_score_out_t *out,
                                rtk_stream_t stream);
+
+/* ---- the confidence sweep: sAMOTA / AMOTA / AMOTP (csrc/track_sweep.hip, TrackScorer.sweep) -----------------------------------
+ *
+ * The sweep metrics of Weng et al., "3D Multi-Object Tracking: A Baseline and New Evaluation Metrics", under rtk_track_score's
+ * matching rule.  L recall levels (40 in that paper).
+ *   clip         a stream's frames from one reset to the next.
+ *   track score  a track is a (stream, clip, track id); its score is the float64 sum of the fp32 object_conf of its logged
+ *                detections, added in log order, divided by their number.
+ *   replay at t  every stream is walked frame by frame.  Detections whose track score is < t are removed (a score equal to t
+ *                stays).  The others go through rtk_track_score's rule in detection order: each takes its best object -- the
+ *                largest IoU > 0, strict >, against ALL kept ground-truth objects, so it does not depend on the filter --; if a
+ *                remaining detection took that object already it is unmatched, without a second choice; a removed detection takes
+ *                nothing, so a later one can win an object it lost in the unfiltered pass.  gt, pred (the remaining detections),
+ *                tp, fp, fn, idsw, iou_sum and the per-clip track table (tracks / mt / pt / ml, 0.8 / 0.2) are counted as above;
+ *                clips still open are closed at the end.  t = -infinity reproduces rtk_track_score's counters and iou_sum bit for
+ *                bit (with the open clips closed).
+ *   thresholds   the KITTI walk: the track scores of the true positives of the unfiltered replay, pooled over the streams and
+ *                sorted descending into s[0..n); G the pooled gt count; cur = 0; for i in order: l = (i+1)/G, r = (i+2)/G if
+ *                i < n-1 else l; if (r - cur) < (cur - l) and i < n-1 the i is skipped, otherwise s[i] is the next threshold and
+ *                cur += 1/L.  float64 throughout.  The first threshold (recall 0) is dropped; the k-th remaining one belongs to
+ *                recall level r_k = k/L; levels the walk never reaches contribute 0 to every average.
+ *   per level    MOTA_k = 1 - (FP+FN+IDSW)/G, sMOTA_k = max(0, 1 - (FP+FN+IDSW - (1-r_k) G)/(r_k G)), MOTP_k = iou_sum/TP.
+ *   averages     AMOTA, sAMOTA, AMOTP: the sum over the reached levels divided by L.
+ * The device produces integers and fixed-order IoU sums; every ratio above is host arithmetic in float64 (track_score.py). */
+
+/* Most track ids of one clip of one stream rtk_score_track_means can tell apart (an open-addressed table in LDS). */
+#define RTK_SCORE_SWEEP_TRACKS 2048
+
+/* The per-stream log rtk_track_score_logged appends to: packed, with per-frame offsets.  F frames and R entries per stream bound the
+ * memory; a frame needs one frame slot, P detection records and G kept-label entries (P, G: its clamped counts), and a frame that
+ * does not fit is not logged at all (RTK_SCORE_FLAG_LOG).  Zero-initialised by the caller; only rtk_track_score_logged writes it. */
+typedef struct {
+    int F, R;
+    const float *object_conf;     /* (B,Kobj) this frame's confidences: the only per-call input of the log */
+    int *cursor;                  /* (B,4) frames | detection records | label entries logged so far | unused: the cursors live here */
+    int *frame;                   /* (B,F,4) first record | first label entry | P + 65536 * (the frame began a clip) | G */
+    int *label;                   /* (B,R) kept label ids, frame after frame */
+    int *rec_track, *rec_best;    /* (B,R) per detection, in order: its track id | the label id of its pre-greedy best object, -1 none */
+    float *rec_conf;              /* (B,R) its object_conf */
+    double *rec_iou;              /* (B,R) the IoU with that best object, 0 when none */
+} rtk_score_log_t;
+
+/* rtk_track_score, bit for bit (counters, state, outputs), in the same single launch; every active stream also appends the frame to
+ * its log.  The frame's position is read from log->cursor on the device, so two calls with identical host arguments append two
+ * frames (a captured launch replays correctly).  An inactive stream appends nothing. */
+RTK_EXPORT int rtk_track_score_logged(const rtk_track_score_in_t *in, const rtk_track_score_state_t *state, const rtk_track_score_out_t *out,
+                                      const rtk_score_log_t *log, rtk_stream_t stream);
+
+/* rec_score (B,R) float64: for every logged detection the score of its track.  One workgroup per stream; flags (B) gains
+ * RTK_SCORE_FLAG_SWEEP for a stream with more than RTK_SCORE_SWEEP_TRACKS track ids in a clip. */
+RTK_EXPORT int rtk_score_track_means(int B, const rtk_score_log_t *log, double *rec_score, int *flags, rtk_stream_t stream);
+
+/* The walk: sorted (*n or more) float64 descending, *n true positives, *gt ground-truth objects (device scalars).  thresholds
+ * (levels + 1): [0] = -infinity, [k] the threshold of level k for k <= *reached, +infinity beyond; *reached <= levels. */
+RTK_EXPORT int rtk_score_thresholds(const double *sorted, const long long *n, const long long *gt, int levels, double *thresholds,
+                                    int *reached, rtk_stream_t stream);
+
+/* Grid (stream, threshold index): counters (count,B,11) and iou_sum (count,B) of the replay at thresholds[index]; T as in
+ * rtk_track_score.  reached NULL: every index is replayed; otherwise indices above *reached write zeros.  tp_mask NULL or (B,R)
+ * uint8, written for index 0 only: 1 where the logged detection is a true positive.  One IoU-sum order per (stream, index):
+ * frames in order, detections in order, from 0. */
+RTK_EXPORT int rtk_score_replay(int B, int T, const rtk_score_log_t *log, const double *rec_score, const double *thresholds,
+                                const int *reached, int count, long long *counters, double *iou_sum, unsigned char *tp_mask,
+                                rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,8 @@
 //                     rider merge and the minimum object size (vod_gt.filter_object_points' objs_combined; track4d_utils.py:105-176)
 //   rtk_track_score   one workgroup per stream: vod_gt.map_gt_objects (track4d_utils.py:50-102), the 0/1 target of
 //                     loss.affinity_loss against the stream's previous frame, and the running CLEAR-MOT counts with the per-stream
-//                     table of ground-truth tracks
+//                     table of ground-truth tracks; rtk_track_score_logged is the same launch that also appends the frame to the
+//                     stream's log for the confidence sweep (track_sweep.hip)
 //
 // Layout of both: 256 threads = 4 waves of 64, one stream's tables in LDS (the byte counts are ts_gto_lds / ts_score_lds below).
 //
@@ -226,8 +227,12 @@ static size_t ts_score_lds(int Kobj, int K, int N) {
            ((size_t)2 * N + (size_t)Kobj * K + (size_t)4 * Kobj + (size_t)5 * K + 8) * sizeof(int);
 }
 
-__global__ __launch_bounds__(TS_THREADS) void track_score_kernel(const rtk_track_score_in_t in, const rtk_track_score_state_t st,
-                                                                 const rtk_track_score_out_t out) {
+// The body of both scoring kernels.  LOG: the frame is also appended to the stream's log (rtk_score_log_t) -- thread i writes
+// detection i's record where it finds its pre-greedy best object, thread j the j-th kept label id, thread 0 the frame's slot and the
+// cursors; a frame that does not fit writes nothing and raises RTK_SCORE_FLAG_LOG.  Without LOG `lg` is not read.
+template <bool LOG>
+__device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in, const rtk_track_score_state_t &st,
+                                                 const rtk_track_score_out_t &out, const rtk_score_log_t &lg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ts_smem[];
     const int b = blockIdx.x, t = threadIdx.x, lane = t & (RTK_WAVE - 1), wave = t / RTK_WAVE;
     const int N = in.N, Kobj = in.Kobj, K = in.K, T = in.T, W = (N + 31) / 32;
@@ -255,6 +260,15 @@ __global__ __launch_bounds__(TS_THREADS) void track_score_kernel(const rtk_track
     int used = count_clamp(st.table_used[b], T);
     int prevP = st.prev_count[b], prevG = st.prev_gt[b];
     long long *cnt = st.counters + (size_t)b * RTK_SCORE_COUNTERS;
+    // the stream's cursors, read by every thread before thread 0 moves them (after two barriers at least)
+    int log_f = 0, log_r = 0, log_l = 0;
+    bool log_fits = false;
+    if (LOG) {
+        log_f = lg.cursor[b * 4 + 0];
+        log_r = lg.cursor[b * 4 + 1];
+        log_l = lg.cursor[b * 4 + 2];
+        log_fits = log_f >= 0 && log_f < lg.F && log_r >= 0 && log_r <= lg.R - P && log_l >= 0 && log_l <= lg.R - G;
+    }
 
     if (t < 8) scal[t] = 0;
     for (int i = t; i < Kobj; i += TS_THREADS) {
@@ -341,6 +355,16 @@ __global__ __launch_bounds__(TS_THREADS) void track_score_kernel(const rtk_track
         }
         best[i] = bj;
         best_iou[i] = bi;
+        if (LOG && log_fits) {
+            const size_t r = (size_t)b * lg.R + log_r + i;
+            lg.rec_track[r] = in.object_ids[ob + i];
+            lg.rec_conf[r] = lg.object_conf[ob + i];
+            lg.rec_best[r] = bj >= 0 ? glabel[bj] : -1;
+            lg.rec_iou[r] = bi;
+        }
+    }
+    if (LOG && log_fits) {
+        for (int j = t; j < G; j += TS_THREADS) lg.label[(size_t)b * lg.R + log_l + j] = glabel[j];
     }
     // ---- which table entry holds each kept object's label id ----
     for (int e = t; e < used; e += TS_THREADS) {
@@ -383,6 +407,15 @@ __global__ __launch_bounds__(TS_THREADS) void track_score_kernel(const rtk_track
         st.table_used[b] = used;
         st.iou_sum[b] = iou_sum;
         cnt[0] += 1; cnt[1] += G; cnt[2] += P; cnt[3] += M; cnt[4] += P - M; cnt[5] += G - M; cnt[6] += idsw;
+        if (LOG) {
+            if (log_fits) {
+                int *fr = lg.frame + ((size_t)b * lg.F + log_f) * 4;
+                fr[0] = log_r; fr[1] = log_l; fr[2] = P | (reset ? 65536 : 0); fr[3] = G;
+                lg.cursor[b * 4 + 0] = log_f + 1; lg.cursor[b * 4 + 1] = log_r + P; lg.cursor[b * 4 + 2] = log_l + G;
+            } else {
+                flags |= RTK_SCORE_FLAG_LOG;
+            }
+        }
         if (flags) st.flags[b] |= flags;
         st.prev_count[b] = P;
         st.prev_gt[b] = G;
@@ -406,13 +439,24 @@ __global__ __launch_bounds__(TS_THREADS) void track_score_kernel(const rtk_track
     }
 }
 
+__global__ __launch_bounds__(TS_THREADS) void track_score_kernel(const rtk_track_score_in_t in, const rtk_track_score_state_t st,
+                                                                 const rtk_track_score_out_t out) {
+    track_score_body<false>(in, st, out, rtk_score_log_t{});
+}
+
+// the logged variant: the same body (and the same LDS: the log goes straight to memory)
+__global__ __launch_bounds__(TS_THREADS) void ts_logged_kernel(const rtk_track_score_in_t in, const rtk_track_score_state_t st,
+                                                               const rtk_track_score_out_t out, const rtk_score_log_t lg) {
+    track_score_body<true>(in, st, out, lg);
+}
+
 extern "C" int rtk_track_score_lds_bytes(int Kobj, int K, int N) {
     if (Kobj < 1 || K < 1 || N < 1 || Kobj > RTK_SCORE_MAX_OBJECTS || K > RTK_SCORE_MAX_BOXES || N > RTK_SCORE_MAX_POINTS) return -1;
     return (int)ts_score_lds(Kobj, K, N);
 }
 
-extern "C" int rtk_track_score(const rtk_track_score_in_t *in, const rtk_track_score_state_t *st, const rtk_track_score_out_t *out,
-                               rtk_stream_t stream) {
+static int ts_score_launch(const rtk_track_score_in_t *in, const rtk_track_score_state_t *st, const rtk_track_score_out_t *out,
+                           const rtk_score_log_t *lg, rtk_stream_t stream) {
     RTK_REQUIRE(in && st && out, "track_score: null argument block");
     RTK_REQUIRE(in->B >= 1 && in->B <= 65535 && in->N >= 1 && in->N <= RTK_SCORE_MAX_POINTS && in->T >= 1,
                 "track_score: bad sizes B=%d N=%d T=%d", in->B, in->N, in->T);
@@ -428,8 +472,28 @@ extern "C" int rtk_track_score(const rtk_track_score_in_t *in, const rtk_track_s
                 st->prev_gt_id && st->prev_count && st->prev_gt && st->flags, "track_score: null state");
     RTK_REQUIRE(out->pred_gt_slot && out->pred_gt_id && out->gt_pred && out->iou && out->aff_target && out->aff_defined,
                 "track_score: null output");
+    if (lg) {
+        RTK_REQUIRE(lg->F >= 1 && lg->R >= 1, "track_score_logged: a log of F=%d frames and R=%d records per stream", lg->F, lg->R);
+        RTK_REQUIRE(lg->object_conf && lg->cursor && lg->frame && lg->label && lg->rec_track && lg->rec_best && lg->rec_conf && lg->rec_iou,
+                    "track_score_logged: null log");
+        (void)hipFuncSetAttribute((const void *)ts_logged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RTK_SCORE_LDS_LIMIT);
+        ts_logged_kernel<<<in->B, TS_THREADS, lds, (hipStream_t)stream>>>(*in, *st, *out, *lg);
+        RTK_CHECK_LAUNCH("track_score_logged");
+        return RTK_OK;
+    }
     (void)hipFuncSetAttribute((const void *)track_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RTK_SCORE_LDS_LIMIT);
     track_score_kernel<<<in->B, TS_THREADS, lds, (hipStream_t)stream>>>(*in, *st, *out);
     RTK_CHECK_LAUNCH("track_score");
     return RTK_OK;
+}
+
+extern "C" int rtk_track_score(const rtk_track_score_in_t *in, const rtk_track_score_state_t *st, const rtk_track_score_out_t *out,
+                               rtk_stream_t stream) {
+    return ts_score_launch(in, st, out, nullptr, stream);
+}
+
+extern "C" int rtk_track_score_logged(const rtk_track_score_in_t *in, const rtk_track_score_state_t *st, const rtk_track_score_out_t *out,
+                                      const rtk_score_log_t *lg, rtk_stream_t stream) {
+    RTK_REQUIRE(lg, "track_score_logged: null log block");
+    return ts_score_launch(in, st, out, lg, stream);
 }

@@ -20,11 +20,42 @@ for the stream's detections, plus two things built on that matching:
     many of them were mostly tracked (matched in > 80 % of the frames they were seen in), mostly lost (< 20 %) or partly tracked.
 
 `TrackScorer.result()` turns the counts into mota = 1 - (fn + fp + idsw) / gt, moda = 1 - (fn + fp) / gt, recall, precision, the
-mt / pt / ml fractions of tracks and the mean IoU of the matches.  These are CLEAR-MOT counts UNDER THE REFERENCE'S OWN POINT-IoU
-MATCHING (best IoU, first come first served, no threshold) AT THE TRACKER'S OPERATING POINT.  They are not the sAMOTA / AMOTA table
-of the reference's README: that one comes from a confidence-swept AB3DMOT variant the reference does not distribute.
+mt / pt / ml fractions of tracks and the mean IoU of the matches: CLEAR-MOT counts under the reference's own point-IoU matching
+(best IoU, first come first served, no threshold) at the tracker's operating point.
 
-Nothing here synchronises with the device except `GtObjects.check()`, `TrackScorer.check()` and `TrackScorer.result()`.
+The confidence sweep.  `TrackScorer(..., sweep_frames=F, sweep_records=R)` makes the same launch append every active stream's
+frame to a packed per-stream log on the device (at most F frames, R detection records and R kept-label entries per stream; a frame
+that does not fit is not logged and raises FLAG_LOG), and `scorer.sweep(levels=40)` evaluates sAMOTA / AMOTA / AMOTP over it in a few
+launches and one download:
+
+    scorer = TrackScorer(streams=B, max_objects=trk.K, max_boxes=32, sweep_frames=512, sweep_records=16384)
+    ...    scorer.update(out, gobj, ...)            # out.object_conf is logged with the match
+    sw     = scorer.sweep()                         # SweepResult: amota, samota, amotp, best, per-level arrays
+
+THESE ARE THE SWEEP METRICS OF WENG ET AL. ("3D Multi-Object Tracking: A Baseline and New Evaluation Metrics") APPLIED TO THIS
+MODULE'S MATCHING RULE.  With L recall levels:
+
+  * a clip is a stream's frames from one reset to the next; a track is a (stream, clip, track id), and its score the float64 sum
+    of the fp32 `object_conf` of its logged detections in log order over their number;
+  * the replay at threshold t walks every stream frame by frame without the detections whose track score is < t (equal stays); the
+    others go through `update`'s rule in detection order -- the best object (largest IoU > 0, strict >, against all kept
+    ground-truth objects: independent of the filter); already taken by a remaining detection: unmatched, no second choice; a
+    removed detection takes nothing, so a later one can win an object it lost unfiltered -- and gt, pred, tp, fp, fn, idsw, iou_sum
+    and the per-clip track table are counted as `update` counts them, open clips closed at the end; t = -inf reproduces
+    `counters` / `iou_sum` bit for bit;
+  * the thresholds are the KITTI walk over the track scores s[0..n) of the unfiltered replay's true positives, pooled and sorted
+    descending, G the pooled gt count, cur = 0: for i in order, l = (i+1)/G, r = (i+2)/G if i < n-1 else l; if (r - cur) < (cur - l)
+    and i < n-1, i is skipped; otherwise s[i] is the next threshold and cur += 1/L.  The first (recall 0) is dropped, the k-th
+    remaining one belongs to recall level r_k = k/L; levels the walk never reaches contribute 0 to every average;
+  * MOTA_k = 1 - (FP+FN+IDSW)/G, sMOTA_k = max(0, 1 - (FP+FN+IDSW - (1-r_k) G)/(r_k G)), MOTP_k = iou_sum/TP; AMOTA, sAMOTA, AMOTP
+    are each the sum over the reached levels divided by L; `best` is the level of the largest MOTA_k (the lowest k among equals).
+
+The device delivers integers and fixed-order IoU sums; every ratio is float64 host arithmetic (`sweep_values`).  They are still NOT
+the numbers of the reference's README table: its evaluator (a confidence-swept AB3DMOT variant) is not distributed, and the IoU and
+the thresholds it uses are unknown.
+
+Nothing here synchronises with the device except `GtObjects.check()`, `TrackScorer.check()`, `TrackScorer.result()` and
+`TrackScorer.sweep()`.
 """
 import ctypes
 
@@ -32,7 +63,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .abi import GtBoxes, GtObjectsIn, GtObjectsOut, ScoreIn, ScoreOut, ScoreState, stream as _stream, view as _view
+from .abi import GtBoxes, GtObjectsIn, GtObjectsOut, ScoreIn, ScoreLog, ScoreOut, ScoreState, stream as _stream, view as _view
 from .gt_device import _flag_bytes, _n_valid
 
 LDS_LIMIT = 65536                      # RTK_SCORE_LDS_LIMIT
@@ -41,6 +72,8 @@ MAX_OBJECTS = 256                      # RTK_SCORE_MAX_OBJECTS
 MAX_POINTS = 32768                     # RTK_SCORE_MAX_POINTS
 COUNTERS = ("frames", "gt", "pred", "tp", "fp", "fn", "idsw", "tracks", "mt", "pt", "ml")
 FLAG_BOXES, FLAG_NVALID, FLAG_TRACKS, FLAG_OBJECTS = 1, 2, 4, 8
+FLAG_LOG, FLAG_SWEEP = 16, 32          # RTK_SCORE_FLAG_LOG, RTK_SCORE_FLAG_SWEEP
+SWEEP_TRACKS = 2048                    # RTK_SCORE_SWEEP_TRACKS
 
 
 # ---- what fits -------------------------------------------------------------------------------------------------------------
@@ -168,17 +201,100 @@ def classify_tracks(seen, matched):
     return mt, len(r) - mt - ml, ml
 
 
+class SweepResult:
+    """What `TrackScorer.sweep` returns (host values; see the module docstring for the definitions).  `levels` L; `reached`, the
+    number of recall levels the walk reached; `thresholds` (L+1) float64: [0] = -inf (the unfiltered replay), [k] the threshold of
+    level k, +inf past `reached`.  Per-level arrays of length L+1, index k = recall level k (index 0: unfiltered, levels past
+    `reached`: 0 for counts, NaN for ratios): tp, fp, fn, idsw, gt, pred, tracks, mt, pt, ml (pooled over the streams) and mota,
+    smota (NaN at index 0), motp, moda, recall, precision.  amota, samota, amotp.  `best`: dict of the level of the largest MOTA
+    (level, threshold, mota, moda, recall, precision, mt_fraction, pt_fraction, ml_fraction and the raw counts), None when no level
+    was reached.  `unfiltered`: the pooled index-0 counts and iou_sum.  `counters` (L+1,B,11) int64 and `iou_sums` (L+1,B) float64 per
+    stream; `flags` (B)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def sweep_values(counters, iou_sums, thresholds, reached, levels):
+    """The sweep's arithmetic, host only: counters (levels+1,B,11) integer counts in COUNTERS order and iou_sums (levels+1,B)
+    float64 of the replays (index 0: unfiltered, index k: recall level k), thresholds (levels+1), reached -> dict with the fields of
+    `SweepResult` except flags.  Counts are pooled over the streams (the IoU sums added in stream order); float64 throughout.  A
+    reached level without a true positive has MOTP NaN and adds nothing to AMOTP (the divisor stays `levels`); AMOTA and sAMOTA take
+    every reached level."""
+    L, reached = int(levels), int(reached)
+    c = np.asarray(counters, dtype=np.int64).reshape(L + 1, -1, len(COUNTERS))
+    q = np.asarray(iou_sums, dtype=np.float64).reshape(L + 1, -1)
+    if not 0 <= reached <= L:
+        raise ValueError("reached=%d outside [0, levels=%d]" % (reached, L))
+    pooled = c.sum(axis=1)
+    iou = np.cumsum(q, axis=1)[:, -1] if q.shape[1] else np.zeros(L + 1)          # cumsum: one addition after the other
+    live = np.arange(L + 1) <= reached
+    pooled[~live] = 0
+    iou = np.where(live, iou, 0.0)
+    g = lambda k: pooled[:, COUNTERS.index(k)].astype(np.float64)
+    G, err = g("gt"), g("fp") + g("fn") + g("idsw")
+    rk = np.arange(L + 1, dtype=np.float64) / float(L)
+    nan = np.full(L + 1, np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mota = np.where(live, 1.0 - err / G, nan)
+        moda = np.where(live, 1.0 - (g("fp") + g("fn")) / G, nan)
+        smota = np.where(live, np.maximum(0.0, 1.0 - (err - (1.0 - rk) * G) / (rk * G)), nan)
+        smota[0] = np.nan
+        motp = np.where(live, iou / g("tp"), nan)
+        recall, precision = np.where(live, g("tp") / G, nan), np.where(live, g("tp") / g("pred"), nan)
+    amota = samota = amotp = 0.0
+    for k in range(1, reached + 1):                                                  # in level order: fixed bits
+        amota += mota[k]
+        samota += smota[k]
+        if pooled[k, COUNTERS.index("tp")] > 0:
+            amotp += motp[k]
+    out = dict(levels=L, reached=reached, thresholds=np.asarray(thresholds, dtype=np.float64).copy(), counters=c, iou_sums=q,
+               mota=mota, smota=smota, motp=motp, moda=moda, recall=recall, precision=precision, iou_sum=iou,
+               amota=amota / L, samota=samota / L, amotp=amotp / L)
+    for k in COUNTERS[1:]:
+        out[k] = pooled[:, COUNTERS.index(k)].copy()
+    counts = lambda k: dict({n: int(pooled[k, i]) for i, n in enumerate(COUNTERS)}, iou_sum=float(iou[k]))
+    out["unfiltered"] = counts(0)
+    best = None
+    for k in range(1, reached + 1):
+        if best is None or mota[k] > mota[best]:                                    # strict >: the lowest level among equals
+            best = k
+    if best is not None:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tr = np.float64(pooled[best, COUNTERS.index("tracks")])
+            frac = {n + "_fraction": float(np.float64(pooled[best, COUNTERS.index(n)]) / tr) for n in ("mt", "pt", "ml")}
+        best = dict(counts(best), level=best, threshold=float(out["thresholds"][best]), mota=float(mota[best]), moda=float(moda[best]),
+                    smota=float(smota[best]), motp=float(motp[best]), recall=float(recall[best]), precision=float(precision[best]), **frac)
+    out["best"] = best
+    return out
+
+
 class TrackScorer:
     """Matches the detections of `streams` sequences to their ground-truth objects frame by frame and keeps the score on the device
     (see the module docstring).  State (device tensors): counters (B,11) int64 in COUNTERS order, iou_sum (B) float64, the table of
     open ground-truth tracks (table_key / table_last / table_seen / table_matched (B,max_gt_tracks) int32, table_used (B)), the
     previous active frame's record (prev_gt_id (B,Kobj), prev_count, prev_gt (B)) and sticky flags (B).  Whether the tables fit
-    also depends on the clouds' size: `update` checks that (`check_fit`)."""
+    also depends on the clouds' size: `update` checks that (`check_fit`).
 
-    def __init__(self, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, device="cuda"):
+    sweep_frames, sweep_records: both None (today's object and launch), or both given: `update` / `update_raw` then also append
+    every active stream's frame to its log for `sweep` -- at most sweep_frames frames, sweep_records detection records and
+    sweep_records kept-label entries per stream, about 24 bytes per record.  The log (device tensors, all cursors included):
+    log_cursor (B,4) int32 frames | records | label entries logged; log_frame (B,F,4) int32 first record | first label entry |
+    detections + 65536 * began a clip | kept objects; log_label (B,R); log_track, log_best (B,R) int32, log_conf (B,R) fp32,
+    log_iou (B,R) float64."""
+
+    def __init__(self, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, device="cuda", sweep_frames=None, sweep_records=None):
         self.B, self.Kobj, self.K, self.T = int(streams), int(max_objects), int(max_boxes), int(max_gt_tracks)
         if self.T < 1:
             raise ValueError("max_gt_tracks=%d must be at least 1" % self.T)
+        if (sweep_frames is None) != (sweep_records is None):
+            raise ValueError("TrackScorer: sweep_frames=%r and sweep_records=%r must be given together" % (sweep_frames, sweep_records))
+        self.logging = sweep_frames is not None
+        if self.logging:
+            self.F, self.R = int(sweep_frames), int(sweep_records)
+            if self.F < 1 or self.R < 1 or self.B * max(self.F * 4, self.R) >= 2 ** 31:
+                raise ValueError("TrackScorer: sweep_frames=%d, sweep_records=%d must be at least 1 (and the log below 2^31 entries)"
+                                 % (self.F, self.R))
         check_fit(self.K, 1, self.Kobj)
         B, z = self.B, lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
         self.counters = torch.zeros(B, len(COUNTERS), dtype=torch.int64, device=device)
@@ -187,19 +303,29 @@ class TrackScorer:
         self.table_used, self.prev_gt, self.flags = z(B), z(B), z(B)
         self.prev_gt_id = torch.full((B, self.Kobj), -1, dtype=torch.int32, device=device)
         self.prev_count = torch.full((B,), -1, dtype=torch.int32, device=device)
+        if self.logging:
+            self.log_cursor, self.log_frame = z(B, 4), z(B, self.F, 4)
+            self.log_label, self.log_track, self.log_best = z(B, self.R), z(B, self.R), z(B, self.R)
+            self.log_conf = torch.zeros(B, self.R, dtype=torch.float32, device=device)
+            self.log_iou = torch.zeros(B, self.R, dtype=torch.float64, device=device)
+
+    def _log_block(self, object_conf=None):
+        return ScoreLog(self.F, self.R, object_conf, self.log_cursor.data_ptr(), self.log_frame.data_ptr(), self.log_label.data_ptr(),
+                        self.log_track.data_ptr(), self.log_best.data_ptr(), self.log_conf.data_ptr(), self.log_iou.data_ptr())
 
     def update(self, out, gobj, reset=None, active=None):
         """out: a `tracker.StepResult`; gobj: the GtObjects of the same frame (its n_valid is used).  active None: the mask the step
-        ran with.  One launch, no synchronisation.  -> MatchResult."""
+        ran with.  With logging on, out.object_conf is logged.  One launch, no synchronisation.  -> MatchResult."""
         if out.max_objects != self.Kobj:
             raise ValueError("TrackScorer(max_objects=%d) against a step with max_objects=%d" % (self.Kobj, out.max_objects))
         return self.update_raw(out.pc1, out.obj, out.num_objects, out.object_ids, gobj, gobj.n_valid, reset,
-                               out.active if active is None else active)
+                               out.active if active is None else active, object_conf=out.object_conf if self.logging else None)
 
-    def update_raw(self, pc1, obj, num_objects, object_ids, gobj, n_valid=None, reset=None, active=None):
+    def update_raw(self, pc1, obj, num_objects, object_ids, gobj, n_valid=None, reset=None, active=None, object_conf=None):
         """pc1 (B,3,N) fp32 of any strides; obj (B,N) int32, the detection each point belongs to (-1 none; detections are numbered in
         association order); num_objects (B) int32; object_ids (B,Kobj) int32 track ids; gobj from `gt_objects` on the same cloud;
-        n_valid (B) / (2,B) / None; reset, active (B) masks or None."""
+        n_valid (B) / (2,B) / None; reset, active (B) masks or None; object_conf (B,Kobj) fp32, the confidence of each detection:
+        required when the scorer logs for `sweep`, ignored otherwise."""
         B, C, N = pc1.shape
         if B != self.B or C != 3 or tuple(obj.shape) != (B, N) or tuple(object_ids.shape) != (B, self.Kobj) or num_objects.numel() != B:
             raise ValueError("TrackScorer(streams=%d, max_objects=%d): got pc1 %s, obj %s, object_ids %s"
@@ -209,6 +335,11 @@ class TrackScorer:
                              % (self.K, gobj.max_boxes, gobj.points, N))
         check_fit(self.K, N, self.Kobj)
         dev = pc1.device
+        if self.logging:
+            if object_conf is None or tuple(object_conf.shape) != (B, self.Kobj):
+                raise ValueError("TrackScorer(sweep_frames=%d, sweep_records=%d) logs for the sweep: update_raw needs object_conf (%d,%d), got %s"
+                                 % (self.F, self.R, B, self.Kobj, None if object_conf is None else tuple(object_conf.shape)))
+            object_conf = object_conf.to(device=dev, dtype=torch.float32).contiguous()
         as32 = lambda x: x.to(device=dev, dtype=torch.int32).contiguous()
         obj, num_objects, object_ids = as32(obj), as32(num_objects), as32(object_ids)
         nv, rst, act = _nv_row(n_valid, B, dev), _flag_bytes(reset, B, dev), _flag_bytes(active, B, dev)
@@ -227,7 +358,11 @@ class TrackScorer:
                        self.prev_count.data_ptr(), self.prev_gt.data_ptr(), self.flags.data_ptr())
         o = ScoreOut(pred_gt_slot.data_ptr(), pred_gt_id.data_ptr(), gt_pred.data_ptr(), iou.data_ptr(), aff_target.data_ptr(),
                      aff_defined.data_ptr())
-        _lib.call("rtk_track_score", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), _stream())
+        if self.logging:
+            lg = self._log_block(object_conf.data_ptr())
+            _lib.call("rtk_track_score_logged", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), ctypes.addressof(lg), _stream())
+        else:
+            _lib.call("rtk_track_score", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), _stream())
         return MatchResult(pred_gt_slot=pred_gt_slot, pred_gt_id=pred_gt_id, gt_pred=gt_pred, iou=iou, aff_target=aff_target,
                            aff_defined=aff_defined)
 
@@ -240,6 +375,11 @@ class TrackScorer:
                 raise RuntimeError("TrackScorer: stream %d has an n_valid outside [0, N]" % b)
             if f & FLAG_OBJECTS:
                 raise RuntimeError("TrackScorer: stream %d has a num_objects outside [0, max_objects=%d]" % (b, self.Kobj))
+            if f & FLAG_LOG:
+                raise RuntimeError("TrackScorer: stream %d has a frame that did not fit its log of sweep_frames=%d frames and "
+                                   "sweep_records=%d records and was not logged (raise them)" % (b, self.F, self.R))
+            if f & FLAG_SWEEP:
+                raise RuntimeError("TrackScorer.sweep: stream %d has more than %d track ids in one clip" % (b, SWEEP_TRACKS))
 
     def check(self):
         """Synchronises.  Raises RuntimeError naming the stream whose track table overflowed or whose sizes were out of range."""
@@ -276,3 +416,45 @@ class TrackScorer:
         overall["iou_sum"] = total_iou
         overall.update({k: float(v) for k, v in values_from_counters(total, total_iou).items()})
         return dict(per_stream=per, overall=overall, flags=flags.copy())
+
+    def sweep(self, levels=40, check=True):
+        """sAMOTA / AMOTA / AMOTP over the log (module docstring): track scores, the unfiltered replay, a sort of the true
+        positives' scores, the threshold walk and the replay at every threshold on the device -- five launches of this library plus
+        torch's sort -- then one download.  The running state and the log are only read: scoring may go on.  check: raise (naming the
+        stream) on any sticky flag, a frame that did not fit the log among them.  -> SweepResult."""
+        if not self.logging:
+            raise RuntimeError("TrackScorer.sweep: the scorer keeps no log (give sweep_frames and sweep_records)")
+        L = int(levels)
+        if not 1 <= L <= 65534:
+            raise ValueError("levels=%d outside [1, 65534]" % L)
+        B, dev, nc = self.B, self.counters.device, len(COUNTERS)
+        lg = self._log_block()
+        lgp, st = ctypes.addressof(lg), _stream()
+        score = torch.zeros(B, self.R, dtype=torch.float64, device=dev)
+        flags = self.flags.clone()
+        _lib.call("rtk_score_track_means", B, lgp, score.data_ptr(), flags.data_ptr(), st)
+        c0 = torch.empty(1, B, nc, dtype=torch.int64, device=dev)
+        q0 = torch.empty(1, B, dtype=torch.float64, device=dev)
+        mask = torch.zeros(B, self.R, dtype=torch.uint8, device=dev)
+        minus = torch.full((1,), float("-inf"), dtype=torch.float64, device=dev)
+        _lib.call("rtk_score_replay", B, self.T, lgp, score.data_ptr(), minus.data_ptr(), None, 1, c0.data_ptr(), q0.data_ptr(),
+                  mask.data_ptr(), st)
+        ordered = torch.where(mask.bool(), score, minus).reshape(-1).sort(descending=True).values
+        n, gt = mask.sum(dtype=torch.int64).reshape(1), c0[0, :, COUNTERS.index("gt")].sum().reshape(1)
+        thr = torch.empty(L + 1, dtype=torch.float64, device=dev)
+        reached = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.call("rtk_score_thresholds", ordered.data_ptr(), n.data_ptr(), gt.data_ptr(), L, thr.data_ptr(), reached.data_ptr(), st)
+        c = torch.empty(L + 1, B, nc, dtype=torch.int64, device=dev)
+        q = torch.empty(L + 1, B, dtype=torch.float64, device=dev)
+        _lib.call("rtk_score_replay", B, self.T, lgp, score.data_ptr(), thr.data_ptr(), reached.data_ptr(), L + 1, c.data_ptr(), q.data_ptr(),
+                  None, st)
+        host = torch.cat([c.reshape(-1), q.reshape(-1).view(torch.int64), thr.view(torch.int64), reached.long(), flags.long()]).cpu().numpy()
+        o = (L + 1) * B * nc
+        counters = host[:o].reshape(L + 1, B, nc).copy()
+        iou_sums = host[o:o + (L + 1) * B].copy().view(np.float64).reshape(L + 1, B)
+        o += (L + 1) * B
+        thresholds = host[o:o + L + 1].copy().view(np.float64)
+        k, fl = int(host[o + L + 1]), host[o + L + 2:].copy()
+        if check:
+            self._raise_on_flags(fl.tolist())
+        return SweepResult(flags=fl, **sweep_values(counters, iou_sums, thresholds, k, L))
