@@ -22,13 +22,12 @@ from ratrack_amd import _lib
 from ratrack_amd import pointnet2_utils as PU
 from ratrack_amd import train_ops as T
 
-from _stage_f64 import _gather, patch_cost_f64
+from _stage_f64 import MARGIN, clear_of_zero, margin, patch_cost_f64
 from _util import reference_state_dict
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 NAMES = ["out", "dfeat", "dwa", "dba", "dwb", "dbb", "dwc", "dbc"]
-MARGIN = 1e-4
 XYZ_SCALE = 1e-3
 
 
@@ -79,34 +78,6 @@ class Case:
         return idx
 
 
-def margin(xyz, knn, wn):
-    """min over the three layers of (smallest |pre-activation|) / (largest |pre-activation| of the layer)."""
-    h = _gather(xyz, knn) - xyz[:, :, None, :]
-    worst = float("inf")
-    for W, b in wn:
-        z = h @ W.T + b
-        worst = min(worst, float(z.abs().min() / z.abs().max()))
-        h = torch.relu(z)
-    return worst
-
-
-def clear_of_zero(xyz, knn, wn):
-    """-> (keep (B, n, 256) bool, number of channels of the three layers whose sign changes between positions).  keep[b, i, c]: no
-    pre-activation that the gradient of out[b, i, c] passes through lies within MARGIN of its layer's largest magnitude of zero --
-    none of the 16 hidden ones at any of query i's 16 positions, nor output channel c at any of them."""
-    h = _gather(xyz, knn) - xyz[:, :, None, :]
-    keep, mixed = None, 0
-    for li, (W, b) in enumerate(wn):
-        z = h @ W.T + b                                            # (B, n, 16, C)
-        near = z.abs() < MARGIN * z.abs().max()
-        on = (z > 0).reshape(-1, z.shape[-1]).double().mean(0)
-        mixed += int(((on > 0.02) & (on < 0.98)).sum())
-        k = ~near.any(2) if li == 2 else ~near.any(3).any(2)[:, :, None]
-        keep = k if keep is None else keep & k
-        h = torch.relu(z)
-    return keep, mixed
-
-
 def reference(case, knn, dtype, device):
     """[out, dfeat, dwa, dba, dwb, dbb, dwc, dbc] of patch_cost_f64 under autograd in `dtype`: the same (padded) tensors, the same table."""
     B, n = case.B, case.n
@@ -153,7 +124,8 @@ def test_patch_cost_backward_matches_float64_autograd(name, B, n, seed, twice, l
     case = Case(B, n, seed, twice=twice, live=live)
     knn = case.knn_device()
     wn64 = weightnet2(DEV, torch.float64)
-    m = margin(case.xyz.to(DEV).double(), knn, wn64)
+    x64 = case.xyz.to(DEV).double()
+    m = margin(x64, x64, knn, wn64)
     print("\n%s: smallest |pre-activation| / layer maximum in float64: %.2e" % (name, m))
     assert m >= MARGIN, "a WeightNet pre-activation within %.0e of zero (%.2e): choose another seed" % (MARGIN, m)
     if limit is not None:
@@ -197,7 +169,8 @@ def test_patch_cost_backward_with_masks_that_vary_by_position(name, B, n, seed, 
     and dfeat are continuous in the pre-activations and keep every entry.  Same bound."""
     case = Case(B, n, seed, twice=twice, live=live, scale=1.0)
     knn = case.knn_device()
-    keep, mixed = clear_of_zero(case.xyz.to(DEV).double(), knn, weightnet2(DEV, torch.float64))
+    x64 = case.xyz.to(DEV).double()
+    keep, mixed = clear_of_zero(x64, x64, knn, weightnet2(DEV, torch.float64))
     kept = float(keep.double().mean())
     print("\n%s: %.1f %% of the cotangent kept, %d of 272 channels change sign between positions" % (name, 100 * kept, mixed))
     assert kept >= 0.5 and mixed >= 136, (kept, mixed)

@@ -10,7 +10,8 @@ from ratrack_amd import model_utils as MU
 from ratrack_amd import pointnet2_utils as PU
 from ratrack_amd.pointnet2_modules import PointnetSAModuleMSG
 
-from _stage_f64 import cost_volume_f64, patch_cost_f64, sa_scale_f64
+from _cost_volume_cases import CASES as CV_CASES, LOOPING as CV_LOOPING, band_share, case_by_name, parameters, tiles_per_workgroup
+from _stage_f64 import MARGIN, _gather, clear_of_zero, cost_volume_f64, decode_sign_masks, margin, patch_cost_f64, sa_scale_f64, weight_net
 
 
 def _group_f64(features, idx):
@@ -129,3 +130,104 @@ def test_cost_volume_and_patch_cost_restatements_match_the_module(B, N, monkeypa
     got = patch_cost_f64(x1, k11, cv, wn2)
     assert ref.abs().max() > 0
     torch.testing.assert_close(got, ref, rtol=1e-12, atol=1e-12 * float(ref.abs().max()))
+
+
+# ---- what tests/test_cost_volume_bwd_gpu.py stands on ---------------------------------------------------------------------------
+def _cv_small(dtype, seed=8):
+    gen = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.randn(*s, generator=gen, dtype=torch.float64).to(dtype)
+    B, n1, n2 = 2, 9, 21
+    knn = torch.randint(0, n2, (B, n1, 16), generator=gen)
+    layers = [(r(256, 256) * 0.06, r(256) * 0.1), (r(256, 256) * 0.06, r(256) * 0.1)]
+    wn = [(r(8, 3), r(8)), (r(8, 8) * 0.4, r(8)), (r(256, 8) * 0.4, r(256))]
+    return r(B, n1, 3), r(B, n2, 3), knn, r(B, n1, 256), r(B, n2, 256), r(256, 3) * 0.3, layers, wn
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_cost_volume_restatement_with_given_decisions(dtype):
+    """decisions=None is the function as it was (restated here), bit for bit; so is decisions = [z > 0] of its own activations, whose
+    product with the slope is leaky_relu's; and a flipped decision takes the other slope."""
+    xyz1, xyz2, knn, p1, p2, wd, layers, wn = args = _cv_small(dtype)
+    lk = lambda t: torch.nn.functional.leaky_relu(t, 0.1)
+    d = _gather(xyz2, knn) - xyz1[:, :, None, :]
+    x = lk(p1[:, :, None, :] + _gather(p2, knn) + d @ wd.T)
+    for W, b in layers:
+        x = lk(x @ W.T + b)
+    old = (weight_net(d, wn) * x).sum(2)
+    assert torch.equal(cost_volume_f64(*args), old)
+    out, acts = cost_volume_f64(*args, with_acts=True)
+    assert torch.equal(out, old) and torch.equal(acts[2], x) and all(a.shape == (2, 9, 16, 256) for a in acts)
+    dec = [a > 0 for a in acts]
+    assert all(0.2 < float(m.double().mean()) < 0.8 for m in dec)
+    out2, acts2 = cost_volume_f64(*args, decisions=dec, with_acts=True)
+    assert torch.equal(out2, old) and all(torch.equal(a, b) for a, b in zip(acts, acts2))
+    flipped = [dec[0], dec[1], ~dec[2]]
+    _, acts3 = cost_volume_f64(*args, decisions=flipped, with_acts=True)
+    neg = ~dec[2]
+    torch.testing.assert_close(acts3[2][neg], acts[2][neg] * 10, rtol=1e-6, atol=0)
+    torch.testing.assert_close(acts3[2][dec[2]], acts[2][dec[2]] * 0.1, rtol=1e-6, atol=0)
+
+
+def test_sign_mask_decoder_inverts_a_literal_encoder():
+    """Bit 4v + r of word (position, g) <-> channel 16v + 4g + r, bit 63 included (the words are signed)."""
+    gen = torch.Generator().manual_seed(1)
+    M = 37
+    want = torch.rand(M, 256, generator=gen) < 0.5
+    want[0], want[1] = True, False
+    want[2] = False
+    want[2, 16 * 15 + 4 * 2 + 3] = True                                       # bit 63 of word 2 alone
+    words = torch.zeros(M, 4, dtype=torch.int64)
+    for m in range(M):
+        for g in range(4):
+            w = 0
+            for v in range(16):
+                for r in range(4):
+                    if want[m, 16 * v + 4 * g + r]:
+                        w |= 1 << (4 * v + r)
+            words[m, g] = w - (1 << 64) if w >= 1 << 63 else w
+    assert int(words[2, 2]) == -(1 << 63) and int(words[0, 0]) == -1
+    assert torch.equal(decode_sign_masks(words), want)
+
+
+def test_margin_helpers_on_one_cloud_and_two():
+    """margin / clear_of_zero take the directions xyz2[knn] - xyz1: one cloud given twice is the patch cost's case."""
+    gen = torch.Generator().manual_seed(3)
+    x1, x2 = torch.randn(2, 20, 3, generator=gen, dtype=torch.float64), torch.randn(2, 30, 3, generator=gen, dtype=torch.float64)
+    knn = torch.randint(0, 30, (2, 20, 16), generator=gen)
+    wn = [(torch.randn(8, 3, generator=gen, dtype=torch.float64), torch.randn(8, generator=gen, dtype=torch.float64)),
+          (torch.randn(8, 8, generator=gen, dtype=torch.float64), torch.randn(8, generator=gen, dtype=torch.float64)),
+          (torch.randn(256, 8, generator=gen, dtype=torch.float64), torch.randn(256, generator=gen, dtype=torch.float64))]
+    d = _gather(x2, knn) - x1[:, :, None, :]
+    z = [d @ wn[0][0].T + wn[0][1]]
+    z.append(torch.relu(z[0]) @ wn[1][0].T + wn[1][1])
+    z.append(torch.relu(z[1]) @ wn[2][0].T + wn[2][1])
+    assert margin(x1, x2, knn, wn) == min(float(t.abs().min() / t.abs().max()) for t in z)
+    keep, mixed = clear_of_zero(x1, x2, knn, wn)
+    near = [t.abs() < MARGIN * t.abs().max() for t in z]
+    want = ~(near[0].any(3).any(2) | near[1].any(3).any(2))[:, :, None] & ~near[2].any(2)
+    assert keep.shape == (2, 20, 256) and torch.equal(keep, want) and 0 < mixed <= 272
+
+
+@pytest.mark.parametrize("name", [c[0] for c in CV_CASES])
+def test_cost_volume_backward_cases_meet_their_conditions(name):
+    """What tests/test_cost_volume_bwd_gpu.py requires of a case's inputs and the float64 reference alone decides, on the host's
+    neighbour table: at least half of the cotangent clear of a WeightNet decision, at least 136 of the 272 WeightNet channels changing
+    sign between positions, at most 1e-3 of the leaky-ReLU pre-activations within the forward's bound of zero, and for the looping
+    shapes more than one tile per workgroup with the last query of some sample keeping part of its cotangent."""
+    case = case_by_name(name)
+    knn = case.knn_host()
+    assert knn.shape == (case.B, case.n1, 16) and int(knn.max()) < case.n2
+    if case.live is not None:
+        assert all(int(knn[b].max()) < v for b, v in enumerate(case.live))
+    par = parameters("cpu", torch.float64)
+    keep, mixed = case.keep_mask(knn, par)
+    kept = float(keep.double().mean())
+    _, acts, _ = case.reference(knn, par, torch.float64, "cpu", grads=False)
+    share = band_share(acts)
+    print("\n%s: kept %.3f, mixed %d, band share %.1e" % (name, kept, mixed, share))
+    assert kept >= 0.5 and mixed >= 136 and share <= 1e-3, (kept, mixed, share)
+    if name in CV_LOOPING:
+        for kernel, (tiles, wgs) in tiles_per_workgroup(case.B, case.n1).items():
+            assert tiles > wgs, (kernel, tiles, wgs)
+        assert case.n1 % 8 != 0 and case.n1 % 4 != 0
+        assert keep.view(case.B, case.n1, 256)[:, -1].any(1).any()

@@ -16,6 +16,7 @@ from ratrack_amd import synth
 from ratrack_amd.track4d import Args, Track4D
 from ratrack_amd.train_ops import bn_relu
 
+from _stage_f64 import decode_sign_masks
 from _util import reference_state_dict, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -878,10 +879,7 @@ def test_cost_volume_train_forward_keeps_what_the_backward_needs(B, N, split, mo
     a1 = torch.nn.functional.leaky_relu(p1.repeat_interleave(16, 0) + p2[nbr] + dvec @ r_wd(W, DEV).t(), 0.1)
     assert float((acts[0] - a1).abs().max()) <= 1e-4 * float(a1.abs().max())
     for a, m in ((acts[0], masks[0]), (acts[1], masks[1])):
-        words = m.view(M, 4, 1)                                                    # (position, g): 64 bits
-        bits = (words >> torch.arange(64, device=DEV).view(1, 1, 64)) & 1          # bit 4v + r
-        got = bits.view(M, 4, 16, 4).permute(0, 2, 1, 3).reshape(M, 256).bool()    # channel 16v + 4g + r
-        assert torch.equal(got, a > 0)
+        assert torch.equal(decode_sign_masks(m), a > 0)
 
 
 def r_wd(W, dev):
