@@ -400,6 +400,33 @@ RTK_EXPORT int rtk_associate_batched(int B, int N, int K, const unsigned char *a
                                      int iters, int *counter, int *ids, int *count, int *object_ids, float *object_conf, int *indices1,
                                      int *num_prev, int *point_track_id, float *scores, rtk_stream_t stream);
 
+/* rtk_track_memory: track memory (a lost track coasts for up to max_age frames) -- the state advance of a tracker that keeps lost
+ * tracks, issued after rtk_associate_batched on the same stream.  The table of a stream (ids, desc, age, hits, its row count `count`,
+ * and n_det = how many of its leading rows are the last active frame's detections; the rows after them are coasted tracks) is
+ * double-buffered: prev_* is read, the others are written.  rtk_object_descriptors and rtk_associate_batched have already written
+ * desc / ids of the current rows j < n_b = num_objects[b]; m_b is the number of previous rows (prev_count[b]; 0 on a reset stream).
+ *   matched    previous row i < m_b is matched iff some j < n_b has indices1[b][j] == i and object_conf[b][j] != 0 (object j
+ *              inherited that row's ID; mutual-best gives at most one such j).
+ *   current    rows j < n_b: age = 0, hits = prev_hits[i] + 1 when inherited from row i, else 1; n_det = n_b.
+ *   survivors  the previous rows i < m_b that are not matched and have prev_age[i] + 1 <= max_age, in increasing i: the s-th becomes
+ *              row n_b + s when n_b + s < K -- ids and the 141 descriptor floats copied bit for bit (no motion model: a coasted
+ *              track holds its last descriptor), age = prev_age[i] + 1, hits = prev_hits[i].
+ *   count      min(K, n_b + S), S the number of survivors.  Survivors that do not fit are dropped, the last in table order first,
+ *              and bit 2 (value 4) of flags[b] is set.  Rows past count: ids = -1, age = 0, hits = 0.
+ *   reset      the previous table is ignored: no survivors, every current row has hits = 1.
+ *   inactive   ids, age, hits, n_det, count equal the previous table's (ids and count by rtk_associate_batched, the descriptors by
+ *              rtk_object_descriptors): a track does not age while its stream sits a frame out.
+ *   An active frame with n_b = 0 ages every previous row.
+ * Per-step outputs: object_hits (B,K) = hits of current object j (0 past n_b); object_gap (B,K) = prev_age of the row object j
+ * inherited from (0: seen last frame, g: re-acquired after g missed frames; -1: fresh ID or past n_b); num_coasted (B) = count - n_det
+ * of the new table (= count - n_b on an active stream).
+ * active / reset may be NULL (all active / none reset).  One workgroup per stream, plain stores only: every run gives the same bits. */
+RTK_EXPORT int rtk_track_memory(int B, int K, int max_age, const unsigned char *active, const unsigned char *reset,
+                                const int *num_objects, const int *indices1, const float *object_conf, const int *prev_ids,
+                                const int *prev_age, const int *prev_hits, const int *prev_n_det, const int *prev_count,
+                                const float *desc_prev, int *ids, int *age, int *hits, int *n_det, int *count, float *desc, int *flags,
+                                int *object_hits, int *object_gap, int *num_coasted, rtk_stream_t stream);
+
 /* The largest K (max_objects) the batched association accepts: its per-stream table must fit one workgroup's LDS. */
 RTK_EXPORT int rtk_track_max_objects(void);
 

@@ -1,5 +1,6 @@
 // track_batched.hip -- the post-backbone half of Track4D.forward (detection + association, models/track4d.py:53-65,108-223) for B
-// independent streams at once: four launches per frame whatever B is, no host round trip (ratrack_amd/tracker.py).
+// independent streams at once: four launches per frame whatever B is, no host round trip (ratrack_amd/tracker.py); a fifth when
+// the tracker keeps lost tracks (max_age).
 //
 //   rtk_dbscan_batched      one workgroup per stream: mover selection + DBSCAN (dbscan_workgroup, rtk_dbscan's) + the objects'
 //                           reference order (by first member point)
@@ -7,6 +8,8 @@
 //   rtk_affinity_pairs      (stream, pair-tile) workgroups: the Affinity MLP on the live m_b x n_b descriptor differences
 //   rtk_associate_batched   one workgroup per stream: log-Sinkhorn (log_ot_lds, rtk_log_sinkhorn's), mutual best match,
 //                           track IDs, point_track_id
+//   rtk_track_memory        one workgroup per stream: the next table = this frame's detections + the unmatched previous rows that
+//                           are still young enough, compacted in table order
 //
 // The DBSCAN and log-OT code lives in assoc_common.h, shared with the B = 1 kernels of fused_misc.hip.
 //
@@ -424,5 +427,97 @@ extern "C" int rtk_associate_batched(int B, int N, int K, const unsigned char *a
     (void)hipFuncSetAttribute((const void *)associate_batched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)assoc_lds_bytes(K));
     associate_batched_kernel<<<B, 256, assoc_lds_bytes(K), (hipStream_t)stream>>>(a);
     RTK_CHECK_LAUNCH("associate_batched");
+    return RTK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// rtk_track_memory: one workgroup per stream, thread t = row t of the tables (K <= 256).  The rules are stated once, in rtk_fused.h.
+// The matched mask of the previous rows comes from indices1 / object_conf; a survivor's position is its rank among the survivors
+// (ordered_slot: ballot + prefix over the four waves); the descriptor rows then move element by element, consecutive threads on
+// consecutive floats.  Plain stores to rows that no other thread writes: nothing depends on the order of execution.
+// ------------------------------------------------------------------------------------------------
+struct MemArgs {
+    int K, max_age;
+    const unsigned char *active, *reset;
+    const int *num_objects, *indices1;
+    const float *object_conf;
+    const int *prev_ids, *prev_age, *prev_hits, *prev_n_det, *prev_count;
+    const float *desc_prev;
+    int *ids, *age, *hits, *n_det, *count;
+    float *desc;
+    int *flags, *object_hits, *object_gap, *num_coasted;
+};
+
+__global__ __launch_bounds__(256) void track_memory_kernel(const MemArgs a) {
+    __shared__ int s_wave[4], s_matched[256], s_src[256];
+    const int b = blockIdx.x, t = threadIdx.x, K = a.K;
+    const size_t row0 = (size_t)b * K;
+    const int *prev_ids = a.prev_ids + row0, *prev_age = a.prev_age + row0, *prev_hits = a.prev_hits + row0;
+    int *ids = a.ids + row0, *age = a.age + row0, *hits = a.hits + row0;
+    int *object_hits = a.object_hits + row0, *object_gap = a.object_gap + row0;
+    const int mp = count_clamp(a.prev_count[b], K);
+    if (a.active && !a.active[b]) {       // the table stays what it was (ids and count: rtk_associate_batched); no track ages
+        if (t < K) { age[t] = prev_age[t]; hits[t] = prev_hits[t]; object_hits[t] = 0; object_gap[t] = -1; }
+        if (t == 0) {
+            const int nd = a.prev_n_det[b];
+            a.n_det[b] = nd;
+            a.num_coasted[b] = mp - count_clamp(nd, mp);
+        }
+        return;
+    }
+    const int m = (a.reset && a.reset[b]) ? 0 : mp;
+    const int n = count_clamp(a.num_objects[b], K);
+    s_matched[t] = 0;
+    __syncthreads();
+    int from = -1;                         // the previous row whose ID current object t inherited
+    if (t < n) {
+        const int i = a.indices1[row0 + t];
+        if (i >= 0 && i < m && a.object_conf[row0 + t] != 0.f) { from = i; s_matched[i] = 1; }
+    }
+    __syncthreads();
+    if (t < n) {
+        const int h = from >= 0 ? prev_hits[from] + 1 : 1;
+        age[t] = 0; hits[t] = h;
+        object_hits[t] = h; object_gap[t] = from >= 0 ? prev_age[from] : -1;
+    } else if (t < K) {
+        object_hits[t] = 0; object_gap[t] = -1;
+    }
+    const int pa = t < m ? prev_age[t] : 0;
+    const bool survives = t < m && !s_matched[t] && pa < a.max_age;       // age + 1 <= max_age
+    int S;
+    const int slot = ordered_slot(survives, s_wave, &S);
+    const int cnt = n + S < K ? n + S : K;
+    if (survives && n + slot < K) {
+        const int r = n + slot;
+        ids[r] = prev_ids[t]; age[r] = pa + 1; hits[r] = prev_hits[t];
+        s_src[slot] = t;
+    }
+    if (t >= cnt && t < K) { ids[t] = -1; age[t] = 0; hits[t] = 0; }
+    if (t == 0) {
+        a.count[b] = cnt; a.n_det[b] = n; a.num_coasted[b] = cnt - n;
+        if (n + S > K) a.flags[b] |= 4;
+    }
+    __syncthreads();
+    const unsigned *src = reinterpret_cast<const unsigned *>(a.desc_prev) + row0 * RTK_DESC;
+    unsigned *dst = reinterpret_cast<unsigned *>(a.desc) + (row0 + n) * RTK_DESC;
+    for (int e = t; e < (cnt - n) * RTK_DESC; e += 256) dst[e] = src[(size_t)s_src[e / RTK_DESC] * RTK_DESC + e % RTK_DESC];
+}
+
+extern "C" int rtk_track_memory(int B, int K, int max_age, const unsigned char *active, const unsigned char *reset,
+                                const int *num_objects, const int *indices1, const float *object_conf, const int *prev_ids,
+                                const int *prev_age, const int *prev_hits, const int *prev_n_det, const int *prev_count,
+                                const float *desc_prev, int *ids, int *age, int *hits, int *n_det, int *count, float *desc, int *flags,
+                                int *object_hits, int *object_gap, int *num_coasted, rtk_stream_t stream) {
+    RTK_REQUIRE(B > 0 && B <= 65535 && num_objects && indices1 && object_conf && prev_ids && prev_age && prev_hits && prev_n_det &&
+                prev_count && desc_prev && ids && age && hits && n_det && count && desc && flags && object_hits && object_gap &&
+                num_coasted, "track_memory: bad arguments");
+    TRACK_REQUIRE_K(K, "track_memory");
+    RTK_REQUIRE(max_age >= 0, "track_memory: max_age=%d is negative", max_age);
+    RTK_REQUIRE(ids != prev_ids && age != prev_age && hits != prev_hits && desc != desc_prev,
+                "track_memory: the new table must not alias the previous one");
+    const MemArgs a = {K, max_age, active, reset, num_objects, indices1, object_conf, prev_ids, prev_age, prev_hits, prev_n_det, prev_count,
+                       desc_prev, ids, age, hits, n_det, count, desc, flags, object_hits, object_gap, num_coasted};
+    track_memory_kernel<<<B, 256, 0, (hipStream_t)stream>>>(a);
+    RTK_CHECK_LAUNCH("track_memory");
     return RTK_OK;
 }

@@ -206,11 +206,18 @@ class SequenceTrainer(Trainer):
     then keeps its state in place (`BatchedTracker(static_state=True)`); it and the scorer's state are advanced by the replay.  reset
     and active always live in static device buffers, so they never re-capture; h=None / a tensor, n_valid=None / a tensor, pretrain
     and the shapes do.  `items`, `h`, `out` and `match` are the graph's static outputs, as with `Trainer(graph=True)`: the next step
-    overwrites them in place (`out` is a new wrapper every step, so its host-side accessors never answer from an earlier step)."""
+    overwrites them in place (`out` is a new wrapper every step, so its host-side accessors never answer from an earlier step).
+    The trainer's tracker follows the reference's rule (previous objects = the last active frame's detections): `max_age` other
+    than None is refused -- `aff_target` is defined against the previous frame's detections only, and the tracking term has no
+    target for a coasted row."""
 
     N_GOBJ = ("slot", "label_id", "size", "count", "members", "centre", "n_valid")
 
-    def __init__(self, model, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, max_pairs=None, **trainer_kw):
+    def __init__(self, model, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, max_pairs=None, max_age=None, **trainer_kw):
+        if max_age is not None:
+            raise ValueError("SequenceTrainer: max_age=%r: the tracking term trains against the previous frame's detections only "
+                             "(track_score's aff_target has no target for a coasted track); train with max_age=None and use track "
+                             "memory at inference" % (max_age,))
         if trainer_kw.get("graph") and next(model.parameters()).device.type != "cuda":
             raise ValueError("SequenceTrainer: graph=True captures the sequence step in a hipGraph and needs the model on the GPU")
         super().__init__(model, **trainer_kw)

@@ -19,6 +19,15 @@ streams in flight at once: `TrackerPipeline`).
 Outputs stay on the device; `StepResult.objects(b)`, `aff_mat(b)`, `indices1(b)` and `BatchedTracker.write_results` synchronise
 when they are called.  More than `max_objects` objects in a stream is an error, never a truncation: the kernels flag it on the
 device and `objects`, `write_results` and `check()` raise.
+
+Track memory (`max_age`, off by default): the reference's rule is that the previous objects of a frame are the detections of the
+stream's last active frame and nothing else -- an object missed for one frame comes back with a fresh ID.  With
+`BatchedTracker(..., max_age=A)` the previous table of a stream is its last active frame's detections (its first `n_det` rows)
+followed by the tracks that were not matched for up to A active frames, each holding its last descriptor (no motion model); the
+association kernels see one table of `count` rows and need not know which is which.  A fifth launch (rtk_track_memory, rules in
+include/rtk_fused.h) advances that table on the device; `StepResult.object_hits`, `object_gap`, `num_coasted` and `prev_age` report
+the lifecycle.  Detections plus coasted tracks beyond `max_objects` rows drop the last coasted tracks and set a flag: `check()`
+raises, `objects` and `write_results` do not (what they report is complete).
 """
 import ctypes
 import os
@@ -32,7 +41,7 @@ from .abi import TrackFrame, View as _View, stream, view as _view  # noqa: F401 
 DESC = 141
 DBSCAN_POINT_BYTES = 48          # RTK_DBSCAN_POINT_BYTES
 DBSCAN_LDS_BYTES = 128 * 1024
-_FLAG_OVERFLOW, _FLAG_NVALID = 1, 2
+_FLAG_OVERFLOW, _FLAG_NVALID, _FLAG_TRUNCATED = 1, 2, 4
 
 
 def max_objects_limit():
@@ -94,7 +103,12 @@ class StepResult:
     step but one overwrites them; with `static_state=True` the NEXT step does, as it advances the state in place).
     From a `BatchedTracker(graph=True)` every tensor here is a static output of the captured graph: the next step overwrites all of
     them in place, so clone what must outlive it.  Each step hands back a new StepResult, so the host-side copy that `objects`,
-    `aff_mat`, `indices1(b)` and `check` keep belongs to that step alone."""
+    `aff_mat`, `indices1(b)` and `check` keep belongs to that step alone.
+    With track memory (`BatchedTracker(max_age=...)`, else None): object_hits (B,K) int32: how many frames object j's track has been
+    detected in, this one included (0 past num_objects); object_gap (B,K) int32: the age of the row object j inherited its ID from --
+    0: seen last frame, g: re-acquired after g missed frames, -1: a fresh ID or past num_objects; num_coasted (B,) int32: the rows of
+    the new table that are coasted tracks; prev_age (B,K) int32: the ages of the previous table's rows, aligned with the rows of `aff`
+    (0: a detection of the last active frame; the first `num_prev` are meaningful)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -136,7 +150,7 @@ class StepResult:
     def objects(self, b):
         """(objects, confs) of stream b in the structure of Track4D.forward: {track id: (1,139,n_i) tensor} in association order,
         confs aligned with it (0 for a fresh track, the 0-dim affinity tensor for an inherited one)."""
-        raise_on_flags(self._host()["flags"], self.max_objects, only=b)
+        raise_on_flags(self._host()["flags"], self.max_objects, only=b, truncation=False)
         m, n = self._sizes(b)
         if n == 0:
             return dict(), []
@@ -158,7 +172,8 @@ class StepResult:
         return objects, confs
 
 
-def raise_on_flags(flags, K, only=None):
+def raise_on_flags(flags, K, only=None, truncation=True):
+    """truncation=False: dropped coasted tracks do not raise (for a caller whose output is complete without them)."""
     for b, f in enumerate(flags):
         if only is not None and b != only:
             continue
@@ -166,13 +181,16 @@ def raise_on_flags(flags, K, only=None):
             raise RuntimeError("BatchedTracker: stream %d has more than max_objects=%d objects (raise max_objects)" % (b, K))
         if f & _FLAG_NVALID:
             raise RuntimeError("BatchedTracker: stream %d has an n_valid outside [0, N]" % b)
+        if truncation and f & _FLAG_TRUNCATED:
+            raise RuntimeError("BatchedTracker: stream %d dropped coasted tracks: its detections and the lost tracks within max_age "
+                               "exceed max_objects=%d rows (raise max_objects)" % (b, K))
 
 
 class BatchedTracker:
     """Tracks `streams` independent sequences in lockstep (see the module docstring)."""
 
     def __init__(self, net, streams, max_objects=128, iters=500, alpha=0.9, eps=1.5, threshold=0.5, train_mode=False,
-                 static_state=False, graph=False, graph_warmup=2, engine=None):
+                 static_state=False, graph=False, graph_warmup=2, engine=None, max_age=None):
         """train_mode: accept a train-mode net -- for a caller that runs the backbone itself and uses `associate` and the state only
         (track_train.SequenceTrainer); `step()` stays the eval-mode path.
         static_state: this frame's objects are always written to slot 0 of `desc` / `ids` / `count` and the previous objects read
@@ -186,7 +204,13 @@ class BatchedTracker:
         graph's static tensors: the next step overwrites them in place.  A new key captures again.  The captured graph keeps the
         weights it was captured with -- the backbone engine's packed images and the packed Affinity image -- as `fused.GraphPipeline`
         does: build a new tracker after changing weights.
-        engine: the `fused.FusedBackbone` that `step()` runs (default: `net._fused_engine()`, looked up every step)."""
+        engine: the `fused.FusedBackbone` that `step()` runs (default: `net._fused_engine()`, looked up every step).
+        max_age: None (default): the reference's rule, the tracker as it is without track memory -- no further launch or buffer, the
+        four lifecycle fields of `StepResult` are None.  An integer A >= 0: a track that is not matched stays in the stream's table
+        for up to A active frames (module docstring); 0 keeps the bookkeeping (hits, gap) and lets nothing coast.  A launch constant:
+        a captured step replays it as it was."""
+        if max_age is not None and (isinstance(max_age, bool) or not isinstance(max_age, int) or max_age < 0):
+            raise ValueError("max_age=%r: None (no track memory) or an integer >= 0 (frames a lost track is kept)" % (max_age,))
         if net.training and not train_mode:
             raise ValueError("BatchedTracker runs the eval-mode (fused) backbone: call net.eval() first")
         kmax = max_objects_limit()
@@ -206,6 +230,12 @@ class BatchedTracker:
         self.ids = torch.full((2, B, K), -1, dtype=torch.int32, device=dev)
         self.count = torch.zeros(2, B, dtype=torch.int32, device=dev)
         self.counter = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.max_age = max_age
+        self.age = self.hits = self.n_det = None
+        if max_age is not None:        # the lifecycle of every row of the table, double-buffered like the table itself
+            self.age = torch.zeros(2, B, K, dtype=torch.int32, device=dev)
+            self.hits = torch.zeros(2, B, K, dtype=torch.int32, device=dev)
+            self.n_det = torch.zeros(2, B, dtype=torch.int32, device=dev)
         self.cur = 0
         self._work = None
         self.last = None
@@ -285,7 +315,8 @@ class BatchedTracker:
 
     def associate(self, pc1, feature1, flow, cls, prop, n_valid, reset, active):
         """The post-backbone half of step(): four launches, the state swap (static_state: the state advance first, five launches);
-        no host synchronisation.  reset / active (B,) uint8 and n_valid (2,B) int32 (or None) are device tensors."""
+        with max_age one more, rtk_track_memory; no host synchronisation.  reset / active (B,) uint8 and n_valid (2,B) int32 (or
+        None) are device tensors."""
         B, K = self.B, self.K
         N = pc1.shape[2]
         dev = self.dev
@@ -296,7 +327,8 @@ class BatchedTracker:
             # into slot 0, so the copy leaves it as it was; a reset stream's previous objects are ignored.
             from .fused import copy_multi
             cur, prev = 0, 1
-            copy_multi([(self.desc[1], self.desc[0]), (self.ids[1], self.ids[0]), (self.count[1], self.count[0])])
+            state = [self.desc, self.ids, self.count] + ([] if self.max_age is None else [self.age, self.hits, self.n_det])
+            copy_multi([(t[1], t[0]) for t in state])
         else:
             cur, prev = self.cur, 1 - self.cur
         i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
@@ -317,30 +349,49 @@ class BatchedTracker:
                   self.ids[prev].data_ptr(), self.count[prev].data_ptr(), self.alpha, self.iters, self.counter.data_ptr(),
                   self.ids[cur].data_ptr(), self.count[cur].data_ptr(), object_ids.data_ptr(), object_conf.data_ptr(), indices1.data_ptr(),
                   num_prev.data_ptr(), point_track_id.data_ptr(), None, st)
+        memory = dict(object_hits=None, object_gap=None, num_coasted=None, prev_age=None)
+        if self.max_age is not None:
+            # the next table: this frame's detections, then the unmatched previous rows that are still young enough
+            memory = dict(object_hits=i32(B, K), object_gap=i32(B, K), num_coasted=i32(B), prev_age=self.age[prev])
+            _lib.call("rtk_track_memory", B, K, self.max_age, active.data_ptr(), reset.data_ptr(), num.data_ptr(), indices1.data_ptr(),
+                      object_conf.data_ptr(), self.ids[prev].data_ptr(), self.age[prev].data_ptr(), self.hits[prev].data_ptr(),
+                      self.n_det[prev].data_ptr(), self.count[prev].data_ptr(), desc_prev.data_ptr(), self.ids[cur].data_ptr(),
+                      self.age[cur].data_ptr(), self.hits[cur].data_ptr(), self.n_det[cur].data_ptr(), self.count[cur].data_ptr(),
+                      desc.data_ptr(), flags.data_ptr(), memory["object_hits"].data_ptr(), memory["object_gap"].data_ptr(),
+                      memory["num_coasted"].data_ptr(), st)
         if not self.static_state:
             self.cur = prev                # this frame's objects are the next frame's previous objects: a swap, not a copy
         out = StepResult(flow=flow, cls=cls, h=self.h, point_track_id=point_track_id, num_objects=num, object_ids=object_ids,
                          object_conf=object_conf, _indices1=indices1, aff=aff, num_prev=num_prev, flags=flags, labels=labels, obj=obj,
-                         descriptors=desc, desc_prev=desc_prev, active=active, pc1=pc1, feature1=feature1, prop=prop, max_objects=K, _cache=None)
+                         descriptors=desc, desc_prev=desc_prev, active=active, pc1=pc1, feature1=feature1, prop=prop, max_objects=K, _cache=None,
+                         **memory)
         self.last = out
         return out
 
     def check(self, out=None):
-        """Raises RuntimeError naming the stream if the last step (or `out`) overflowed max_objects or had a bad n_valid."""
+        """Raises RuntimeError naming the stream if the last step (or `out`) overflowed max_objects, had a bad n_valid or (track
+        memory) dropped coasted tracks that did not fit max_objects rows."""
         out = out if out is not None else self.last
         if out is not None:
             out.check()
 
     # ---- result files ------------------------------------------------------------------------------
-    def write_results(self, root, seqs, indices, out):
+    def write_results(self, root, seqs, indices, out, min_hits=1):
         """One result file per active stream, <root>/<seqs[b]>/<indices[b]:05d>.txt, byte-identical to
         vod_io.write_track_results(root, seqs[b], indices[b], *out.objects(b)); one device->host copy for the whole batch.
-        Returns the paths written."""
+        min_hits (track memory only): objects whose track has been detected in fewer frames (`object_hits` < min_hits) are left out
+        of the file -- confirmed tracks only.  Returns the paths written."""
+        if isinstance(min_hits, bool) or not isinstance(min_hits, int) or min_hits < 1:
+            raise ValueError("min_hits=%r: an integer >= 1" % (min_hits,))
+        if min_hits > 1 and out.object_hits is None:
+            raise ValueError("min_hits=%d needs the hit counts of track memory: build the tracker with max_age (0 or more)" % min_hits)
         B, K = self.B, self.K
         N = out.pc1.shape[2]
         pc1 = out.pc1.float()
         flat = [out.num_objects, out.flags, out.active.to(torch.int32), out.object_ids.reshape(-1), out.object_conf.reshape(-1).view(torch.int32),
                 out.obj.reshape(-1), pc1.contiguous().reshape(-1).view(torch.int32)]
+        if min_hits > 1:
+            flat.append(out.object_hits.reshape(-1))
         host = torch.cat([t.reshape(-1) for t in flat]).cpu()
         o = 0
 
@@ -352,7 +403,8 @@ class BatchedTracker:
         num, flags, act = take(B).tolist(), take(B).tolist(), take(B).tolist()
         ids, conf = take(B * K).view(B, K), take(B * K).view(torch.float32).view(B, K)
         obj, xyz = take(B * N).view(B, N), take(B * 3 * N).view(torch.float32).view(B, 3, N)
-        raise_on_flags([f if a else 0 for f, a in zip(flags, act)], K)
+        hits = take(B * K).view(B, K) if min_hits > 1 else None
+        raise_on_flags([f if a else 0 for f, a in zip(flags, act)], K, truncation=False)
         paths = []
         for b in range(B):
             if not act[b]:
@@ -368,6 +420,8 @@ class BatchedTracker:
             xb = xyz[b].numpy()
             with open(path, "w+") as f:
                 for j in range(num[b]):
+                    if hits is not None and int(hits[b, j]) < min_hits:
+                        continue
                     parts = ["NA", "1", "-1", "-1", str(float(conf[b, j])), str(int(ids[b, j]))]
                     for p in members[j]:
                         parts += [str(float(xb[0, p])), str(float(xb[1, p])), str(float(xb[2, p]))]

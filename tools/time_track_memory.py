@@ -1,0 +1,149 @@
+"""What track memory costs: the tracked step (BatchedTracker.step) with max_age=None and with max_age=2, eager and captured, and the
+max_age=None step of a checkout of the parent commit on the same machine.
+
+    python tools/time_track_memory.py [--parent DIR] [--rounds 5] [--streams 64] [--points 256] [--max-objects 128] [--iters 100]
+                                      [--warmup 10] [--out profiles/track_memory_timing.json]
+
+Every measurement is a process of its own (this one starts them and never touches the GPU itself); the processes of one round run one
+after the other, this tree and the parent's (--parent: a checkout of the parent commit with its library built) alternating, so that a
+drift of the machine lands on both.  A process steps the tracker through four synthetic frames of --streams clouds of --points points
+in rotation (synth.make_frame_pairs, synthetic weights with the segmentation head's bias raised so that there are objects to cluster,
+associate and lose) and reports the median device time between events around step(); the eager ones also the median time of the
+rtk_track_memory launch and of the four association launches (`_lib.TIMING`).  Per configuration the JSON holds the median and the
+spread (min, max) over the rounds.  max_age=None executes no new code: it must sit inside the run-to-run spread of the parent.
+Not part of bench.py."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ASSOC = ("rtk_dbscan_batched", "rtk_object_descriptors", "rtk_affinity_pairs", "rtk_associate_batched")
+
+
+def measure(a):
+    """One configuration in this process -> dict."""
+    sys.path.insert(0, os.path.abspath(a.root))
+    import torch
+    from ratrack_amd import _lib, synth, tracker as T
+    from ratrack_amd.track4d import Args, Track4D
+    dev = "cuda"
+    B, N = a.streams, a.points
+    frames = []
+    for i in range(4):
+        d = synth.make_frame_pairs(B, N, case_id=1000 + i)
+        frames.append([torch.from_numpy(d[k]).to(dev) for k in ("pc1", "pc2", "feature1", "feature2")])
+    net = Track4D(Args()).to(dev).eval()
+    sd = net.state_dict()
+    synth.fill_state_dict(sd)
+    sd["fd_layer.cp.linear.bias"].add_(a.moving_bias)
+    net.invalidate_fused()
+    kw = {} if a.max_age == "none" else dict(max_age=int(a.max_age))
+    trk = T.BatchedTracker(net, streams=B, max_objects=a.max_objects, graph=a.mode == "graph", **kw)
+    state = {"i": 0}
+
+    def step():
+        state["i"] += 1
+        return trk.step(*frames[state["i"] % 4])
+    with torch.no_grad():
+        for _ in range(a.warmup):
+            step()
+        torch.cuda.synchronize()
+        pairs = []
+        for _ in range(a.iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = step()
+            e1.record()
+            pairs.append((e0, e1))
+        torch.cuda.synchronize()
+        res = dict(step_ms=round(statistics.median(e0.elapsed_time(e1) for e0, e1 in pairs), 4),
+                   detected_objects=int(out.num_objects.sum()), previous_rows=int(out.num_prev.sum()))
+        if kw:
+            res["coasted_rows"] = int(out.num_coasted.sum())
+            flags = out.flags.cpu().tolist()
+            res["streams_truncated"] = sum(1 for f in flags if f & 4)
+        else:
+            trk.check()
+        if a.mode == "eager":
+            _lib.TIMING = []
+            for _ in range(a.iters):
+                step()
+            torch.cuda.synchronize()
+            per = {}
+            for name, e0, e1 in _lib.TIMING:
+                per.setdefault(name, []).append(e0.elapsed_time(e1))
+            _lib.TIMING = None
+            res["four_association_launches_ms"] = round(sum(statistics.median(per[k]) for k in ASSOC), 4)
+            if "rtk_track_memory" in per:
+                res["rtk_track_memory_ms"] = round(statistics.median(per["rtk_track_memory"]), 4)
+        res["captured"] = bool(getattr(trk, "captured", False))
+        res["device"] = torch.cuda.get_device_name(0)
+    print("RESULT " + json.dumps(res), flush=True)
+
+
+def child(a, root, max_age, mode):
+    cmd = [sys.executable, os.path.abspath(__file__), "--one", "--root", root, "--max-age", str(max_age), "--mode", mode,
+           "--streams", str(a.streams), "--points", str(a.points), "--max-objects", str(a.max_objects), "--iters", str(a.iters),
+           "--warmup", str(a.warmup), "--moving-bias", str(a.moving_bias)]
+    out = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.timeout, check=True).stdout.decode()
+    return json.loads([l for l in out.splitlines() if l.startswith("RESULT ")][-1][7:])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", default=None, help="a checkout of the parent commit, its library built")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--streams", type=int, default=64)
+    ap.add_argument("--points", type=int, default=256)
+    ap.add_argument("--max-objects", type=int, default=128)
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--moving-bias", type=float, default=4.0, help="added to the segmentation head's bias")
+    ap.add_argument("--timeout", type=float, default=240.0, help="seconds a measuring process may take")
+    ap.add_argument("--out", default=os.path.join("profiles", "track_memory_timing.json"))
+    ap.add_argument("--one", action="store_true", help="(internal) measure one configuration in this process")
+    ap.add_argument("--root", default=HERE)
+    ap.add_argument("--max-age", default="none")
+    ap.add_argument("--mode", default="eager", choices=("eager", "graph"))
+    a = ap.parse_args()
+    if a.one:
+        return measure(a)
+    configs = [("this", HERE, "none"), ("this", HERE, 2)] + ([("parent", a.parent, "none")] if a.parent else [])
+    runs = {}
+    for r in range(a.rounds):
+        for mode in ("eager", "graph"):
+            order = configs if r % 2 == 0 else configs[::-1]          # the trees alternate, and who goes first alternates too
+            for tree, root, max_age in order:
+                key = "%s/max_age=%s/%s" % (tree, max_age, mode)
+                runs.setdefault(key, []).append(child(a, root, max_age, mode))
+                print(key, runs[key][-1], flush=True)
+    res = {"what": "BatchedTracker.step, device ms between events, median of --iters per process; per configuration the median, min and "
+                   "max over the rounds (one process each, the trees alternating)",
+           "streams": a.streams, "points": a.points, "max_objects": a.max_objects, "iters": a.iters, "rounds": a.rounds,
+           "device": next(iter(runs.values()))[0]["device"], "configurations": {}}
+    for key, rs in runs.items():
+        ms = [x["step_ms"] for x in rs]
+        c = dict(step_ms_median=round(statistics.median(ms), 4), step_ms_min=min(ms), step_ms_max=max(ms), step_ms_runs=ms)
+        for k in ("four_association_launches_ms", "rtk_track_memory_ms"):
+            if k in rs[0]:
+                c[k + "_median"] = round(statistics.median(x[k] for x in rs), 4)
+        for k in ("detected_objects", "previous_rows", "coasted_rows", "streams_truncated", "captured"):
+            if k in rs[0]:
+                c[k] = rs[-1][k]
+        res["configurations"][key] = c
+    if a.parent:
+        for mode in ("eager", "graph"):
+            p, t = res["configurations"]["parent/max_age=none/" + mode], res["configurations"]["this/max_age=none/" + mode]
+            res["max_age_none_inside_parent_spread_" + mode] = bool(p["step_ms_min"] <= t["step_ms_median"] <= p["step_ms_max"])
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
