@@ -36,10 +36,12 @@ extern "C" {
 #define RTK_SCORE_FLAG_OBJECTS 8     /* rtk_track_score: a num_objects outside [0, Kobj] (clamped) */
 #define RTK_SCORE_FLAG_LOG 16        /* rtk_track_score_logged: a frame did not fit the stream's log and was not logged at all */
 #define RTK_SCORE_FLAG_SWEEP 32      /* rtk_score_track_means: more track ids in one clip than RTK_SCORE_SWEEP_TRACKS (no score written) */
+#define RTK_SCORE_FLAG_TABLE 64      /* rtk_track_score_memory: a table_count outside [num_objects, Kobj] (clamped) */
 
 /* LDS bytes of one workgroup for these sizes (host functions: no device is touched). */
 RTK_EXPORT int rtk_gt_objects_lds_bytes(int K, int N);
 RTK_EXPORT int rtk_track_score_lds_bytes(int Kobj, int K, int N);
+RTK_EXPORT int rtk_track_score_memory_lds_bytes(int Kobj, int K, int N);      /* rtk_track_score_memory: Kobj more words */
 
 /* W = (N + 31) / 32 mask words per object; bit p & 31 of word p >> 5 is point p. */
 typedef struct {
@@ -172,6 +174,43 @@ typedef struct {
  * frames (a captured launch replays correctly).  An inactive stream appends nothing. */
 RTK_EXPORT int rtk_track_score_logged(const rtk_track_score_in_t *in, const rtk_track_score_state_t *state, const rtk_track_score_out_t *out,
                                       const rtk_score_log_t *log, rtk_stream_t stream);
+
+/* The record of a tracker that keeps lost tracks (BatchedTracker(max_age=...), rtk_track_memory in rtk_fused.h).  The previous table
+ * of such a tracker is taller than the previous frame's detections: rows of coasted tracks follow them, and `aff` has a row for each.
+ * rtk_track_score_memory keeps a record as tall as that table, so that row i of aff_target is row i of aff. */
+typedef struct {
+    const int *table_ids;         /* (B,Kobj) input: the track id of every row of the tracker's NEW table -- the one this frame's */
+    const int *table_count;       /* (B) input:      rtk_associate_batched and rtk_track_memory wrote -- and its row count */
+    int *row_track;               /* (B,Kobj) state: the track id of every row of the record, -1 past prev_count */
+    int *labelled_coasted;        /* (B) state: the record's rows at or past its frame's detection count whose label id is >= 0 */
+} rtk_score_memory_t;
+
+/* rtk_track_score (with log == NULL) or rtk_track_score_logged, in the same single launch, with a record of the whole table.  In the
+ * state block prev_gt_id is the label id of EVERY row of the record and prev_count the record's row count; prev_gt keeps its meaning.
+ * mem->row_track is -1-initialised and mem->labelled_coasted zero-initialised by the caller; only this entry point writes them.
+ * Counters, table, matching and log are rtk_track_score's, bit for bit.  What differs, per active stream b with P = its clamped
+ * num_objects:
+ *   target       the formula is unchanged: aff_target[i][j] = 1 iff i < prev_count, j < P, prev_gt_id[i] >= 0 and prev_gt_id[i] is
+ *                detection j's label id.  The record is as tall as the previous table, so target row i is aff row i, a coasted row
+ *                included.  Two rows of the record may carry one label id -- a lost track still coasts while its object was detected
+ *                again under a fresh id -- and then BOTH rows get the 1.  That is intended: both rows are that object, and either
+ *                is a correct row for the detection to be associated with.  A coasted row that never matched an object has label
+ *                id -1 and an all-zero target row.
+ *   new record   R = table_count[b] clamped to [P, Kobj] rows; outside that range RTK_SCORE_FLAG_TABLE is raised (sticky).  Row
+ *                r < P holds (object_ids[r], detection r's label id or -1).  Row P <= r < R holds table_ids[r] and the label id
+ *                of the OLD record's first row with the same row_track, -1 when there is none or the stream is reset.  Track ids
+ *                are unique within a stream's table, so no permutation has to come out of rtk_track_memory; a row the tracker
+ *                dropped is simply not found again.  Rows past R: -1 / -1.  labelled_coasted = the rows P <= r < R with a label
+ *                id >= 0.
+ *   aff_defined  prev_count > 0 && P > 0 && G > 0 && (prev_gt > 0 || labelled_coasted > 0), the state read before this frame
+ *                replaces it.  Without coasted rows that is rtk_track_score's rule bit for bit; with them a frame stays defined
+ *                when the previous frame had no kept ground-truth object but a coasted row remembers one (an object hidden for
+ *                one frame: the re-acquisition to train).
+ *   reset        drops the record first, as above; an inactive stream changes no state and writes -1 / 0 outputs.
+ * With table_ids = object_ids and table_count = num_objects every output and every shared state tensor equals rtk_track_score's.
+ * Every row is written by exactly one thread with plain stores: the same bits on every run. */
+RTK_EXPORT int rtk_track_score_memory(const rtk_track_score_in_t *in, const rtk_track_score_state_t *state, const rtk_track_score_out_t *out,
+                                      const rtk_score_log_t *log /* NULL: no log */, const rtk_score_memory_t *mem, rtk_stream_t stream);
 
 /* rec_score (B,R) float64: for every logged detection the score of its track.  One workgroup per stream; flags (B) gains
  * RTK_SCORE_FLAG_SWEEP for a stream with more than RTK_SCORE_SWEEP_TRACKS track ids in a clip. */

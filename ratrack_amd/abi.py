@@ -99,6 +99,10 @@ class ScoreLog(ctypes.Structure):
                                                             "rec_iou")]
 
 
+class ScoreMemory(ctypes.Structure):
+    _fields_ = [(n, _p) for n in ("table_ids", "table_count", "row_track", "labelled_coasted")]
+
+
 # ---- include/rtk_train.h --------------------------------------------------------------------------------------------------------
 
 class BnFin(ctypes.Structure):
@@ -137,13 +141,14 @@ STRUCTS = {
     "rtk_gt_boxes_t": GtBoxes, "rtk_gt_in_t": GtIn, "rtk_gt_out_t": GtOut, "rtk_eval_in_t": EvalIn,
     "rtk_gt_objects_in_t": GtObjectsIn, "rtk_gt_objects_out_t": GtObjectsOut, "rtk_track_score_in_t": ScoreIn,
     "rtk_track_score_state_t": ScoreState, "rtk_track_score_out_t": ScoreOut, "rtk_score_log_t": ScoreLog,
+    "rtk_score_memory_t": ScoreMemory,
     "rtk_bn_fin_t": BnFin, "rtk_tn_job_t": TnJob, "rtk_pack_job_t": PackJob, "rtk_inverse_index_job_t": InverseIndexJob,
     "rtk_pool_src_t": PoolSrc, "rtk_pw_operand_t": PwOperand, "rtk_pw_wgrad_job_t": PwWgradJob,
 }
 
 # name -> argtypes.  A struct pointer that callers pass as ctypes.addressof() is _p; one they pass as an array or byref() is typed.
-# The argument blocks of rtk_gt.h and rtk_score.h (GtIn, GtOut, EvalIn, GtObjectsIn, ..., ScoreOut, ScoreLog) and rtk_track_frame_t go by
-# address; the two *_lds_bytes are host functions that return a byte count.
+# The argument blocks of rtk_gt.h and rtk_score.h (GtIn, GtOut, EvalIn, GtObjectsIn, ..., ScoreOut, ScoreLog, ScoreMemory) and rtk_track_frame_t go by
+# address; the *_lds_bytes are host functions that return a byte count.
 SIGNATURES = {
     # ---- include/rtk_pointnet2.h
     "rtk_furthest_point_sampling": [_i] * 3 + [_p] * 3 + [_p],
@@ -202,9 +207,11 @@ SIGNATURES = {
     # ---- include/rtk_score.h
     "rtk_gt_objects_lds_bytes": [_i, _i],
     "rtk_track_score_lds_bytes": [_i, _i, _i],
+    "rtk_track_score_memory_lds_bytes": [_i, _i, _i],
     "rtk_gt_objects": [_p, _p, _p],
     "rtk_track_score": [_p, _p, _p, _p],
     "rtk_track_score_logged": [_p, _p, _p, _p, _p],
+    "rtk_track_score_memory": [_p, _p, _p, _p, _p, _p],
     "rtk_score_track_means": [_i, _p, _p, _p, _p],
     "rtk_score_thresholds": [_p, _p, _p, _i, _p, _p, _p],
     "rtk_score_replay": [_i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p],

@@ -54,6 +54,17 @@ The device delivers integers and fixed-order IoU sums; every ratio is float64 ho
 the numbers of the reference's README table: its evaluator (a confidence-swept AB3DMOT variant) is not distributed, and the IoU and
 the thresholds it uses are unknown.
 
+Track memory.  Behind a `BatchedTracker(max_age=...)` the previous table is taller than the previous frame's detections: coasted
+tracks follow them, and `StepResult.aff` has a row for each.  `TrackScorer(..., track_memory=True)` keeps its record by the tracker's
+table (`StepResult.table_ids` / `table_count`), one launch per frame as before (rtk_track_score_memory, rules in
+include/rtk_score.h): `prev_gt_id` then holds the label id of EVERY row of the record, `row_track` its track id, and a coasted row
+keeps the label id its track last had -- so row i of `aff_target` is row i of `aff`, and a coasted row whose object is detected
+again has a 1 in that detection's column.  Two rows may carry one label id (a lost track still coasts while its object came back
+under a fresh ID); both get the 1, on purpose: both rows are that object.  `aff_defined` = prev_count > 0 and P > 0 and G > 0 and
+(prev_gt > 0 or labelled_coasted > 0): the plain rule wherever nothing coasts, and a frame stays defined when the previous frame had
+no kept ground-truth object but a coasted row remembers one.  A plain `TrackScorer` may still score a memory tracker -- its counters
+are right -- but its target has no row for a coasted track.
+
 Nothing here synchronises with the device except `GtObjects.check()`, `TrackScorer.check()`, `TrackScorer.result()` and
 `TrackScorer.sweep()`.
 """
@@ -63,7 +74,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .abi import GtBoxes, GtObjectsIn, GtObjectsOut, ScoreIn, ScoreLog, ScoreOut, ScoreState, stream as _stream, view as _view
+from .abi import GtBoxes, GtObjectsIn, GtObjectsOut, ScoreIn, ScoreLog, ScoreMemory, ScoreOut, ScoreState, stream as _stream, view as _view
 from .gt_device import _flag_bytes, _n_valid
 
 LDS_LIMIT = 65536                      # RTK_SCORE_LDS_LIMIT
@@ -73,14 +84,16 @@ MAX_POINTS = 32768                     # RTK_SCORE_MAX_POINTS
 COUNTERS = ("frames", "gt", "pred", "tp", "fp", "fn", "idsw", "tracks", "mt", "pt", "ml")
 FLAG_BOXES, FLAG_NVALID, FLAG_TRACKS, FLAG_OBJECTS = 1, 2, 4, 8
 FLAG_LOG, FLAG_SWEEP = 16, 32          # RTK_SCORE_FLAG_LOG, RTK_SCORE_FLAG_SWEEP
+FLAG_TABLE = 64                        # RTK_SCORE_FLAG_TABLE
 SWEEP_TRACKS = 2048                    # RTK_SCORE_SWEEP_TRACKS
 
 
 # ---- what fits -------------------------------------------------------------------------------------------------------------
 
-def check_fit(max_boxes, points, max_objects=None):
+def check_fit(max_boxes, points, max_objects=None, track_memory=False):
     """Raises ValueError, stating the limit, for sizes whose per-stream tables do not fit one workgroup's LDS: those of `gt_objects`
-    (max_boxes, points) and, with max_objects, those of `TrackScorer.update` as well.  Host only."""
+    (max_boxes, points) and, with max_objects, those of `TrackScorer.update` as well (track_memory: of its memory variant, which
+    keeps max_objects more words).  Host only."""
     K, N = int(max_boxes), int(points)
     if not 1 <= K <= MAX_BOXES:
         raise ValueError("max_boxes=%d outside [1, %d] (a point's ground-truth objects are one 64-bit mask)" % (K, MAX_BOXES))
@@ -94,7 +107,7 @@ def check_fit(max_boxes, points, max_objects=None):
     Kobj = int(max_objects)
     if not 1 <= Kobj <= MAX_OBJECTS:
         raise ValueError("max_objects=%d outside [1, %d]" % (Kobj, MAX_OBJECTS))
-    need = _lib._fn("rtk_track_score_lds_bytes")(Kobj, K, N)
+    need = _lib._fn("rtk_track_score_memory_lds_bytes" if track_memory else "rtk_track_score_lds_bytes")(Kobj, K, N)
     if need < 0 or need > LDS_LIMIT:
         raise ValueError("TrackScorer: max_objects=%d, max_boxes=%d and N=%d need %d bytes of LDS per stream, the limit is %d"
                          % (Kobj, K, N, need, LDS_LIMIT))
@@ -281,9 +294,16 @@ class TrackScorer:
     sweep_records kept-label entries per stream, about 24 bytes per record.  The log (device tensors, all cursors included):
     log_cursor (B,4) int32 frames | records | label entries logged; log_frame (B,F,4) int32 first record | first label entry |
     detections + 65536 * began a clip | kept objects; log_label (B,R); log_track, log_best (B,R) int32, log_conf (B,R) fp32,
-    log_iou (B,R) float64."""
+    log_iou (B,R) float64.
 
-    def __init__(self, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, device="cuda", sweep_frames=None, sweep_records=None):
+    track_memory: False (today's object, launches and bits, also behind a tracker with track memory), or True: the record follows
+    the table of a `BatchedTracker(max_age=...)` (module docstring).  prev_gt_id (B,Kobj) is then the label id of every row of the
+    record and prev_count its row count; two more state tensors sit next to them: row_track (B,Kobj) int32, the track id of every
+    row of the record (-1 past prev_count), and labelled_coasted (B) int32, the record's rows past its frame's detections that carry
+    a label id.  `update` takes the table from the StepResult, `update_raw` as table_ids= / table_count=."""
+
+    def __init__(self, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, device="cuda", sweep_frames=None, sweep_records=None,
+                 track_memory=False):
         self.B, self.Kobj, self.K, self.T = int(streams), int(max_objects), int(max_boxes), int(max_gt_tracks)
         if self.T < 1:
             raise ValueError("max_gt_tracks=%d must be at least 1" % self.T)
@@ -295,7 +315,8 @@ class TrackScorer:
             if self.F < 1 or self.R < 1 or self.B * max(self.F * 4, self.R) >= 2 ** 31:
                 raise ValueError("TrackScorer: sweep_frames=%d, sweep_records=%d must be at least 1 (and the log below 2^31 entries)"
                                  % (self.F, self.R))
-        check_fit(self.K, 1, self.Kobj)
+        self.track_memory = bool(track_memory)
+        check_fit(self.K, 1, self.Kobj, self.track_memory)
         B, z = self.B, lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
         self.counters = torch.zeros(B, len(COUNTERS), dtype=torch.int64, device=device)
         self.iou_sum = torch.zeros(B, dtype=torch.float64, device=device)
@@ -303,6 +324,9 @@ class TrackScorer:
         self.table_used, self.prev_gt, self.flags = z(B), z(B), z(B)
         self.prev_gt_id = torch.full((B, self.Kobj), -1, dtype=torch.int32, device=device)
         self.prev_count = torch.full((B,), -1, dtype=torch.int32, device=device)
+        if self.track_memory:
+            self.row_track = torch.full((B, self.Kobj), -1, dtype=torch.int32, device=device)
+            self.labelled_coasted = z(B)
         if self.logging:
             self.log_cursor, self.log_frame = z(B, 4), z(B, self.F, 4)
             self.log_label, self.log_track, self.log_best = z(B, self.R), z(B, self.R), z(B, self.R)
@@ -315,17 +339,27 @@ class TrackScorer:
 
     def update(self, out, gobj, reset=None, active=None):
         """out: a `tracker.StepResult`; gobj: the GtObjects of the same frame (its n_valid is used).  active None: the mask the step
-        ran with.  With logging on, out.object_conf is logged.  One launch, no synchronisation.  -> MatchResult."""
+        ran with.  With logging on, out.object_conf is logged; with track_memory, out.table_ids / out.table_count are the table.
+        One launch, no synchronisation.  -> MatchResult."""
         if out.max_objects != self.Kobj:
             raise ValueError("TrackScorer(max_objects=%d) against a step with max_objects=%d" % (self.Kobj, out.max_objects))
+        table = {}
+        if self.track_memory:
+            if getattr(out, "table_ids", None) is None or getattr(out, "table_count", None) is None:
+                raise ValueError("TrackScorer(track_memory=True) keeps its record by the tracker's table, and this step has none: "
+                                 "build the tracker with max_age (0 or more)")
+            table = dict(table_ids=out.table_ids, table_count=out.table_count)
         return self.update_raw(out.pc1, out.obj, out.num_objects, out.object_ids, gobj, gobj.n_valid, reset,
-                               out.active if active is None else active, object_conf=out.object_conf if self.logging else None)
+                               out.active if active is None else active, object_conf=out.object_conf if self.logging else None, **table)
 
-    def update_raw(self, pc1, obj, num_objects, object_ids, gobj, n_valid=None, reset=None, active=None, object_conf=None):
+    def update_raw(self, pc1, obj, num_objects, object_ids, gobj, n_valid=None, reset=None, active=None, object_conf=None, table_ids=None,
+                   table_count=None):
         """pc1 (B,3,N) fp32 of any strides; obj (B,N) int32, the detection each point belongs to (-1 none; detections are numbered in
         association order); num_objects (B) int32; object_ids (B,Kobj) int32 track ids; gobj from `gt_objects` on the same cloud;
         n_valid (B) / (2,B) / None; reset, active (B) masks or None; object_conf (B,Kobj) fp32, the confidence of each detection:
-        required when the scorer logs for `sweep`, ignored otherwise."""
+        required when the scorer logs for `sweep`, ignored otherwise; table_ids (B,Kobj) int32 and table_count (B) int32: the
+        tracker's NEW table (the one this frame's association wrote: its first num_objects rows are this frame's detections),
+        required with track_memory, ignored otherwise."""
         B, C, N = pc1.shape
         if B != self.B or C != 3 or tuple(obj.shape) != (B, N) or tuple(object_ids.shape) != (B, self.Kobj) or num_objects.numel() != B:
             raise ValueError("TrackScorer(streams=%d, max_objects=%d): got pc1 %s, obj %s, object_ids %s"
@@ -333,8 +367,12 @@ class TrackScorer:
         if gobj.max_boxes != self.K or gobj.points != N or gobj.count.numel() != B:
             raise ValueError("TrackScorer(max_boxes=%d): ground-truth objects of %d slots over %d points against %d points"
                              % (self.K, gobj.max_boxes, gobj.points, N))
-        check_fit(self.K, N, self.Kobj)
+        check_fit(self.K, N, self.Kobj, self.track_memory)
         dev = pc1.device
+        if self.track_memory and (table_ids is None or table_count is None or tuple(table_ids.shape) != (B, self.Kobj) or table_count.numel() != B):
+            raise ValueError("TrackScorer(track_memory=True): update_raw needs the tracker's table, table_ids (%d,%d) and table_count (%d), got %s and %s"
+                             % (B, self.Kobj, B, None if table_ids is None else tuple(table_ids.shape),
+                                None if table_count is None else tuple(table_count.shape)))
         if self.logging:
             if object_conf is None or tuple(object_conf.shape) != (B, self.Kobj):
                 raise ValueError("TrackScorer(sweep_frames=%d, sweep_records=%d) logs for the sweep: update_raw needs object_conf (%d,%d), got %s"
@@ -358,7 +396,13 @@ class TrackScorer:
                        self.prev_count.data_ptr(), self.prev_gt.data_ptr(), self.flags.data_ptr())
         o = ScoreOut(pred_gt_slot.data_ptr(), pred_gt_id.data_ptr(), gt_pred.data_ptr(), iou.data_ptr(), aff_target.data_ptr(),
                      aff_defined.data_ptr())
-        if self.logging:
+        if self.track_memory:
+            table_ids, table_count = as32(table_ids), as32(table_count)
+            mm = ScoreMemory(table_ids.data_ptr(), table_count.data_ptr(), self.row_track.data_ptr(), self.labelled_coasted.data_ptr())
+            lg = self._log_block(object_conf.data_ptr()) if self.logging else None
+            _lib.call("rtk_track_score_memory", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o),
+                      None if lg is None else ctypes.addressof(lg), ctypes.addressof(mm), _stream())
+        elif self.logging:
             lg = self._log_block(object_conf.data_ptr())
             _lib.call("rtk_track_score_logged", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), ctypes.addressof(lg), _stream())
         else:
@@ -375,6 +419,8 @@ class TrackScorer:
                 raise RuntimeError("TrackScorer: stream %d has an n_valid outside [0, N]" % b)
             if f & FLAG_OBJECTS:
                 raise RuntimeError("TrackScorer: stream %d has a num_objects outside [0, max_objects=%d]" % (b, self.Kobj))
+            if f & FLAG_TABLE:
+                raise RuntimeError("TrackScorer: stream %d has a table_count outside [num_objects, max_objects=%d]" % (b, self.Kobj))
             if f & FLAG_LOG:
                 raise RuntimeError("TrackScorer: stream %d has a frame that did not fit its log of sweep_frames=%d frames and "
                                    "sweep_records=%d records and was not logged (raise them)" % (b, self.F, self.R))

@@ -13,6 +13,12 @@ the descriptors down to `flow` (through the mean) and `prop_features` (through t
 as in the reference (main_utils.py:158-160).  No host synchronisation, a fixed number of launches, no floating-point atomics: the
 term is reproducible bit for bit.
 
+Re-acquisition.  With `SequenceTrainer(..., reacquire=A)` the trainer's tracker keeps lost tracks for up to A frames
+(`BatchedTracker(max_age=A)`) and its scorer keeps a record of the whole table (`TrackScorer(track_memory=True)`): `out.num_prev`
+counts the coasted rows too, `aff_target` has a row for each, and the term trains the MLP to give a coasted track the detection
+of the object it last was.  The training kernels need no change: they take m_b = `out.num_prev` rows, and a taller table is just
+more live pairs.
+
 A batch with more live pairs than `max_pairs` (the workspace holds 8 KiB per pair) leaves the streams beyond the cap out of the term
 and flags them; `check()` raises naming them -- nothing is truncated silently.
 """
@@ -189,8 +195,8 @@ def check(out):
 class _TrainTracker(T.BatchedTracker):
     """BatchedTracker's state and `associate` behind a train-mode backbone that the trainer runs itself."""
 
-    def __init__(self, net, streams, max_objects, static_state=False):
-        super().__init__(net, streams, max_objects=max_objects, train_mode=True, static_state=static_state)
+    def __init__(self, net, streams, max_objects, static_state=False, max_age=None):
+        super().__init__(net, streams, max_objects=max_objects, train_mode=True, static_state=static_state, max_age=max_age)
 
     def step(self, *a, **k):
         raise RuntimeError("SequenceTrainer runs the train-mode backbone itself: use SequenceTrainer.step")
@@ -207,25 +213,38 @@ class SequenceTrainer(Trainer):
     and active always live in static device buffers, so they never re-capture; h=None / a tensor, n_valid=None / a tensor, pretrain
     and the shapes do.  `items`, `h`, `out` and `match` are the graph's static outputs, as with `Trainer(graph=True)`: the next step
     overwrites them in place (`out` is a new wrapper every step, so its host-side accessors never answer from an earlier step).
-    The trainer's tracker follows the reference's rule (previous objects = the last active frame's detections): `max_age` other
-    than None is refused -- `aff_target` is defined against the previous frame's detections only, and the tracking term has no
-    target for a coasted row."""
+    reacquire: None (default): the trainer's tracker follows the reference's rule (previous objects = the last active frame's
+    detections), the object and the launches as they are without it.  An integer A >= 0: the tracker is built with max_age=A and
+    the scorer with track_memory=True, so that the term also covers the coasted rows of the previous table (module docstring);
+    the tracker's lifecycle state and the scorer's record live at fixed addresses, and graph=True replays advance them.
+    `max_age` other than None is refused: a plain scorer's `aff_target` is defined against the previous frame's detections only
+    and has no target for a coasted row -- `reacquire` is the keyword that changes the scorer with the tracker."""
 
     N_GOBJ = ("slot", "label_id", "size", "count", "members", "centre", "n_valid")
 
-    def __init__(self, model, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, max_pairs=None, max_age=None, **trainer_kw):
+    def __init__(self, model, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, max_pairs=None, max_age=None, reacquire=None,
+                 **trainer_kw):
         if max_age is not None:
             raise ValueError("SequenceTrainer: max_age=%r: the tracking term trains against the previous frame's detections only "
-                             "(track_score's aff_target has no target for a coasted track); train with max_age=None and use track "
-                             "memory at inference" % (max_age,))
+                             "(track_score's aff_target has no target for a coasted track); to train with track memory give "
+                             "reacquire=%r, which builds the tracker with that max_age and a scorer that has such a target"
+                             % (max_age, max_age))
+        if reacquire is not None and (isinstance(reacquire, bool) or not isinstance(reacquire, int) or reacquire < 0):
+            raise ValueError("reacquire=%r: None (no track memory) or an integer >= 0 (frames a lost track is kept)" % (reacquire,))
         if trainer_kw.get("graph") and next(model.parameters()).device.type != "cuda":
             raise ValueError("SequenceTrainer: graph=True captures the sequence step in a hipGraph and needs the model on the GPU")
         super().__init__(model, **trainer_kw)
         if self._dev.type != "cuda":
             raise ValueError("SequenceTrainer needs a model on the GPU (the tracker, the scorer and the tracking term are HIP only)")
         model.train()
-        self.tracker = _TrainTracker(model, streams, max_objects, static_state=bool(self.graph))
-        self.scorer = TrackScorer(streams=streams, max_objects=max_objects, max_boxes=max_boxes, max_gt_tracks=max_gt_tracks, device=self._dev)
+        self.reacquire = reacquire
+        if reacquire is None:
+            self.tracker = _TrainTracker(model, streams, max_objects, static_state=bool(self.graph))
+            self.scorer = TrackScorer(streams=streams, max_objects=max_objects, max_boxes=max_boxes, max_gt_tracks=max_gt_tracks, device=self._dev)
+        else:
+            self.tracker = _TrainTracker(model, streams, max_objects, static_state=bool(self.graph), max_age=reacquire)
+            self.scorer = TrackScorer(streams=streams, max_objects=max_objects, max_boxes=max_boxes, max_gt_tracks=max_gt_tracks,
+                                      device=self._dev, track_memory=True)
         self.max_pairs = default_max_pairs(int(streams), int(max_objects)) if max_pairs is None else int(max_pairs)
         self.last = None
         self._default_masks = None

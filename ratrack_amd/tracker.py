@@ -108,7 +108,10 @@ class StepResult:
     detected in, this one included (0 past num_objects); object_gap (B,K) int32: the age of the row object j inherited its ID from --
     0: seen last frame, g: re-acquired after g missed frames, -1: a fresh ID or past num_objects; num_coasted (B,) int32: the rows of
     the new table that are coasted tracks; prev_age (B,K) int32: the ages of the previous table's rows, aligned with the rows of `aff`
-    (0: a detection of the last active frame; the first `num_prev` are meaningful)."""
+    (0: a detection of the last active frame; the first `num_prev` are meaningful); table_ids (B,K) int32 and table_count (B) int32:
+    the table this step wrote -- the track id of every row, this frame's detections first and the coasted tracks after them, and its
+    row count (the tracker's own buffers, overwritten like `descriptors`): what `TrackScorer(track_memory=True)` keeps its record
+    by."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -349,10 +352,11 @@ class BatchedTracker:
                   self.ids[prev].data_ptr(), self.count[prev].data_ptr(), self.alpha, self.iters, self.counter.data_ptr(),
                   self.ids[cur].data_ptr(), self.count[cur].data_ptr(), object_ids.data_ptr(), object_conf.data_ptr(), indices1.data_ptr(),
                   num_prev.data_ptr(), point_track_id.data_ptr(), None, st)
-        memory = dict(object_hits=None, object_gap=None, num_coasted=None, prev_age=None)
+        memory = dict(object_hits=None, object_gap=None, num_coasted=None, prev_age=None, table_ids=None, table_count=None)
         if self.max_age is not None:
             # the next table: this frame's detections, then the unmatched previous rows that are still young enough
-            memory = dict(object_hits=i32(B, K), object_gap=i32(B, K), num_coasted=i32(B), prev_age=self.age[prev])
+            memory = dict(object_hits=i32(B, K), object_gap=i32(B, K), num_coasted=i32(B), prev_age=self.age[prev],
+                          table_ids=self.ids[cur], table_count=self.count[cur])
             _lib.call("rtk_track_memory", B, K, self.max_age, active.data_ptr(), reset.data_ptr(), num.data_ptr(), indices1.data_ptr(),
                       object_conf.data_ptr(), self.ids[prev].data_ptr(), self.age[prev].data_ptr(), self.hits[prev].data_ptr(),
                       self.n_det[prev].data_ptr(), self.count[prev].data_ptr(), desc_prev.data_ptr(), self.ids[cur].data_ptr(),
