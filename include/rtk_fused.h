@@ -420,12 +420,39 @@ RTK_EXPORT int rtk_associate_batched(int B, int N, int K, const unsigned char *a
  * Per-step outputs: object_hits (B,K) = hits of current object j (0 past n_b); object_gap (B,K) = prev_age of the row object j
  * inherited from (0: seen last frame, g: re-acquired after g missed frames; -1: fresh ID or past n_b); num_coasted (B) = count - n_det
  * of the new table (= count - n_b on an active stream).
- * active / reset may be NULL (all active / none reset).  One workgroup per stream, plain stores only: every run gives the same bits. */
+ * active / reset may be NULL (all active / none reset).  One workgroup per stream, plain stores only: every run gives the same bits.
+ * (Coasted tracks that move with their track's velocity: rtk_track_memory_motion below, a separate entry point.) */
 RTK_EXPORT int rtk_track_memory(int B, int K, int max_age, const unsigned char *active, const unsigned char *reset,
                                 const int *num_objects, const int *indices1, const float *object_conf, const int *prev_ids,
                                 const int *prev_age, const int *prev_hits, const int *prev_n_det, const int *prev_count,
                                 const float *desc_prev, int *ids, int *age, int *hits, int *n_det, int *count, float *desc, int *flags,
                                 int *object_hits, int *object_gap, int *num_coasted, rtk_stream_t stream);
+
+/* rtk_track_memory_motion: rtk_track_memory with a constant-velocity motion model (csrc/track_motion.hip) -- issued INSTEAD of it,
+ * never with it.  Every row of the table carries a velocity, vel (B,K,3) fp32, double-buffered like the table (prev_vel is read,
+ * vel is written; they must not alias): the object's displacement per frame in the sensor frame, taken from channels 134..136 of its
+ * descriptor (its mean predicted scene flow, which includes the ego motion -- no pose is needed).  Everything stated for
+ * rtk_track_memory holds unchanged: ids, age, hits, n_det, count, flags bit 2, object_hits, object_gap, num_coasted, and what a
+ * reset, an inactive stream and an empty frame do.  In addition (`from` = the previous row current row j inherited its ID from, -1
+ * when it did not; all arithmetic is fp32, every operation rounded on its own, no FMA):
+ *   current    rows j < n_b, with f = desc[b][j][134..136] (written by rtk_object_descriptors; desc is read AND written here):
+ *              vel[j] = f bit for bit when from < 0 or beta == 1, else vel[j] = v + beta * (f - v) with v = prev_vel[from] (a
+ *              subtraction, a multiplication, an addition).  object_velocity[j] = vel[j].  The descriptor row is not touched.
+ *   survivors  previous row i that becomes row r: the 141 descriptor words are copied bit for bit except channels 0..2, the centre:
+ *              desc[r][c] = desc_prev[i][c] + prev_vel[i][c] (one addition), so a track that coasts g frames has moved g times;
+ *              channels 134..136 keep the last measured flow.  vel[r] = prev_vel[i] bit for bit.
+ *   reset      no survivors; every current row takes vel = f.
+ *   inactive   vel = prev_vel for all K rows and no centre moves (no frame passed; rtk_object_descriptors carried the descriptors
+ *              over); object_velocity = 0.
+ *   Rows past count: vel = 0.  object_velocity past n_b: 0.
+ * beta in (0, 1] (a NaN is refused): 1 = the velocity is the last measured mean flow, smaller = exponential smoothing along the
+ * track.  One workgroup per stream, plain stores only: every run gives the same bits. */
+RTK_EXPORT int rtk_track_memory_motion(int B, int K, int max_age, float beta, const unsigned char *active, const unsigned char *reset,
+                                       const int *num_objects, const int *indices1, const float *object_conf, const int *prev_ids,
+                                       const int *prev_age, const int *prev_hits, const int *prev_n_det, const int *prev_count,
+                                       const float *desc_prev, const float *prev_vel, int *ids, int *age, int *hits, int *n_det,
+                                       int *count, float *desc, float *vel, int *flags, int *object_hits, int *object_gap,
+                                       int *num_coasted, float *object_velocity, rtk_stream_t stream);
 
 /* The largest K (max_objects) the batched association accepts: its per-stream table must fit one workgroup's LDS. */
 RTK_EXPORT int rtk_track_max_objects(void);

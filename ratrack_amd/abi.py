@@ -200,6 +200,7 @@ SIGNATURES = {
     "rtk_affinity_pairs": [_i, _i] + [_p] * 7 + [_p],
     "rtk_associate_batched": [_i] * 3 + [_p] * 7 + [_f, _i] + [_p] * 9 + [_p],
     "rtk_track_memory": [_i] * 3 + [_p] * 21 + [_p],
+    "rtk_track_memory_motion": [_i] * 3 + [_f] + [_p] * 24 + [_p],
     "rtk_track_max_objects": [],
     # ---- include/rtk_gt.h
     "rtk_gt_labels": [_p, _p, _p],

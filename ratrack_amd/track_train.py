@@ -17,7 +17,8 @@ Re-acquisition.  With `SequenceTrainer(..., reacquire=A)` the trainer's tracker 
 (`BatchedTracker(max_age=A)`) and its scorer keeps a record of the whole table (`TrackScorer(track_memory=True)`): `out.num_prev`
 counts the coasted rows too, `aff_target` has a row for each, and the term trains the MLP to give a coasted track the detection
 of the object it last was.  The training kernels need no change: they take m_b = `out.num_prev` rows, and a taller table is just
-more live pairs.
+more live pairs.  `motion="flow"` (with `reacquire`) is forwarded to the tracker: the coasted rows then move with their tracks'
+velocities.
 
 A batch with more live pairs than `max_pairs` (the workspace holds 8 KiB per pair) leaves the streams beyond the cap out of the term
 and flags them; `check()` raises naming them -- nothing is truncated silently.
@@ -195,8 +196,9 @@ def check(out):
 class _TrainTracker(T.BatchedTracker):
     """BatchedTracker's state and `associate` behind a train-mode backbone that the trainer runs itself."""
 
-    def __init__(self, net, streams, max_objects, static_state=False, max_age=None):
-        super().__init__(net, streams, max_objects=max_objects, train_mode=True, static_state=static_state, max_age=max_age)
+    def __init__(self, net, streams, max_objects, static_state=False, max_age=None, motion=None, motion_beta=1.0):
+        super().__init__(net, streams, max_objects=max_objects, train_mode=True, static_state=static_state, max_age=max_age,
+                         motion=motion, motion_beta=motion_beta)
 
     def step(self, *a, **k):
         raise RuntimeError("SequenceTrainer runs the train-mode backbone itself: use SequenceTrainer.step")
@@ -218,12 +220,16 @@ class SequenceTrainer(Trainer):
     the scorer with track_memory=True, so that the term also covers the coasted rows of the previous table (module docstring);
     the tracker's lifecycle state and the scorer's record live at fixed addresses, and graph=True replays advance them.
     `max_age` other than None is refused: a plain scorer's `aff_target` is defined against the previous frame's detections only
-    and has no target for a coasted row -- `reacquire` is the keyword that changes the scorer with the tracker."""
+    and has no target for a coasted row -- `reacquire` is the keyword that changes the scorer with the tracker.
+    motion, motion_beta (need reacquire): forwarded to the tracker (`BatchedTracker(motion="flow")`): the coasted rows of
+    `out.desc_prev` then hold centres moved on by their tracks' velocities, so the MLP is trained on the difference it will see when
+    it tracks with the same setting.  Nothing else changes: `out.desc_prev` stays detached, the training kernels take whatever rows
+    the table holds, and the scorer's record is keyed by track id."""
 
     N_GOBJ = ("slot", "label_id", "size", "count", "members", "centre", "n_valid")
 
     def __init__(self, model, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, max_pairs=None, max_age=None, reacquire=None,
-                 **trainer_kw):
+                 motion=None, motion_beta=1.0, **trainer_kw):
         if max_age is not None:
             raise ValueError("SequenceTrainer: max_age=%r: the tracking term trains against the previous frame's detections only "
                              "(track_score's aff_target has no target for a coasted track); to train with track memory give "
@@ -231,6 +237,7 @@ class SequenceTrainer(Trainer):
                              % (max_age, max_age))
         if reacquire is not None and (isinstance(reacquire, bool) or not isinstance(reacquire, int) or reacquire < 0):
             raise ValueError("reacquire=%r: None (no track memory) or an integer >= 0 (frames a lost track is kept)" % (reacquire,))
+        T.check_motion(motion, motion_beta, reacquire, "reacquire")
         if trainer_kw.get("graph") and next(model.parameters()).device.type != "cuda":
             raise ValueError("SequenceTrainer: graph=True captures the sequence step in a hipGraph and needs the model on the GPU")
         super().__init__(model, **trainer_kw)
@@ -242,7 +249,8 @@ class SequenceTrainer(Trainer):
             self.tracker = _TrainTracker(model, streams, max_objects, static_state=bool(self.graph))
             self.scorer = TrackScorer(streams=streams, max_objects=max_objects, max_boxes=max_boxes, max_gt_tracks=max_gt_tracks, device=self._dev)
         else:
-            self.tracker = _TrainTracker(model, streams, max_objects, static_state=bool(self.graph), max_age=reacquire)
+            self.tracker = _TrainTracker(model, streams, max_objects, static_state=bool(self.graph), max_age=reacquire, motion=motion,
+                                         motion_beta=motion_beta)
             self.scorer = TrackScorer(streams=streams, max_objects=max_objects, max_boxes=max_boxes, max_gt_tracks=max_gt_tracks,
                                       device=self._dev, track_memory=True)
         self.max_pairs = default_max_pairs(int(streams), int(max_objects)) if max_pairs is None else int(max_pairs)

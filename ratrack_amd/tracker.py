@@ -23,11 +23,18 @@ device and `objects`, `write_results` and `check()` raise.
 Track memory (`max_age`, off by default): the reference's rule is that the previous objects of a frame are the detections of the
 stream's last active frame and nothing else -- an object missed for one frame comes back with a fresh ID.  With
 `BatchedTracker(..., max_age=A)` the previous table of a stream is its last active frame's detections (its first `n_det` rows)
-followed by the tracks that were not matched for up to A active frames, each holding its last descriptor (no motion model); the
+followed by the tracks that were not matched for up to A active frames, each holding its last descriptor (no motion model unless `motion` asks for one, below); the
 association kernels see one table of `count` rows and need not know which is which.  A fifth launch (rtk_track_memory, rules in
 include/rtk_fused.h) advances that table on the device; `StepResult.object_hits`, `object_gap`, `num_coasted` and `prev_age` report
 the lifecycle.  Detections plus coasted tracks beyond `max_objects` rows drop the last coasted tracks and set a flag: `check()`
 raises, `objects` and `write_results` do not (what they report is complete).
+
+Motion (`motion="flow"`, off by default, needs `max_age`): every row of the table also carries a velocity -- the object's displacement
+per frame in the sensor frame, its mean predicted scene flow (descriptor channels 134..136; the flow includes the ego motion, so no
+pose is needed), smoothed along the track by `motion_beta` -- and a coasted row's centre (channels 0..2) is advanced by it every
+frame it coasts, so that the Affinity MLP sees one frame of motion in `desc_cur - desc_prev` however long the track was lost.  The
+fifth launch is then rtk_track_memory_motion (csrc/track_motion.hip) instead of rtk_track_memory; `StepResult.object_velocity` and
+`table_velocity` report the estimate.  Without `motion` a coasted track holds its last descriptor, as above.
 """
 import ctypes
 import os
@@ -111,7 +118,11 @@ class StepResult:
     (0: a detection of the last active frame; the first `num_prev` are meaningful); table_ids (B,K) int32 and table_count (B) int32:
     the table this step wrote -- the track id of every row, this frame's detections first and the coasted tracks after them, and its
     row count (the tracker's own buffers, overwritten like `descriptors`): what `TrackScorer(track_memory=True)` keeps its record
-    by."""
+    by.
+    With `BatchedTracker(motion="flow")` (else None): object_velocity (B,K,3): the velocity of object j's track after this frame's
+    measurement, metres per frame in the sensor frame (0 past num_objects and on an inactive stream); table_velocity (B,K,3): the
+    velocity of every row of the table this step wrote, aligned with `table_ids` (0 past `table_count`) -- a view of the tracker's
+    own buffer, overwritten when `table_ids` is."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -189,11 +200,26 @@ def raise_on_flags(flags, K, only=None, truncation=True):
                                "exceed max_objects=%d rows (raise max_objects)" % (b, K))
 
 
+def check_motion(motion, motion_beta, memory, memory_name):
+    """The `motion` / `motion_beta` keywords of a tracker whose track memory is switched on by the keyword `memory_name` (value
+    `memory`, None = off): raises ValueError on a combination that means nothing."""
+    if motion not in (None, "flow"):
+        raise ValueError("motion=%r: None (a coasted track holds its last descriptor) or \"flow\" (it moves with its track's velocity, "
+                         "the mean predicted scene flow)" % (motion,))
+    ok = isinstance(motion_beta, (int, float)) and not isinstance(motion_beta, bool) and 0.0 < float(motion_beta) <= 1.0
+    if not ok:
+        raise ValueError("motion_beta=%r: a number in (0, 1] (the weight of a frame's measured flow in its track's velocity)" % (motion_beta,))
+    if motion is not None and memory is None:
+        raise ValueError("motion=%r needs %s: only a track that is kept while it is lost can coast" % (motion, memory_name))
+    if motion is None and float(motion_beta) != 1.0:
+        raise ValueError("motion_beta=%r without motion: there is no velocity to smooth (give motion=\"flow\")" % (motion_beta,))
+
+
 class BatchedTracker:
     """Tracks `streams` independent sequences in lockstep (see the module docstring)."""
 
     def __init__(self, net, streams, max_objects=128, iters=500, alpha=0.9, eps=1.5, threshold=0.5, train_mode=False,
-                 static_state=False, graph=False, graph_warmup=2, engine=None, max_age=None):
+                 static_state=False, graph=False, graph_warmup=2, engine=None, max_age=None, motion=None, motion_beta=1.0):
         """train_mode: accept a train-mode net -- for a caller that runs the backbone itself and uses `associate` and the state only
         (track_train.SequenceTrainer); `step()` stays the eval-mode path.
         static_state: this frame's objects are always written to slot 0 of `desc` / `ids` / `count` and the previous objects read
@@ -211,9 +237,17 @@ class BatchedTracker:
         max_age: None (default): the reference's rule, the tracker as it is without track memory -- no further launch or buffer, the
         four lifecycle fields of `StepResult` are None.  An integer A >= 0: a track that is not matched stays in the stream's table
         for up to A active frames (module docstring); 0 keeps the bookkeeping (hits, gap) and lets nothing coast.  A launch constant:
-        a captured step replays it as it was."""
+        a captured step replays it as it was.
+        motion: None (default): a coasted track holds its last descriptor -- the tracker as it is without the keyword: the same
+        launches, no further buffer, `StepResult.object_velocity` and `table_velocity` are None.  "flow" (needs max_age): every
+        row carries a velocity taken from its object's mean predicted scene flow and a coasted row's centre moves by it every frame
+        (module docstring; rules in include/rtk_fused.h, rtk_track_memory_motion, which replaces rtk_track_memory).
+        motion_beta in (0, 1]: the weight of this frame's measured flow in an inherited track's velocity, v + beta (flow - v); a
+        fresh track starts at its flow.  The default 1.0 makes the velocity the last measured mean flow: tracking quality has not
+        been measured on real sequences here, so no smoothing default can be justified.  A launch constant, like max_age."""
         if max_age is not None and (isinstance(max_age, bool) or not isinstance(max_age, int) or max_age < 0):
             raise ValueError("max_age=%r: None (no track memory) or an integer >= 0 (frames a lost track is kept)" % (max_age,))
+        check_motion(motion, motion_beta, max_age, "max_age")
         if net.training and not train_mode:
             raise ValueError("BatchedTracker runs the eval-mode (fused) backbone: call net.eval() first")
         kmax = max_objects_limit()
@@ -239,6 +273,10 @@ class BatchedTracker:
             self.age = torch.zeros(2, B, K, dtype=torch.int32, device=dev)
             self.hits = torch.zeros(2, B, K, dtype=torch.int32, device=dev)
             self.n_det = torch.zeros(2, B, dtype=torch.int32, device=dev)
+        self.motion, self.motion_beta = motion, float(motion_beta)
+        self.vel = None
+        if motion is not None:         # every row's velocity, metres per frame
+            self.vel = torch.zeros(2, B, K, 3, device=dev)
         self.cur = 0
         self._work = None
         self.last = None
@@ -318,7 +356,7 @@ class BatchedTracker:
 
     def associate(self, pc1, feature1, flow, cls, prop, n_valid, reset, active):
         """The post-backbone half of step(): four launches, the state swap (static_state: the state advance first, five launches);
-        with max_age one more, rtk_track_memory; no host synchronisation.  reset / active (B,) uint8 and n_valid (2,B) int32 (or
+        with max_age one more, rtk_track_memory (with motion: rtk_track_memory_motion in its place); no host synchronisation.  reset / active (B,) uint8 and n_valid (2,B) int32 (or
         None) are device tensors."""
         B, K = self.B, self.K
         N = pc1.shape[2]
@@ -331,6 +369,7 @@ class BatchedTracker:
             from .fused import copy_multi
             cur, prev = 0, 1
             state = [self.desc, self.ids, self.count] + ([] if self.max_age is None else [self.age, self.hits, self.n_det])
+            state += [] if self.vel is None else [self.vel]                # seven of the launch's eight jobs
             copy_multi([(t[1], t[0]) for t in state])
         else:
             cur, prev = self.cur, 1 - self.cur
@@ -352,12 +391,25 @@ class BatchedTracker:
                   self.ids[prev].data_ptr(), self.count[prev].data_ptr(), self.alpha, self.iters, self.counter.data_ptr(),
                   self.ids[cur].data_ptr(), self.count[cur].data_ptr(), object_ids.data_ptr(), object_conf.data_ptr(), indices1.data_ptr(),
                   num_prev.data_ptr(), point_track_id.data_ptr(), None, st)
-        memory = dict(object_hits=None, object_gap=None, num_coasted=None, prev_age=None, table_ids=None, table_count=None)
-        if self.max_age is not None:
+        memory = dict(object_hits=None, object_gap=None, num_coasted=None, prev_age=None, table_ids=None, table_count=None,
+                      object_velocity=None, table_velocity=None)
+        if self.motion is not None:
+            # the next table as below, its rows' velocities, and the survivors' centres moved on by one frame
+            memory.update(object_hits=i32(B, K), object_gap=i32(B, K), num_coasted=i32(B), prev_age=self.age[prev],
+                          table_ids=self.ids[cur], table_count=self.count[cur], object_velocity=torch.empty(B, K, 3, device=dev),
+                          table_velocity=self.vel[cur])
+            _lib.call("rtk_track_memory_motion", B, K, self.max_age, self.motion_beta, active.data_ptr(), reset.data_ptr(), num.data_ptr(),
+                      indices1.data_ptr(), object_conf.data_ptr(), self.ids[prev].data_ptr(), self.age[prev].data_ptr(),
+                      self.hits[prev].data_ptr(), self.n_det[prev].data_ptr(), self.count[prev].data_ptr(), desc_prev.data_ptr(),
+                      self.vel[prev].data_ptr(), self.ids[cur].data_ptr(), self.age[cur].data_ptr(), self.hits[cur].data_ptr(),
+                      self.n_det[cur].data_ptr(), self.count[cur].data_ptr(), desc.data_ptr(), self.vel[cur].data_ptr(), flags.data_ptr(),
+                      memory["object_hits"].data_ptr(), memory["object_gap"].data_ptr(), memory["num_coasted"].data_ptr(),
+                      memory["object_velocity"].data_ptr(), st)
+        elif self.max_age is not None:
             # the next table: this frame's detections, then the unmatched previous rows that are still young enough
-            memory = dict(object_hits=i32(B, K), object_gap=i32(B, K), num_coasted=i32(B), prev_age=self.age[prev],
+            memory.update(object_hits=i32(B, K), object_gap=i32(B, K), num_coasted=i32(B), prev_age=self.age[prev],
                           table_ids=self.ids[cur], table_count=self.count[cur])
-            _lib.call("rtk_track_memory", B, K, self.max_age, active.data_ptr(), reset.data_ptr(), num.data_ptr(), indices1.data_ptr(),
+            _lib.call("rtk_track_memory",B, K, self.max_age, active.data_ptr(), reset.data_ptr(), num.data_ptr(), indices1.data_ptr(),
                       object_conf.data_ptr(), self.ids[prev].data_ptr(), self.age[prev].data_ptr(), self.hits[prev].data_ptr(),
                       self.n_det[prev].data_ptr(), self.count[prev].data_ptr(), desc_prev.data_ptr(), self.ids[cur].data_ptr(),
                       self.age[cur].data_ptr(), self.hits[cur].data_ptr(), self.n_det[cur].data_ptr(), self.count[cur].data_ptr(),

@@ -3,6 +3,7 @@ max_age=None step of a checkout of the parent commit on the same machine.
 
     python tools/time_track_memory.py [--parent DIR] [--rounds 5] [--streams 64] [--points 256] [--max-objects 128] [--iters 100]
                                       [--warmup 10] [--out profiles/track_memory_timing.json]
+    python tools/time_track_memory.py --motion [--parent DIR] [--rounds 3] ... [--out profiles/track_motion_timing.json]
 
 Every measurement is a process of its own (this one starts them and never touches the GPU itself); the processes of one round run one
 after the other, this tree and the parent's (--parent: a checkout of the parent commit with its library built) alternating, so that a
@@ -11,6 +12,9 @@ in rotation (synth.make_frame_pairs, synthetic weights with the segmentation hea
 associate and lose) and reports the median device time between events around step(); the eager ones also the median time of the
 rtk_track_memory launch and of the four association launches (`_lib.TIMING`).  Per configuration the JSON holds the median and the
 spread (min, max) over the rounds.  max_age=None executes no new code: it must sit inside the run-to-run spread of the parent.
+--motion: what a motion model for the coasted tracks costs, by the same protocol: max_age=2 without motion (no new code: inside the
+spread of the parent's max_age=2), max_age=2 with motion="flow" (--motion-beta), and the parent's max_age=2; the eager processes report
+the rtk_track_memory launch or the rtk_track_memory_motion launch that replaces it, measured in the same session.
 Not part of bench.py."""
 import argparse
 import json
@@ -41,6 +45,8 @@ def measure(a):
     sd["fd_layer.cp.linear.bias"].add_(a.moving_bias)
     net.invalidate_fused()
     kw = {} if a.max_age == "none" else dict(max_age=int(a.max_age))
+    if a.motion_kw != "none":
+        kw.update(motion=a.motion_kw, motion_beta=a.motion_beta)
     trk = T.BatchedTracker(net, streams=B, max_objects=a.max_objects, graph=a.mode == "graph", **kw)
     state = {"i": 0}
 
@@ -77,15 +83,17 @@ def measure(a):
                 per.setdefault(name, []).append(e0.elapsed_time(e1))
             _lib.TIMING = None
             res["four_association_launches_ms"] = round(sum(statistics.median(per[k]) for k in ASSOC), 4)
-            if "rtk_track_memory" in per:
-                res["rtk_track_memory_ms"] = round(statistics.median(per["rtk_track_memory"]), 4)
+            for name in ("rtk_track_memory", "rtk_track_memory_motion"):
+                if name in per:
+                    res[name + "_ms"] = round(statistics.median(per[name]), 4)
         res["captured"] = bool(getattr(trk, "captured", False))
         res["device"] = torch.cuda.get_device_name(0)
     print("RESULT " + json.dumps(res), flush=True)
 
 
-def child(a, root, max_age, mode):
+def child(a, root, max_age, mode, motion="none"):
     cmd = [sys.executable, os.path.abspath(__file__), "--one", "--root", root, "--max-age", str(max_age), "--mode", mode,
+           "--motion-kw", motion, "--motion-beta", str(a.motion_beta),
            "--streams", str(a.streams), "--points", str(a.points), "--max-objects", str(a.max_objects), "--iters", str(a.iters),
            "--warmup", str(a.warmup), "--moving-bias", str(a.moving_bias)]
     out = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.timeout, check=True).stdout.decode()
@@ -103,7 +111,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--moving-bias", type=float, default=4.0, help="added to the segmentation head's bias")
     ap.add_argument("--timeout", type=float, default=240.0, help="seconds a measuring process may take")
-    ap.add_argument("--out", default=os.path.join("profiles", "track_memory_timing.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/track_memory_timing.json, with --motion profiles/track_motion_timing.json")
+    ap.add_argument("--motion", action="store_true", help="measure max_age=2 with and without motion=\"flow\" (and the parent's max_age=2)")
+    ap.add_argument("--motion-beta", type=float, default=1.0)
+    ap.add_argument("--motion-kw", default="none", choices=("none", "flow"), help="(internal) the motion keyword of the one configuration")
     ap.add_argument("--one", action="store_true", help="(internal) measure one configuration in this process")
     ap.add_argument("--root", default=HERE)
     ap.add_argument("--max-age", default="none")
@@ -111,14 +122,19 @@ def main():
     a = ap.parse_args()
     if a.one:
         return measure(a)
-    configs = [("this", HERE, "none"), ("this", HERE, 2)] + ([("parent", a.parent, "none")] if a.parent else [])
+    if a.out is None:
+        a.out = os.path.join("profiles", "track_motion_timing.json" if a.motion else "track_memory_timing.json")
+    if a.motion:
+        configs = [("this", HERE, 2, "none"), ("this", HERE, 2, "flow")] + ([("parent", a.parent, 2, "none")] if a.parent else [])
+    else:
+        configs = [("this", HERE, "none", "none"), ("this", HERE, 2, "none")] + ([("parent", a.parent, "none", "none")] if a.parent else [])
     runs = {}
     for r in range(a.rounds):
         for mode in ("eager", "graph"):
             order = configs if r % 2 == 0 else configs[::-1]          # the trees alternate, and who goes first alternates too
-            for tree, root, max_age in order:
-                key = "%s/max_age=%s/%s" % (tree, max_age, mode)
-                runs.setdefault(key, []).append(child(a, root, max_age, mode))
+            for tree, root, max_age, motion in order:
+                key = "%s/max_age=%s%s/%s" % (tree, max_age, "" if motion == "none" else ",motion=" + motion, mode)
+                runs.setdefault(key, []).append(child(a, root, max_age, mode, motion))
                 print(key, runs[key][-1], flush=True)
     res = {"what": "BatchedTracker.step, device ms between events, median of --iters per process; per configuration the median, min and "
                    "max over the rounds (one process each, the trees alternating)",
@@ -127,17 +143,19 @@ def main():
     for key, rs in runs.items():
         ms = [x["step_ms"] for x in rs]
         c = dict(step_ms_median=round(statistics.median(ms), 4), step_ms_min=min(ms), step_ms_max=max(ms), step_ms_runs=ms)
-        for k in ("four_association_launches_ms", "rtk_track_memory_ms"):
+        for k in ("four_association_launches_ms", "rtk_track_memory_ms", "rtk_track_memory_motion_ms"):
             if k in rs[0]:
                 c[k + "_median"] = round(statistics.median(x[k] for x in rs), 4)
+                c[k + "_runs"] = [x[k] for x in rs]
         for k in ("detected_objects", "previous_rows", "coasted_rows", "streams_truncated", "captured"):
             if k in rs[0]:
                 c[k] = rs[-1][k]
         res["configurations"][key] = c
     if a.parent:
+        same = "2" if a.motion else "none"          # the configuration that executes no new code, in both trees
         for mode in ("eager", "graph"):
-            p, t = res["configurations"]["parent/max_age=none/" + mode], res["configurations"]["this/max_age=none/" + mode]
-            res["max_age_none_inside_parent_spread_" + mode] = bool(p["step_ms_min"] <= t["step_ms_median"] <= p["step_ms_max"])
+            p, t = res["configurations"]["parent/max_age=%s/%s" % (same, mode)], res["configurations"]["this/max_age=%s/%s" % (same, mode)]
+            res["max_age_%s_inside_parent_spread_%s" % (same, mode)] = bool(p["step_ms_min"] <= t["step_ms_median"] <= p["step_ms_max"])
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
