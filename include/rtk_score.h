@@ -37,6 +37,7 @@ extern "C" {
 #define RTK_SCORE_FLAG_LOG 16        /* rtk_track_score_logged: a frame did not fit the stream's log and was not logged at all */
 #define RTK_SCORE_FLAG_SWEEP 32      /* rtk_score_track_means: more track ids in one clip than RTK_SCORE_SWEEP_TRACKS (no score written) */
 #define RTK_SCORE_FLAG_TABLE 64      /* rtk_track_score_memory: a table_count outside [num_objects, Kobj] (clamped) */
+#define RTK_SCORE_FLAG_HOTA 128      /* rtk_score_hota: a clip with more labels, track ids or pairs than its tables hold (outputs unspecified) */
 
 /* LDS bytes of one workgroup for these sizes (host functions: no device is touched). */
 RTK_EXPORT int rtk_gt_objects_lds_bytes(int K, int N);
@@ -228,6 +229,52 @@ RTK_EXPORT int rtk_score_thresholds(const double *sorted, const long long *n, co
 RTK_EXPORT int rtk_score_replay(int B, int T, const rtk_score_log_t *log, const double *rec_score, const double *thresholds,
                                 const int *reached, int count, long long *counters, double *iou_sum, unsigned char *tp_mask,
                                 rtk_stream_t stream);
+
+/* ---- HOTA: DetA, AssA, LocA (csrc/track_hota.hip, TrackScorer.hota) --------------------------------------------------------------
+ *
+ * The metric of Luiten et al., "HOTA: A Higher Order Metric for Evaluating Multi-Object Tracking", over the same log, under
+ * rtk_track_score's matching rule and the reference's point IoU.  TrackEval's own numbers use a Hungarian assignment on box IoU:
+ * these are NOT those, as the sweep's are not the reference README's table.
+ *   levels       A of them (19 by default), alpha_a = (double)a / (double)(A + 1) for a = 1..A (0.05 ... 0.95).
+ *   removal      clip, log, track score and the removal by a threshold t are the sweep's: a detection whose track score is < t is
+ *                removed -- it is no prediction, belongs to no track and takes nothing.  No rec_score, no threshold or
+ *                t = -infinity removes nothing.
+ *   candidate    per (stream, alpha_a), frames in log order: a remaining detection with a best label (rec_best != -1) and
+ *                rec_iou >= alpha_a (float64 >=; both are correctly rounded quotients, so an IoU of 3/5 is a candidate at
+ *                alpha = 12/20).  A remaining detection that is no candidate takes nothing and is a false positive at this alpha,
+ *                and THE OBJECT STAYS FREE for a later detection: threshold first, then match, as TrackEval zeroes the pairs below
+ *                alpha before it matches -- not "replay, then drop the weak matches".
+ *   match        candidates in detection order take their best object; taken by an earlier candidate: unmatched, no second
+ *                choice.  A match is a true positive (label g, track t, IoU).
+ *   per clip     cg[g] the frames of the clip whose kept labels contain g; ct[t] the remaining detections of the clip with track
+ *                id t (neither depends on alpha); n[g,t] the true positives of the pair.  A clip closes at a reset frame or at the
+ *                end of the log.
+ *   counters     running over the stream: frames | clips | gt = sum cg | pred = sum ct | tp = sum n | pairs = the distinct (g,t)
+ *                with n > 0.  Hence fn = gt - tp and fp = pred - tp.
+ *   sums         each one running float64 from 0 over the whole stream: loc gains a true positive's IoU when it is matched, in
+ *                log order; at a clip's close, for its pairs IN ORDER OF FIRST APPEARANCE (frame order, then detection order), with
+ *                N = (double)(n*n) from the integer product: ass += N / (double)(cg + ct - n), ass_re += N / (double)cg,
+ *                ass_pr += N / (double)ct -- one division and one addition each, no FMA contraction.
+ *   host         float64, the streams pooled in stream order, per alpha: DetA = TP/(TP+FN+FP), DetRe = TP/(TP+FN),
+ *                DetPr = TP/(TP+FP), AssA = ass/TP, AssRe = ass_re/TP, AssPr = ass_pr/TP, LocA = loc/TP,
+ *                HOTA_alpha = sqrt(DetA * AssA); a ratio without a denominator is NaN.  HOTA, DetA, AssA, DetRe, DetPr, AssRe,
+ *                AssPr, LocA are the sums over alpha, in alpha order, of the non-NaN terms, divided by A (AMOTP's rule).
+ * The device produces the integers and the four sums; every ratio is host arithmetic (track_score.py, hota_values). */
+#define RTK_SCORE_HOTA_COUNTERS 6    /* frames | clips | gt | pred | tp | pairs */
+#define RTK_SCORE_HOTA_SUMS 4        /* ass | ass_re | ass_pr | loc */
+/* Most distinct (label id, track id) pairs of one clip of one stream (an insertion-ordered list with a lookup table in LDS). */
+#define RTK_SCORE_HOTA_PAIRS 1024
+
+/* Grid (stream, alpha index): counters (alphas,B,6) and sums (alphas,B,4) of level a = index + 1 of `alphas` levels (1..63).  T bounds
+ * the label ids of one clip (rtk_track_score's T; a T whose tables do not fit RTK_SCORE_LDS_LIMIT is refused), and
+ * RTK_SCORE_SWEEP_TRACKS its track ids.  A clip of stream b with more labels than T, more track ids than RTK_SCORE_SWEEP_TRACKS or
+ * more pairs than RTK_SCORE_HOTA_PAIRS raises RTK_SCORE_FLAG_HOTA in flags[b] (or-ed in; nothing else of flags is touched): that
+ * stream's outputs are then unspecified but written, the other streams are unaffected.  Reads the log, rec_score and threshold and
+ * writes only its three outputs. */
+RTK_EXPORT int rtk_score_hota(int B, int T, const rtk_score_log_t *log, const double *rec_score /* (B,R) or NULL */,
+                              const double *threshold /* device scalar, or NULL: nothing removed */, int alphas,
+                              long long *counters /* (alphas,B,6) */, double *sums /* (alphas,B,4) */, int *flags /* (B) */,
+                              rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

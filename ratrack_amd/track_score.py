@@ -65,8 +65,21 @@ under a fresh ID); both get the 1, on purpose: both rows are that object.  `aff_
 no kept ground-truth object but a coasted row remembers one.  A plain `TrackScorer` may still score a memory tracker -- its counters
 are right -- but its target has no row for a coasted track.
 
-Nothing here synchronises with the device except `GtObjects.check()`, `TrackScorer.check()`, `TrackScorer.result()` and
-`TrackScorer.sweep()`.
+HOTA.  `scorer.hota(alphas=19)` evaluates HOTA with its parts DetA, AssA and LocA (Luiten et al., "HOTA: A Higher Order Metric for
+Evaluating Multi-Object Tracking") over the same log, in one launch and one download -- two launches with `threshold=`, for instance
+`scorer.hota(threshold=sw.best["threshold"])`, which removes the detections the sweep removes at that threshold:
+
+    ho = scorer.hota()                              # HotaResult: hota, deta_mean, assa_mean, loca_mean, per-alpha arrays
+
+AssA is the share of a trajectory that carries one track id: what CLEAR-MOT's single `idsw` integer cannot say and what track memory
+is there to raise.  THIS IS HOTA UNDER THIS MODULE'S MATCHING RULE AND THE REFERENCE'S POINT IoU: per level alpha (a / (A + 1)), a
+remaining detection is a candidate when its pre-greedy best object has IoU >= alpha; candidates take their best object in detection
+order, first come first served, and a detection below alpha takes nothing (threshold first, then match).  TrackEval's own numbers use
+a Hungarian assignment on box IoU and are not these.  The definitions are in include/rtk_score.h; the device delivers integers and
+four fixed-order float64 sums, `hota_values` is the arithmetic.
+
+Nothing here synchronises with the device except `GtObjects.check()`, `TrackScorer.check()`, `TrackScorer.result()`,
+`TrackScorer.sweep()` and `TrackScorer.hota()`.
 """
 import ctypes
 
@@ -86,6 +99,10 @@ FLAG_BOXES, FLAG_NVALID, FLAG_TRACKS, FLAG_OBJECTS = 1, 2, 4, 8
 FLAG_LOG, FLAG_SWEEP = 16, 32          # RTK_SCORE_FLAG_LOG, RTK_SCORE_FLAG_SWEEP
 FLAG_TABLE = 64                        # RTK_SCORE_FLAG_TABLE
 SWEEP_TRACKS = 2048                    # RTK_SCORE_SWEEP_TRACKS
+FLAG_HOTA = 128                        # RTK_SCORE_FLAG_HOTA
+HOTA_COUNTERS = ("frames", "clips", "gt", "pred", "tp", "pairs")
+HOTA_SUMS = ("ass", "ass_re", "ass_pr", "loc")
+HOTA_PAIRS = 1024                      # RTK_SCORE_HOTA_PAIRS
 
 
 # ---- what fits -------------------------------------------------------------------------------------------------------------
@@ -282,6 +299,49 @@ def sweep_values(counters, iou_sums, thresholds, reached, levels):
     return out
 
 
+class HotaResult:
+    """What `TrackScorer.hota` returns (host values; definitions in include/rtk_score.h).  `alphas` A and `alpha` (A) float64, the
+    levels a / (A + 1).  Per-level arrays of length A, pooled over the streams: tp, fn, fp, gt, pred, pairs (integers) and deta, detre,
+    detpr, assa, assre, asspr, loca, hota_alpha (NaN where the denominator is 0).  Scalars, each the sum over the levels of the
+    non-NaN terms divided by A: hota, deta_mean, assa_mean, detre_mean, detpr_mean, assre_mean, asspr_mean, loca_mean.  `counters`
+    (A,B,6) int64 in HOTA_COUNTERS order and `sums` (A,B,4) float64 in HOTA_SUMS order per stream; `flags` (B); `threshold` (None
+    or the float the detections were filtered with)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def hota_values(counters, sums):
+    """HOTA's arithmetic, host only: counters (A,S,6) integer counts in HOTA_COUNTERS order and sums (A,S,4) float64 in HOTA_SUMS order
+    of A levels and any number S of streams -> dict with the fields of `HotaResult` except flags and threshold.  Counts are pooled over
+    the streams and the sums added in stream order; float64 throughout.  A level without a denominator is NaN and adds nothing to the
+    means, whose divisor stays A."""
+    c = np.asarray(counters, dtype=np.int64)
+    q = np.asarray(sums, dtype=np.float64)
+    if c.ndim != 3 or c.shape[2] != len(HOTA_COUNTERS) or q.shape != c.shape[:2] + (len(HOTA_SUMS),) or c.shape[0] < 1:
+        raise ValueError("hota_values: counters %s and sums %s are not (A,S,%d) and (A,S,%d)" % (c.shape, q.shape, len(HOTA_COUNTERS), len(HOTA_SUMS)))
+    A = c.shape[0]
+    pooled = c.sum(axis=1)
+    qs = np.cumsum(q, axis=1)[:, -1] if q.shape[1] else np.zeros((A, len(HOTA_SUMS)))       # cumsum: one addition after the other
+    g = lambda k: pooled[:, HOTA_COUNTERS.index(k)].astype(np.float64)
+    tp, fn, fp = g("tp"), g("gt") - g("tp"), g("pred") - g("tp")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        val = dict(deta=tp / (tp + fn + fp), detre=tp / (tp + fn), detpr=tp / (tp + fp), assa=qs[:, 0] / tp, assre=qs[:, 1] / tp,
+                   asspr=qs[:, 2] / tp, loca=qs[:, 3] / tp)
+        val["hota_alpha"] = np.sqrt(val["deta"] * val["assa"])
+    out = dict(alphas=A, alpha=np.arange(1, A + 1, dtype=np.float64) / float(A + 1), counters=c, sums=q, **val)
+    for k in ("tp", "gt", "pred", "pairs"):
+        out[k] = pooled[:, HOTA_COUNTERS.index(k)].copy()
+    out["fn"], out["fp"] = out["gt"] - out["tp"], out["pred"] - out["tp"]
+    for k, name in (("hota_alpha", "hota"),) + tuple((n, n + "_mean") for n in ("deta", "assa", "detre", "detpr", "assre", "asspr", "loca")):
+        acc = 0.0
+        for v in val[k]:                                                                 # in level order: fixed bits
+            if not np.isnan(v):
+                acc += float(v)
+        out[name] = acc / A
+    return out
+
+
 class TrackScorer:
     """Matches the detections of `streams` sequences to their ground-truth objects frame by frame and keeps the score on the device
     (see the module docstring).  State (device tensors): counters (B,11) int64 in COUNTERS order, iou_sum (B) float64, the table of
@@ -426,6 +486,9 @@ class TrackScorer:
                                    "sweep_records=%d records and was not logged (raise them)" % (b, self.F, self.R))
             if f & FLAG_SWEEP:
                 raise RuntimeError("TrackScorer.sweep: stream %d has more than %d track ids in one clip" % (b, SWEEP_TRACKS))
+            if f & FLAG_HOTA:
+                raise RuntimeError("TrackScorer.hota: stream %d has a clip with more than max_gt_tracks=%d label ids, %d track ids or %d "
+                                   "(label id, track id) pairs" % (b, self.T, SWEEP_TRACKS, HOTA_PAIRS))
 
     def check(self):
         """Synchronises.  Raises RuntimeError naming the stream whose track table overflowed or whose sizes were out of range."""
@@ -504,3 +567,42 @@ class TrackScorer:
         if check:
             self._raise_on_flags(fl.tolist())
         return SweepResult(flags=fl, **sweep_values(counters, iou_sums, thresholds, k, L))
+
+    def hota(self, alphas=19, threshold=None, check=True):
+        """HOTA, DetA, AssA and LocA over the log (module docstring; definitions in include/rtk_score.h) at `alphas` levels
+        a / (alphas + 1).  threshold None: every logged detection counts, one launch.  A float or a 0-dim tensor (for instance
+        `sweep().best["threshold"]`): the detections whose track score is below it are removed as the sweep removes them, two
+        launches (track scores, then HOTA).  Then one download.  The running state and the log are only read: scoring may go on.
+        check: raise (naming the stream) on any sticky flag and on a clip that overflowed HOTA's tables; check=False returns the
+        other streams' numbers (`flags` tells which to leave out).  -> HotaResult."""
+        if not self.logging:
+            raise RuntimeError("TrackScorer.hota: the scorer keeps no log (give sweep_frames and sweep_records)")
+        A = int(alphas)
+        if not 1 <= A <= 63:
+            raise ValueError("alphas=%d outside [1, 63]" % A)
+        B, dev, nc, ns = self.B, self.counters.device, len(HOTA_COUNTERS), len(HOTA_SUMS)
+        lg = self._log_block()
+        lgp, st = ctypes.addressof(lg), _stream()
+        flags = self.flags.clone()
+        score = thr = None
+        if threshold is not None:
+            thr = torch.as_tensor(threshold, dtype=torch.float64).reshape(1).to(dev)
+            score = torch.zeros(B, self.R, dtype=torch.float64, device=dev)
+            _lib.call("rtk_score_track_means", B, lgp, score.data_ptr(), flags.data_ptr(), st)
+        c = torch.empty(A, B, nc, dtype=torch.int64, device=dev)
+        q = torch.empty(A, B, ns, dtype=torch.float64, device=dev)
+        _lib.call("rtk_score_hota", B, self.T, lgp, None if score is None else score.data_ptr(), None if thr is None else thr.data_ptr(), A,
+                  c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
+        parts = [c.reshape(-1), q.reshape(-1).view(torch.int64), flags.long()]
+        if thr is not None:
+            parts.append(thr.view(torch.int64))
+        host = torch.cat(parts).cpu().numpy()
+        o = A * B * nc
+        counters = host[:o].reshape(A, B, nc).copy()
+        sums = host[o:o + A * B * ns].copy().view(np.float64).reshape(A, B, ns)
+        o += A * B * ns
+        fl = host[o:o + B].copy()
+        tau = None if thr is None else float(host[o + B:].copy().view(np.float64)[0])
+        if check:
+            self._raise_on_flags(fl.tolist())
+        return HotaResult(flags=fl, threshold=tau, **hota_values(counters, sums))
