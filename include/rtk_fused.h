@@ -116,6 +116,15 @@ RTK_EXPORT int rtk_sa_scale(int samples, int n, int npoint, int nsample, const f
                             int out_pitch, int out_offset, const int *src_nuniq, const int *dst_nuniq,
                             rtk_stream_t stream);
 
+/* rtk_sa_scale with the tile loop as it was before it was software-pipelined (one unit's loads requested, waited for and used
+ * before the next unit's go out).  Same arguments, bit-identical result; the comparison implementation of tests and timing tools,
+ * not called by the package. */
+RTK_EXPORT int rtk_sa_scale_serial(int samples, int n, int npoint, int nsample, const float *xyz,
+                                   const float *new_xyz, const int *idx, const float *q, int q_pitch, int c1_16,
+                                   const float *w1xyz_packed, int nlayers, const rtk_layer_t *layers, float *out,
+                                   int out_pitch, int out_offset, const int *src_nuniq, const int *dst_nuniq,
+                                   rtk_stream_t stream);
+
 /* Point-to-patch cost volume for k = 16 neighbours.  p1 (samples*n1, 256) / p2 (samples*n2, 256):
  * first-layer projections of the query / neighbour features (bias folded into p1);
  * layer 1 = leaky(p1[i] + p2[idx] + Wd.(xyz2[idx] - xyz1[i])), then layers[0..1] (256->256, leaky),
@@ -195,6 +204,12 @@ RTK_EXPORT int rtk_sa_scale_split(int samples, int n, int npoint, int nsample, c
                                   const int *idx, const float *q, int q_pitch, int c1, const float *w1xyz_packed,
                                   const void *split_image, const float *image_scale, const float *bias2, float *out, int out_pitch,
                                   int out_offset, const int *src_nuniq, const int *dst_nuniq, rtk_stream_t stream);
+/* ... with the serial tile loop: see rtk_sa_scale_serial.  Same arguments, bit-identical result. */
+RTK_EXPORT int rtk_sa_scale_split_serial(int samples, int n, int npoint, int nsample, const float *xyz, const float *new_xyz,
+                                         const int *idx, const float *q, int q_pitch, int c1, const float *w1xyz_packed,
+                                         const void *split_image, const float *image_scale, const float *bias2, float *out,
+                                         int out_pitch, int out_offset, const int *src_nuniq, const int *dst_nuniq,
+                                         rtk_stream_t stream);
 RTK_EXPORT int rtk_split_mlp2(int positions, const float *x, const void *images, const float *image_scales, const float *bias1,
                               const float *bias2, float *y, rtk_stream_t stream);
 

@@ -169,6 +169,7 @@ SIGNATURES = {
     "rtk_pointwise_mlp_tap": [_i, _i, P(Interp), P(Layer), _p, _i, _p, P(Layer), _i, _p, _i, _p],
     "rtk_pointwise_mlp_pair": [_i, _i, _i, P(Src), _p, P(Layer), _p, _i, _i, _i, P(Layer), _p, _i, _p],
     "rtk_sa_scale": [_i] * 4 + [_p] * 4 + [_i, _i, _p, _i, P(Layer), _p, _i, _i, _p, _p, _p],
+    "rtk_sa_scale_serial": [_i] * 4 + [_p] * 4 + [_i, _i, _p, _i, P(Layer), _p, _i, _i, _p, _p, _p],
     "rtk_cost_volume": [_i] * 3 + [_p] * 6 + [P(Layer), P(Layer), _p, _i, _p],
     "rtk_patch_cost": [_i] * 2 + [_p] * 3 + [_i, P(Layer), _p, _i, _i, _p],
     "rtk_patch_cost_wave16": [_i] * 2 + [_p] * 3 + [_i, P(Layer), _p, _i, _i, _p],
@@ -178,6 +179,7 @@ SIGNATURES = {
     "rtk_cost_volume_split_gconst": [_i] * 3 + [_p] * 10 + [P(Layer), _p, _i, _i, _p],
     "rtk_cost_volume_split_term": [_i] * 3 + [_p] * 11 + [P(Layer), _p, _i, _i, _p],
     "rtk_sa_scale_split": [_i] * 4 + [_p] * 4 + [_i, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p],
+    "rtk_sa_scale_split_serial": [_i] * 4 + [_p] * 4 + [_i, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p],
     "rtk_split_mlp2": [_i, _p, _p, _p, _p, _p, _p, _p],
     "rtk_prepare_inputs": [_i] * 2 + [_p] * 6 + [_p],
     "rtk_fps_centroids": [_i] * 3 + [_p] * 8 + [_p],

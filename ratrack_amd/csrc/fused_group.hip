@@ -46,7 +46,9 @@ struct SaParams {
 };
 
 // NS = neighbours per centroid; V1/V2/V3 = layer widths / 16 (V3 = 0: two-layer MLP).
-template <int NS, int V1, int V2, int V3>
+// PIPE (one tile per unit, NS <= 16): the tile loop software-pipelined by one unit (the first of the two loops below).  false: the loop as
+// it was before (rtk_sa_scale_serial, the comparison implementation); the two compute the same bits.
+template <int NS, int V1, int V2, int V3, bool PIPE>
 __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
     const float kinf = rtk_hidden_inf();
     constexpr int NF = V1 * V2 + V2 * V3;
@@ -75,6 +77,106 @@ __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
     for (int v = 0; v < V1; ++v) w1[v] = P.w1[v * 64 + lane];
     __syncthreads();
     const int slot0 = j % NS;                         // neighbour slot of this lane within the first tile
+    if constexpr (PIPE && TILES == 1) {
+        // The serial loop below makes six dependent round trips per 16-position tile (src_nuniq + centroid, index, neighbour, q row +
+        // bias2, bias3 twice), each closed by a full wait, around ~420 cycles of MFMAs.  Here everything that does not change from
+        // tile to tile is read once (src_nuniq per workgroup, the bias fragments per wave, into registers), lanes g == 3 load
+        // component 2 and select their constant afterwards (no branch around a load), and the gathers of unit u + 1 are in flight
+        // under the MFMA chain of unit u: its ball index and centroid are requested at the top of u, its neighbour coordinate and q
+        // row -- into registers of their own -- in front of u's layers 2 and 3.  Whether a next unit exists is wave-uniform; without
+        // one nothing is requested.  The lanes past live_c are redirected before every index load exactly as in the serial loop, so
+        // this loop reads the rows the serial one reads and no others.  Same operations on the same values: the same bits.
+        const int src_e = P.src_nuniq ? __builtin_amdgcn_readfirstlane(P.src_nuniq[b]) : 0x7fffffff;
+        const int gc = g < 3 ? g : 2;
+        f4 b2[V3 ? V2 : 1], bl[VL];
+        if constexpr (V3 != 0) {
+#pragma unroll
+            for (int v = 0; v < V2; ++v) b2[v] = bias_frag(P.bias2, v, g);
+        }
+#pragma unroll
+        for (int v = 0; v < VL; ++v) bl[v] = bias_frag(V3 ? P.bias3 : P.bias2, v, g);
+        const int stride = nbx * 4;
+        int unit = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (an SGPR: the loop's branches are scalar)
+        if (unit >= live_groups) return;                       // (no barrier follows)
+        // state of the unit in work (c, valid, cg and -- requested, not waited for -- nx, a1) and of the one after it (*_n)
+        int c, c_n = 0, id_n = 0;
+        bool valid, valid_n = false;
+        float cg, nx, cg_n = 0.f, nx_n = 0.f;
+        f4 a1[V1], a1n[V1];
+        auto centroid_of = [&](int u, int &cc, bool &vv) {        // global centroid index of this lane in unit u, redirected past live_c
+            int cl = u * CPT + j / NS;
+            vv = cl < live_c;
+            if (!vv) cl = live_c - 1;
+            cc = b * P.npoint + cl;
+        };
+        auto gather = [&](int id, float &x, f4 (&a)[V1]) {         // neighbour coordinate and q row (duplicate source rows alias row 0)
+            x = P.xyz[(long)(b * P.n + id) * 3 + gc];
+            const float *qrow = P.q + (long)(b * P.n + (id < src_e ? id : 0)) * P.q_pitch + 4 * g;
+#pragma unroll
+            for (int v = 0; v < V1; ++v) a[v] = *reinterpret_cast<const f4 *>(qrow + 16 * v);
+        };
+        // one unit; MORE: another one follows, whose loads go out here.  (Two copies of the body, the steady state and the last unit,
+        // instead of a test inside one: behind a branch around a load the compiler has to wait as if the load had not been issued.)
+        auto tile = [&](auto more) {
+            constexpr bool MORE = decltype(more)::value;
+            if constexpr (MORE) {
+                centroid_of(unit + stride, c_n, valid_n);
+                id_n = P.idx[(long)c_n * NS + slot0];
+                cg_n = P.new_xyz[(long)c_n * 3 + gc];
+            }
+            __builtin_amdgcn_sched_barrier(0);      // (the requests stay here: the scheduler otherwise moves them down to their first use)
+            const float bop = g < 3 ? __fsub_rn(nx, cg) : 1.0f;
+#pragma unroll
+            for (int v = 0; v < V1; ++v) a1[v] = mfma4(w1[v], bop, a1[v]);
+#pragma unroll
+            for (int v = 0; v < V1; ++v) a1[v] = relu_med4(a1[v], kinf);
+            if constexpr (MORE) gather(id_n, nx_n, a1n);
+            __builtin_amdgcn_sched_barrier(0);
+            f4 best[VL];
+            f4 a2[V2];
+            if constexpr (V3 == 0) {
+#pragma unroll
+                for (int v = 0; v < V2; ++v) a2[v] = f4_zero();
+                mlp_layer_res<V1, V2>(s_w, lane, a1, a2);
+#pragma unroll
+                for (int v = 0; v < V2; ++v) best[v] = a2[v];
+            } else {
+#pragma unroll
+                for (int v = 0; v < V2; ++v) a2[v] = b2[v];
+                mlp_layer_res<V1, V2>(s_w, lane, a1, a2);
+#pragma unroll
+                for (int v = 0; v < V2; ++v) a2[v] = relu_med4(a2[v], kinf);
+                f4 a3[V3 ? V3 : 1];
+#pragma unroll
+                for (int v = 0; v < V3; ++v) a3[v] = f4_zero();
+                mlp_layer_res<V2, (V3 ? V3 : 1)>(s_w + V1 * V2 * 64, lane, a2, a3);
+#pragma unroll
+                for (int v = 0; v < V3; ++v) best[v] = a3[v];
+            }
+            // bias before the maximum, behind a VALU instruction the compiler knows: see the serial loop
+#pragma unroll
+            for (int v = 0; v < VL; ++v) {
+                f4 m = best[v] + bl[v];
+                row_max_group_f4<(NS > 16 ? 16 : NS)>(m);
+                best[v] = relu_med4(m, kinf);
+            }
+            if (valid && slot0 == 0) {
+                float *o = P.out + (long)c * P.out_pitch + P.out_offset + 4 * g;
+#pragma unroll
+                for (int v = 0; v < VL; ++v) *reinterpret_cast<f4 *>(o + 16 * v) = best[v];
+            }
+        };
+        centroid_of(unit, c, valid);
+        cg = P.new_xyz[(long)c * 3 + gc];
+        gather(P.idx[(long)c * NS + slot0], nx, a1);
+        while (unit + stride < live_groups) {
+            tile(std::true_type{});
+            unit += stride; c = c_n; valid = valid_n; cg = cg_n; nx = nx_n;
+            for (int v = 0; v < V1; ++v) a1[v] = a1n[v];      // (a rotation of registers; the trip count is a constant)
+        }
+        tile(std::false_type{});
+        return;
+    }
     for (int unit = bx * 4 + (threadIdx.x >> 6); unit < live_groups; unit += nbx * 4) {
         int cl = unit * CPT + (NS >= 16 ? 0 : j / NS);        // centroid of this lane within the sample
         const bool valid = cl < live_c;                       // (a group of 16 / NS centroids may straddle dst_nuniq)
@@ -138,10 +240,11 @@ __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
     }
 }
 
-extern "C" int rtk_sa_scale(int samples, int n, int npoint, int nsample, const float *xyz, const float *new_xyz,
-                            const int *idx, const float *q, int q_pitch, int c1_16, const float *w1xyz_packed,
-                            int nlayers, const rtk_layer_t *layers, float *out, int out_pitch, int out_offset,
-                            const int *src_nuniq, const int *dst_nuniq, rtk_stream_t stream) {
+template <bool PIPE>
+static int sa_scale_launch(int samples, int n, int npoint, int nsample, const float *xyz, const float *new_xyz,
+                           const int *idx, const float *q, int q_pitch, int c1_16, const float *w1xyz_packed,
+                           int nlayers, const rtk_layer_t *layers, float *out, int out_pitch, int out_offset,
+                           const int *src_nuniq, const int *dst_nuniq, rtk_stream_t stream) {
     RTK_REQUIRE(samples > 0 && n > 0 && npoint > 0 && xyz && new_xyz && idx && q && w1xyz_packed && layers && out,
                 "sa_scale: bad arguments");
     RTK_REQUIRE(nlayers == 1 || nlayers == 2, "sa_scale: nlayers=%d (1 or 2 layers after the offset layer)", nlayers);
@@ -170,7 +273,7 @@ extern "C" int rtk_sa_scale(int samples, int n, int npoint, int nsample, const f
     const long key = (((long)nsample * 32 + v1) * 32 + v2) * 32 + v3;
 #define SA_CASE(ns, a, b, c)                                              \
     case (((long)(ns) * 32 + (a)) * 32 + (b)) * 32 + (c):                 \
-        sa_scale_kernel<ns, a, b, c><<<blocks, 256, 0, s>>>(P);           \
+        sa_scale_kernel<ns, a, b, c, PIPE><<<blocks, 256, 0, s>>>(P);     \
         break;
     switch (key) {
         SA_CASE(4, 1, 1, 2)     // sa1 scale 0: r=2,  ns=4,  16-16-32
@@ -186,6 +289,22 @@ extern "C" int rtk_sa_scale(int samples, int n, int npoint, int nsample, const f
 #undef SA_CASE
     RTK_CHECK_LAUNCH("sa_scale");
     return RTK_OK;
+}
+
+extern "C" int rtk_sa_scale(int samples, int n, int npoint, int nsample, const float *xyz, const float *new_xyz,
+                            const int *idx, const float *q, int q_pitch, int c1_16, const float *w1xyz_packed,
+                            int nlayers, const rtk_layer_t *layers, float *out, int out_pitch, int out_offset,
+                            const int *src_nuniq, const int *dst_nuniq, rtk_stream_t stream) {
+    return sa_scale_launch<true>(samples, n, npoint, nsample, xyz, new_xyz, idx, q, q_pitch, c1_16, w1xyz_packed, nlayers, layers, out,
+                                 out_pitch, out_offset, src_nuniq, dst_nuniq, stream);
+}
+
+extern "C" int rtk_sa_scale_serial(int samples, int n, int npoint, int nsample, const float *xyz, const float *new_xyz,
+                                   const int *idx, const float *q, int q_pitch, int c1_16, const float *w1xyz_packed,
+                                   int nlayers, const rtk_layer_t *layers, float *out, int out_pitch, int out_offset,
+                                   const int *src_nuniq, const int *dst_nuniq, rtk_stream_t stream) {
+    return sa_scale_launch<false>(samples, n, npoint, nsample, xyz, new_xyz, idx, q, q_pitch, c1_16, w1xyz_packed, nlayers, layers, out,
+                                  out_pitch, out_offset, src_nuniq, dst_nuniq, stream);
 }
 
 // =================================================================================================

@@ -765,16 +765,31 @@ struct SaSplitParams {
     const int *src_nuniq, *dst_nuniq;
 };
 
-// Register budget: asked for five waves per SIMD the three shapes allocate 86 / 84 / 86 registers without a spill (136 / 132 / 120
-// unconstrained) and fit on a SIMD next to another batch's forward cost volume (404 of 512): +2-3 % frame-pairs/s in the
-// pipelined forward.  (The first capped build computed wrong maxima: see the epilogue.)
+// Register budget: four waves per SIMD (<= 128 registers), which is what the launcher's grid gives anyway (SA_WGS_TARGET workgroups of
+// four waves on 1024 SIMDs).  The pipelined loop holds the next unit's q rows (32 registers at C1 = 64) and coordinates next to the
+// tile in work: 122 / 127 / 116 registers, no scratch.  (Five waves, <= 96 registers, held the serial loop -- 94 / 94 / 76 -- and was
+// chosen when an SA wave fitted on a SIMD next to a 404-register forward cost volume; that kernel now allocates CV_FWD_VGPRS and shares
+// its SIMDs with nothing.  Under that cap the pipelined loop spills 45 / 71 / 10 registers.  The first capped build computed wrong
+// maxima: see the epilogue.)
 #ifndef SA_SPLIT_WAVES
-#define SA_SPLIT_WAVES 5
+#define SA_SPLIT_WAVES 4
 #endif
 #ifndef SA_WGS_TARGET
 #define SA_WGS_TARGET 1024
 #endif
-template <int NS, int C1>
+// The k-step of layer 2 behind which the pipelined loop requests the next unit's rows at C1 = 64 (four k-steps; at C1 = 32 they go
+// out in front of layer 2).  Behind step 1 a quarter of the tile's activations is dead and the rows fit: in front of layer 2 the
+// 64-channel shapes spill 2 / 11 registers.  <16, 64> also needs its epilogue fenced off from layer 2 (else the scheduler hoists the
+// eight bias reads and the first block's maximum over the last MFMAs: 6 - 11 registers spilled); SA_EPI_FENCE_ALL fences every shape.
+#ifndef SA_GATHER_STEP
+#define SA_GATHER_STEP 1
+#endif
+#ifndef SA_EPI_FENCE_ALL
+#define SA_EPI_FENCE_ALL 0
+#endif
+// PIPE: the tile loop software-pipelined by one unit with its constants out of the loop (the first of the two loops below); false: the
+// loop as it was before (rtk_sa_scale_split_serial, the comparison implementation).  The two compute the same bits.
+template <int NS, int C1, bool PIPE>
 __global__ __launch_bounds__(256, SA_SPLIT_WAVES) void sa_scale_split_kernel(const SaSplitParams P) {
     constexpr int KS = C1 / 16, VB1 = C1 / 32, NFR = KS * 2 * 2, CPT = 32 / NS;      // k-steps, 32-blocks of layer 1, fragments, centroids per tile
     // (as in sa_scale_kernel, fused_group.hip: the lanes of the last tile past live_c are redirected to centroid live_c - 1 before the
@@ -789,10 +804,135 @@ __global__ __launch_bounds__(256, SA_SPLIT_WAVES) void sa_scale_split_kernel(con
     const int live_c = min(dst_e, P.npoint);                      // centroids >= live_c are duplicates of centroid 0: neither computed nor written
     const int live_units = (live_c + CPT - 1) / CPT;
     if (bx * 4 >= live_units) return;
+    __shared__ __attribute__((aligned(16))) float s_bias2[PIPE ? 64 : 4];     // PIPE: bias2 and the offset image [KS][64] behind the image
+    __shared__ float s_w1[PIPE ? KS * 64 : 1];
     for (int i = threadIdx.x; i < NFR * 64; i += blockDim.x) s_img[i] = P.image[i];
+    if constexpr (PIPE) {
+        if (threadIdx.x < 64) s_bias2[threadIdx.x] = P.bias2[threadIdx.x];
+        for (int i = threadIdx.x; i < KS * 64; i += blockDim.x) s_w1[i] = P.w1[i];
+    }
     __syncthreads();
     const int src_e = P.src_nuniq ? P.src_nuniq[b] : 0x7fffffff;
     const float winv = ldc(P.wsc);
+    if constexpr (PIPE) {
+        // The serial loop below reloads the 2 VB1 offset weights of a lane and its eight bias2 fragments on every tile (the latter
+        // only after the last layer-2 MFMA, waited for one by one) and makes three dependent round trips per tile: ball index ->
+        // coordinates and q rows -> bias.  Here the offset image and bias2 live in LDS behind the split image (filled with it), and the gathers of unit u + 1 are in flight under unit u's layer 2: its ball index and centroid are requested at the top
+        // of u, its neighbour coordinates and q rows -- into registers of their own, which become layer 1's accumulators at the top of
+        // the next trip -- under u's layer-2 MFMAs (SA_GATHER_STEP).  Whether a next unit exists is wave-uniform; without one nothing is
+        // requested.  Lanes past live_c are redirected before every index load as in the serial loop: the same rows are read.
+        const int stride = nbx * 4;
+        int unit = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (an SGPR: the loop's branches are scalar)
+        if (unit >= live_units) return;                       // (no barrier follows)
+        // A lane's two operands of the offset layer are (dx, dz) (hh = 0) or (dy, 1) (hh = 1): it loads component hh and component 2 of
+        // the neighbour and of the centroid -- every lane both, the lanes hh = 1 select their constant afterwards.
+        // State of the unit in work (c, valid, ca, cb and -- requested, not waited for -- na, nb, a) and of the one after it (*_n).
+        int c, c_n = 0, id_n = 0;
+        bool valid, valid_n = false;
+        float ca, cb, na, nb, ca_n = 0.f, cb_n = 0.f, na_n = 0.f, nb_n = 0.f;
+        f16v a[VB1], an[VB1];
+        auto centroid_of = [&](int u, int &cc, bool &vv) {        // global centroid index of this lane in unit u, redirected past live_c
+            int cl = u * CPT + pp;
+            vv = cl < live_c;
+            if (!vv) cl = live_c - 1;
+            cc = b * P.npoint + cl;
+        };
+        auto gather = [&](int id, float &xa, float &xb, f16v (&r)[VB1]) {     // neighbour coordinates and q rows (duplicate source rows alias row 0)
+            const long src = (long)b * P.n + id;
+            xa = P.xyz[src * 3 + hh]; xb = P.xyz[src * 3 + 2];
+            const float *qrow = P.q + ((long)b * P.n + (id < src_e ? id : 0)) * P.q_pitch + 4 * hh;
+#pragma unroll
+            for (int v = 0; v < VB1; ++v)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f4 t = *reinterpret_cast<const f4 *>(qrow + 32 * v + 8 * q);
+                    r[v][4 * q] = t.x; r[v][4 * q + 1] = t.y; r[v][4 * q + 2] = t.z; r[v][4 * q + 3] = t.w;
+                }
+        };
+        // one unit; MORE: another one follows, whose loads go out here.  (Two copies of the body, the steady state and the last unit,
+        // instead of a test inside one: behind a branch around a load the compiler has to wait as if the load had not been issued.)
+        auto tile = [&](auto more) {
+            constexpr bool MORE = decltype(more)::value;
+            constexpr int GS = KS == 4 ? SA_GATHER_STEP : 0;
+            if constexpr (MORE) {
+                centroid_of(unit + stride, c_n, valid_n);
+                id_n = P.idx[(long)c_n * NS + slot];
+                ca_n = P.new_xyz[(long)c_n * 3 + hh]; cb_n = P.new_xyz[(long)c_n * 3 + 2];
+            }
+            __builtin_amdgcn_sched_barrier(0);      // (the requests stay here: the scheduler otherwise moves them down to their first use)
+            const float b0 = __fsub_rn(na, ca), dz = __fsub_rn(nb, cb);
+            const float b1 = hh ? 1.0f : dz;
+            f4 h[4 * VB1];
+#pragma unroll
+            for (int v = 0; v < VB1; ++v) {
+                const int ch = 32 * v + col;
+                const float *wr = s_w1 + (ch >> 4) * 64 + (ch & 15);
+                a[v] = mfma_f32x2(wr[16 * hh], b0, a[v]);
+                a[v] = mfma_f32x2(wr[16 * (2 + hh)], b1, a[v]);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) h[4 * v + q] = relu_med4((f4){a[v][4 * q], a[v][4 * q + 1], a[v][4 * q + 2], a[v][4 * q + 3]}, kinf);
+            }
+            const LaneScale sc = lane_scale32(h);
+            const float cs = sc.inv * winv;
+            f16v acc[2];
+#pragma unroll
+            for (int v = 0; v < 2; ++v)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[v][e] = 0.f;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                u4v bp[2];
+                split2(h[2 * s], h[2 * s + 1], sc.s, bp);
+                u4v fr[2][2];
+#pragma unroll
+                for (int v = 0; v < 2; ++v)
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) fr[v][p] = __builtin_bit_cast(u4v, s_img[((s * 2 + v) * 2 + p) * 64 + lane]);
+#define RTK_SA_MM(pa, pb) acc[0] = mfma_h(fr[0][pa], bp[pb], acc[0]); acc[1] = mfma_h(fr[1][pa], bp[pb], acc[1]);
+                RTK_SA_MM(1, 0) RTK_SA_MM(0, 1) RTK_SA_MM(0, 0)
+#undef RTK_SA_MM
+                if (MORE && s == GS) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    gather(id_n, na_n, nb_n, an);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            // epilogue: as in the serial loop, the bias from LDS
+            if constexpr (SA_EPI_FENCE_ALL || (NS == 16 && C1 == 64)) __builtin_amdgcn_sched_barrier(0);
+            f4 m[2][4];
+#pragma unroll
+            for (int v = 0; v < 2; ++v)
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    m[v][q] = scale_bias4((f4){acc[v][4 * q], acc[v][4 * q + 1], acc[v][4 * q + 2], acc[v][4 * q + 3]}, cs,
+                                          *reinterpret_cast<const f4 *>(s_bias2 + 32 * v + 8 * q + 4 * hh));
+            const int qo = 2 * ((col >> 3) & 1) + ((col >> 2) & 1);
+            float *o = P.out + (long)c * P.out_pitch + P.out_offset + 4 * hh + 8 * qo;
+            if constexpr (NS == 32) {
+                f4 t[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) t[q] = wave_max_pair16(m[0][q], m[1][q], kinf);
+                const f4 r = relu_med4(row_max16_transpose4(t[0], t[1], t[2], t[3]), kinf);
+                if (valid && (col & 3) == 0) *reinterpret_cast<f4 *>(o + 32 * ((col >> 4) & 1)) = r;
+            } else {
+#pragma unroll
+                for (int v = 0; v < 2; ++v) {
+                    const f4 r = relu_med4(row_max16_transpose4(m[v][0], m[v][1], m[v][2], m[v][3]), kinf);
+                    if (valid && (col & 3) == 0) *reinterpret_cast<f4 *>(o + 32 * v) = r;
+                }
+            }
+        };
+        centroid_of(unit, c, valid);
+        ca = P.new_xyz[(long)c * 3 + hh]; cb = P.new_xyz[(long)c * 3 + 2];
+        gather(P.idx[(long)c * NS + slot], na, nb, a);
+        while (unit + stride < live_units) {
+            tile(std::true_type{});
+            unit += stride; c = c_n; valid = valid_n; ca = ca_n; cb = cb_n; na = na_n; nb = nb_n;
+            for (int v = 0; v < VB1; ++v) a[v] = an[v];       // (a rotation of registers; the trip count is a constant)
+        }
+        tile(std::false_type{});
+        return;
+    }
     for (int unit = bx * 4 + (threadIdx.x >> 6); unit < live_units; unit += nbx * 4) {
         int cl = unit * CPT + pp;                                  // centroid of this lane within the sample
         const bool valid = cl < live_c;
@@ -1019,10 +1159,11 @@ extern "C" int rtk_cost_volume_bwd_split(int samples, int n1, int n2, const floa
     return RTK_OK;
 }
 
-extern "C" int rtk_sa_scale_split(int samples, int n, int npoint, int nsample, const float *xyz, const float *new_xyz, const int *idx,
-                                  const float *q, int q_pitch, int c1, const float *w1xyz_packed, const void *split_image,
-                                  const float *image_scale, const float *bias2, float *out, int out_pitch, int out_offset,
-                                  const int *src_nuniq, const int *dst_nuniq, rtk_stream_t stream) {
+template <bool PIPE>
+static int sa_scale_split_launch(int samples, int n, int npoint, int nsample, const float *xyz, const float *new_xyz, const int *idx,
+                                 const float *q, int q_pitch, int c1, const float *w1xyz_packed, const void *split_image,
+                                 const float *image_scale, const float *bias2, float *out, int out_pitch, int out_offset,
+                                 const int *src_nuniq, const int *dst_nuniq, rtk_stream_t stream) {
     RTK_REQUIRE(samples > 0 && n > 0 && npoint > 0 && xyz && new_xyz && idx && q && w1xyz_packed && split_image && image_scale && bias2 && out,
                 "sa_scale_split: bad arguments");
     RTK_REQUIRE(q_pitch % 4 == 0 && out_pitch % 4 == 0 && out_offset % 4 == 0, "sa_scale_split: pitches/offset must be multiples of 4");
@@ -1038,13 +1179,29 @@ extern "C" int rtk_sa_scale_split(int samples, int n, int npoint, int nsample, c
     while ((long)bx * samples > SA_WGS_TARGET && bx > 1) bx = (bx + 1) / 2;      // few, fat workgroups: the LDS image fill is paid per workgroup
     const dim3 blocks = rtk_xcd_grid(samples, bx, P.gx);
     hipStream_t s = (hipStream_t)stream;
-    if (nsample == 32 && c1 == 64) sa_scale_split_kernel<32, 64><<<blocks, 256, 0, s>>>(P);
-    else if (nsample == 16 && c1 == 64) sa_scale_split_kernel<16, 64><<<blocks, 256, 0, s>>>(P);
-    else if (nsample == 16 && c1 == 32) sa_scale_split_kernel<16, 32><<<blocks, 256, 0, s>>>(P);
+    if (nsample == 32 && c1 == 64) sa_scale_split_kernel<32, 64, PIPE><<<blocks, 256, 0, s>>>(P);
+    else if (nsample == 16 && c1 == 64) sa_scale_split_kernel<16, 64, PIPE><<<blocks, 256, 0, s>>>(P);
+    else if (nsample == 16 && c1 == 32) sa_scale_split_kernel<16, 32, PIPE><<<blocks, 256, 0, s>>>(P);
     else {
         rtk_set_error("sa_scale_split: no kernel instance for nsample=%d, %d -> 64 channels", nsample, c1);
         return RTK_ERR_UNSUPPORTED;
     }
     RTK_CHECK_LAUNCH("sa_scale_split");
     return RTK_OK;
+}
+
+extern "C" int rtk_sa_scale_split(int samples, int n, int npoint, int nsample, const float *xyz, const float *new_xyz, const int *idx,
+                                  const float *q, int q_pitch, int c1, const float *w1xyz_packed, const void *split_image,
+                                  const float *image_scale, const float *bias2, float *out, int out_pitch, int out_offset,
+                                  const int *src_nuniq, const int *dst_nuniq, rtk_stream_t stream) {
+    return sa_scale_split_launch<true>(samples, n, npoint, nsample, xyz, new_xyz, idx, q, q_pitch, c1, w1xyz_packed, split_image, image_scale,
+                                       bias2, out, out_pitch, out_offset, src_nuniq, dst_nuniq, stream);
+}
+
+extern "C" int rtk_sa_scale_split_serial(int samples, int n, int npoint, int nsample, const float *xyz, const float *new_xyz, const int *idx,
+                                         const float *q, int q_pitch, int c1, const float *w1xyz_packed, const void *split_image,
+                                         const float *image_scale, const float *bias2, float *out, int out_pitch, int out_offset,
+                                         const int *src_nuniq, const int *dst_nuniq, rtk_stream_t stream) {
+    return sa_scale_split_launch<false>(samples, n, npoint, nsample, xyz, new_xyz, idx, q, q_pitch, c1, w1xyz_packed, split_image, image_scale,
+                                        bias2, out, out_pitch, out_offset, src_nuniq, dst_nuniq, stream);
 }

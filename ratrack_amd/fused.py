@@ -680,6 +680,12 @@ def cv_shared_workgroups(samples, n1, dev):
     return 8 * min(w, tiles)
 
 
+# The two entry points of an MSG scale: (chain, split).  The *_serial ones run the tile loops without software pipelining -- the
+# comparison implementation of tests and timing tools.
+SA_ENTRIES = ("rtk_sa_scale", "rtk_sa_scale_split")
+SA_ENTRIES_SERIAL = ("rtk_sa_scale_serial", "rtk_sa_scale_split_serial")
+
+
 def sa_scale(geo, W, lvl, s, q, qcol, out, out_offset):
     """One MSG scale (level lvl, scale s) of PNHead weights W on geometry geo; q[:, qcol:] holds its layer-1 projection.
     Duplicate centroids (geo.nuniq) are skipped; gathers from duplicate source rows alias row 0."""
@@ -692,12 +698,12 @@ def sa_scale(geo, W, lvl, s, q, qcol, out, out_offset):
         macs = sc.nsample * (4 * sc.c1 + sc.chain.macs)
         _TRACE.append(("sa_scale", _live_rows(geo.nuniq[lvl], geo.npoint, geo.samples), macs))
     if sc.split_image is not None:
-        _lib.call("rtk_sa_scale_split", geo.samples, src.shape[1], geo.npoint, sc.nsample, src.data_ptr(), dst.data_ptr(),
+        _lib.call(SA_ENTRIES[1], geo.samples, src.shape[1], geo.npoint, sc.nsample, src.data_ptr(), dst.data_ptr(),
                   geo.ball[lvl][s].data_ptr(), qptr, qpitch, sc.c1, sc.w1img.data_ptr(), sc.split_image.data_ptr(), sc.split_scale.data_ptr(),
                   sc.split_bias.data_ptr(),
                   optr, opitch, out_offset, src_nu, geo.nuniq[lvl].data_ptr(), _stream())
         return
-    _lib.call("rtk_sa_scale", geo.samples, src.shape[1], geo.npoint, sc.nsample, src.data_ptr(), dst.data_ptr(),
+    _lib.call(SA_ENTRIES[0], geo.samples, src.shape[1], geo.npoint, sc.nsample, src.data_ptr(), dst.data_ptr(),
               geo.ball[lvl][s].data_ptr(), qptr, qpitch, ceil16(sc.c1) // 16, sc.w1img.data_ptr(),
               sc.chain.n, sc.chain.arr, optr, opitch, out_offset, src_nu, geo.nuniq[lvl].data_ptr(), _stream())
 
