@@ -80,6 +80,16 @@ RTK_EXPORT int rtk_pointwise_mlp(int rows, int rows_per_sample, const rtk_interp
                                  const rtk_layer_t *layers, float *out, int out_pitch, int out_channels,
                                  int out_channel_major, const int *row_nuniq, float *colmax, rtk_stream_t stream);
 
+/* ... with the tile loop software-pipelined by one group: row_nuniq[b], interp.nuniq[b] and the first group's rows requested
+ * together, the next group's rows requested under the current group's products and stores (only if that group is live).  Same
+ * arguments, bit-identical result.  Measured in one build against the serial loop rtk_pointwise_mlp runs, it does not pay at the
+ * benchmarked shapes; it is kept as the comparison implementation of the tests and of the same-box
+ * measurements. */
+RTK_EXPORT int rtk_pointwise_mlp_pipelined(int rows, int rows_per_sample, const rtk_interp_t *interp, int nsrc,
+                                              const rtk_src_t *srcs, const float *sample_bias, int nlayers,
+                                           const rtk_layer_t *layers, float *out, int out_pitch, int out_channels,
+                                           int out_channel_major, const int *row_nuniq, float *colmax, rtk_stream_t stream);
+
 /* rtk_pointwise_mlp of one split layer on a 128-channel interpolation segment (the encoder's fp1: split 128 -> 128 image, no other
  * source, no sample bias, every row live) writing out (rows, out_pitch) channels 0..127 and colmax exactly as rtk_pointwise_mlp does,
  * and then taking the same tile through one more split layer, 128 -> 256 without activation: proj_out[(rows, proj_pitch)] =
@@ -89,6 +99,11 @@ RTK_EXPORT int rtk_pointwise_mlp(int rows, int rows_per_sample, const rtk_interp
 RTK_EXPORT int rtk_pointwise_mlp_tap(int rows, int rows_per_sample, const rtk_interp_t *interp, const rtk_layer_t *layer, float *out,
                                      int out_pitch, float *colmax, const rtk_layer_t *proj, int frame_split, float *proj_out,
                                      int proj_pitch, rtk_stream_t stream);
+
+/* ... with the software-pipelined tile loop: see rtk_pointwise_mlp_pipelined.  Same arguments, bit-identical result. */
+RTK_EXPORT int rtk_pointwise_mlp_tap_pipelined(int rows, int rows_per_sample, const rtk_interp_t *interp, const rtk_layer_t *layer, float *out,
+                                            int out_pitch, float *colmax, const rtk_layer_t *proj, int frame_split, float *proj_out,
+                                            int proj_pitch, rtk_stream_t stream);
 
 /* Two chains that read the same rows, in one launch: chain A (one split layer, 25 -> 2 blocks of 16 channels) on the whole input
  * vector srcs[0] || srcs[1] ... (25 slots) with its optional sample_bias, written point-major to out_a (rows, out_a_pitch); chain B

@@ -166,7 +166,9 @@ SIGNATURES = {
     "rtk_knn_point": [_i] * 4 + [_p] * 3 + [_p],
     # ---- include/rtk_fused.h
     "rtk_pointwise_mlp": [_i, _i, P(Interp), _i, P(Src), _p, _i, P(Layer), _p, _i, _i, _i, _p, _p, _p],
+    "rtk_pointwise_mlp_pipelined": [_i, _i, P(Interp), _i, P(Src), _p, _i, P(Layer), _p, _i, _i, _i, _p, _p, _p],
     "rtk_pointwise_mlp_tap": [_i, _i, P(Interp), P(Layer), _p, _i, _p, P(Layer), _i, _p, _i, _p],
+    "rtk_pointwise_mlp_tap_pipelined": [_i, _i, P(Interp), P(Layer), _p, _i, _p, P(Layer), _i, _p, _i, _p],
     "rtk_pointwise_mlp_pair": [_i, _i, _i, P(Src), _p, P(Layer), _p, _i, _i, _i, P(Layer), _p, _i, _p],
     "rtk_sa_scale": [_i] * 4 + [_p] * 4 + [_i, _i, _p, _i, P(Layer), _p, _i, _i, _p, _p, _p],
     "rtk_sa_scale_serial": [_i] * 4 + [_p] * 4 + [_i, _i, _p, _i, P(Layer), _p, _i, _i, _p, _p, _p],

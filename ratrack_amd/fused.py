@@ -270,6 +270,13 @@ def _interp_ptr(interp):
     return ctypes.pointer(_Interp(ptr, pitch, ch, m, idx.data_ptr(), d2.data_ptr(), _ptr(nu)))
 
 
+# The entry points of a per-point chain and of the encoder's last layer with its projection tap: (chain, tap).  The *_pipelined ones
+# run the software-pipelined tile loops -- the comparison implementation (same bits; measured in one build they do not pay, DESIGN
+# section 4.6): tests and same-box measurements swap the tuples.
+PW_ENTRIES = ("rtk_pointwise_mlp", "rtk_pointwise_mlp_tap")
+PW_ENTRIES_PIPELINED = ("rtk_pointwise_mlp_pipelined", "rtk_pointwise_mlp_tap_pipelined")
+
+
 def pointwise(rows, rows_per_sample, srcs, chain, out, out_channels=None, sample_bias=None, interp=None, channel_major=False,
               row_nuniq=None, colmax=None):
     """srcs: see _src_array.  out: (rows, pitch) point-major (may be a column-sliced view) or (samples, C, n) channel-major.
@@ -279,7 +286,7 @@ def pointwise(rows, rows_per_sample, srcs, chain, out, out_channels=None, sample
         macs = chain.macs + (3 * interp[1] if interp is not None else 0)
         _TRACE.append(("pointwise", _live_rows(row_nuniq, rows_per_sample, rows // rows_per_sample), macs))
     optr, opitch = (out.data_ptr(), 0) if channel_major else _colptr(out)
-    _lib.call("rtk_pointwise_mlp", rows, rows_per_sample, _interp_ptr(interp), len(srcs), _src_array(srcs), _ptr(sample_bias), chain.n,
+    _lib.call(PW_ENTRIES[0], rows, rows_per_sample, _interp_ptr(interp), len(srcs), _src_array(srcs), _ptr(sample_bias), chain.n,
               chain.split_arr() if PW_SPLIT else chain.arr, optr, opitch, oc, int(channel_major), _ptr(row_nuniq), _ptr(colmax), _stream())
     return out
 
@@ -296,7 +303,7 @@ def pointwise_tap(rows, rows_per_sample, chain, out, colmax, interp, proj, frame
         _TRACE.append(("pointwise", rows, chain.macs + 3 * interp[1]))
         _TRACE.append(("pointwise", rows, proj[0].macs))
     pa = (_Layer * 2)(proj[0].split_arr()[0], proj[1].split_arr()[0])
-    _lib.call("rtk_pointwise_mlp_tap", rows, rows_per_sample, _interp_ptr(interp), chain.split_arr(), *_colptr(out), colmax.data_ptr(), pa,
+    _lib.call(PW_ENTRIES[1], rows, rows_per_sample, _interp_ptr(interp), chain.split_arr(), *_colptr(out), colmax.data_ptr(), pa,
               frame_split, *_colptr(proj_out), _stream())
     return out, proj_out
 
