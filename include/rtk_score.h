@@ -38,6 +38,7 @@ extern "C" {
 #define RTK_SCORE_FLAG_SWEEP 32      /* rtk_score_track_means: more track ids in one clip than RTK_SCORE_SWEEP_TRACKS (no score written) */
 #define RTK_SCORE_FLAG_TABLE 64      /* rtk_track_score_memory: a table_count outside [num_objects, Kobj] (clamped) */
 #define RTK_SCORE_FLAG_HOTA 128      /* rtk_score_hota: a clip with more labels, track ids or pairs than its tables hold (outputs unspecified) */
+#define RTK_SCORE_FLAG_IDENTITY 256  /* rtk_score_identity: the same, of its tables */
 
 /* LDS bytes of one workgroup for these sizes (host functions: no device is touched). */
 RTK_EXPORT int rtk_gt_objects_lds_bytes(int K, int N);
@@ -275,6 +276,52 @@ RTK_EXPORT int rtk_score_hota(int B, int T, const rtk_score_log_t *log, const do
                               const double *threshold /* device scalar, or NULL: nothing removed */, int alphas,
                               long long *counters /* (alphas,B,6) */, double *sums /* (alphas,B,4) */, int *flags /* (B) */,
                               rtk_stream_t stream);
+
+/* ---- Identity: IDF1, IDP, IDR (csrc/track_identity.hip, csrc/lds_assignment.h, TrackScorer.identity) ---------------------------------
+ *
+ * The identity metrics of Ristani et al., "Performance Measures and a Data Set for Multi-Target, Multi-Camera Tracking", over the
+ * same log, under this module's rules and the reference's point IoU.  The arrangement is TrackEval's `Identity`: every pair above the
+ * threshold counts, then ONE GLOBAL ASSIGNMENT of whole trajectories per sequence (here: per clip).  TrackEval's own numbers use box
+ * IoU at 0.5: these are NOT those.
+ *   levels       `count` of them (1..63), explicit float64 values handed over by the caller (TrackScorer.identity: the single
+ *                level 0.5 by default -- IDF1 is a one-threshold metric by convention; HOTA's levels work as well).
+ *   removal      clip, log, track score and the removal by a threshold t are the sweep's and HOTA's: a detection whose track score
+ *                is < t is removed.  No rec_score, no threshold or t = -infinity removes nothing.
+ *   candidate    per (stream, level alpha), in every frame: a remaining detection whose rec_best is not -1 AND IS ONE OF THE FRAME'S
+ *                KEPT LABELS, with rec_iou >= alpha (float64 >=, as in HOTA: an IoU of 3/5 is a candidate at 0.6).  THERE IS NO
+ *                GREEDY PASS: two detections of one frame that share a best label are both candidates, as TrackEval counts every
+ *                pair above the threshold and not only the matched ones.  The log holds only a detection's BEST object, so a second
+ *                object above alpha is not seen: a detection is a candidate for at most one label per frame.
+ *   per clip     n[g,t] the frames in which a candidate with track id t has best label g (track ids are unique within a frame: a
+ *                frame adds at most 1 to a pair, and a log that repeats a track id within a frame still adds 1); gt gains every
+ *                frame's kept-label count and pred its remaining detections.  A clip closes at a reset frame or at the end of the
+ *                log, and idtp then gains THE WEIGHT OF A MAXIMUM-WEIGHT ONE-TO-ONE MATCHING between the clip's labels and its track
+ *                ids under the weights n.  That is TrackEval's minimisation of fn_mat + fp_mat: with cg, ct the frames of a label
+ *                and the detections of a track, a matching costs sum cg + sum ct - 2 sum n(matched).
+ *   counters     running over the stream: frames | clips | gt | pred | idtp | pairs = the distinct (g,t) with n > 0.  The optimum
+ *                WEIGHT is unique even where the optimal matching is not, so every output is an integer and the same on every run;
+ *                the matching itself and the number of matched pairs are not unique and are not delivered.
+ *   host         float64, the streams pooled: idfn = gt - idtp, idfp = pred - idtp, IDR = idtp / gt, IDP = idtp / pred,
+ *                IDF1 = 2 idtp / (gt + pred); a ratio without a denominator is NaN (track_score.py, identity_values).
+ * The solver is exact integer arithmetic in LDS (csrc/lds_assignment.h states its contract); no floating point enters a counter. */
+#define RTK_SCORE_ID_COUNTERS 6      /* frames | clips | gt | pred | idtp | pairs */
+/* Most distinct (label id, track id) pairs of one clip of one stream: the edges of the assignment. */
+#define RTK_SCORE_ID_PAIRS 1024
+
+/* LDS bytes of one workgroup of rtk_score_identity for T label ids per clip (a host function: no device is touched); -1 for a T
+ * below 1.  The kernel is built for two label capacities, 1024 and the largest that fits RTK_SCORE_LDS_LIMIT, and a T takes the
+ * smaller one that holds it: this is that instance's figure, or for a larger T what its tables would need. */
+RTK_EXPORT int rtk_score_identity_lds_bytes(int T);
+
+/* Grid (stream, level index): counters (count,B,6) of level alphas[index].  T bounds the label ids of one clip (rtk_track_score's T; a
+ * T whose tables do not fit RTK_SCORE_LDS_LIMIT is refused, and so is a log of more than 2^28 frames per stream: a pair's weight is a
+ * frame count and the solver's sums stay in an int), RTK_SCORE_SWEEP_TRACKS its track ids and RTK_SCORE_ID_PAIRS its pairs.  A clip of
+ * stream b beyond one of the three raises RTK_SCORE_FLAG_IDENTITY in flags[b] (or-ed in; nothing else of flags is touched): that
+ * stream's outputs are then unspecified but written, the other streams are unaffected.  Reads the log, rec_score, threshold and alphas
+ * and writes only counters and flags. */
+RTK_EXPORT int rtk_score_identity(int B, int T, const rtk_score_log_t *log, const double *rec_score /* (B,R) or NULL */,
+                                  const double *threshold /* device scalar, or NULL: nothing removed */, const double *alphas /* device, (count) */,
+                                  int count, long long *counters /* (count,B,6) */, int *flags /* (B) */, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -221,6 +221,8 @@ SIGNATURES = {
     "rtk_score_thresholds": [_p, _p, _p, _i, _p, _p, _p],
     "rtk_score_replay": [_i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p],
     "rtk_score_hota": [_i, _i, _p, _p, _p, _i, _p, _p, _p, _p],
+    "rtk_score_identity_lds_bytes": [_i],
+    "rtk_score_identity": [_i, _i, _p, _p, _p, _p, _i, _p, _p, _p],
     # ---- include/rtk_train.h
     "rtk_bn_train_stats": [_i] * 5 + [_p] * 3 + [_p],
     "rtk_bn_relu_fwd": [_i] * 5 + [_p, _p, _i, _p, _p],

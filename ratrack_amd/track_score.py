@@ -78,8 +78,22 @@ order, first come first served, and a detection below alpha takes nothing (thres
 a Hungarian assignment on box IoU and are not these.  The definitions are in include/rtk_score.h; the device delivers integers and
 four fixed-order float64 sums, `hota_values` is the arithmetic.
 
+Identity.  `scorer.identity(alphas=(0.5,))` evaluates IDF1, IDP and IDR (Ristani et al., "Performance Measures and a Data Set for
+Multi-Target, Multi-Camera Tracking") over the same log, in one launch and one download -- two launches with `threshold=`:
+
+    idn = scorer.identity()                         # IdentityResult: idf1, idr, idp, idtp, idfn, idfp per level
+
+IDF1 is the share of all detections that sit under the single best identity of their object.  Per level alpha every remaining
+detection whose best object is one of the frame's kept labels with IoU >= alpha is a candidate -- there is no greedy pass, two
+detections of a frame may share a label --; per clip n[g,t] counts the frames in which a candidate of track t had label g, and when
+the clip closes idtp gains the weight of a MAXIMUM-WEIGHT ONE-TO-ONE MATCHING of the clip's labels and track ids under n, solved
+exactly on the device (csrc/lds_assignment.h).  That is TrackEval's `Identity` arrangement (every pair above the threshold, one global
+assignment), but under this module's log -- a detection's best object only -- and the reference's point IoU: TrackEval's own numbers
+use box IoU at 0.5 and are not these.  The definitions are in include/rtk_score.h; the device delivers integers, `identity_values`
+is the arithmetic.
+
 Nothing here synchronises with the device except `GtObjects.check()`, `TrackScorer.check()`, `TrackScorer.result()`,
-`TrackScorer.sweep()` and `TrackScorer.hota()`.
+`TrackScorer.sweep()`, `TrackScorer.hota()` and `TrackScorer.identity()`.
 """
 import ctypes
 
@@ -103,6 +117,9 @@ FLAG_HOTA = 128                        # RTK_SCORE_FLAG_HOTA
 HOTA_COUNTERS = ("frames", "clips", "gt", "pred", "tp", "pairs")
 HOTA_SUMS = ("ass", "ass_re", "ass_pr", "loc")
 HOTA_PAIRS = 1024                      # RTK_SCORE_HOTA_PAIRS
+FLAG_IDENTITY = 256                    # RTK_SCORE_FLAG_IDENTITY
+IDENTITY_COUNTERS = ("frames", "clips", "gt", "pred", "idtp", "pairs")
+IDENTITY_PAIRS = 1024                  # RTK_SCORE_ID_PAIRS
 
 
 # ---- what fits -------------------------------------------------------------------------------------------------------------
@@ -342,6 +359,36 @@ def hota_values(counters, sums):
     return out
 
 
+class IdentityResult:
+    """What `TrackScorer.identity` returns (host values; definitions in include/rtk_score.h).  `alpha` (A) float64, the levels as
+    given.  Per-level arrays of length A, pooled over the streams: idtp, idfn, idfp, gt, pred, pairs (integers) and idf1, idr, idp
+    (NaN where the denominator is 0).  `counters` (A,B,6) int64 in IDENTITY_COUNTERS order per stream; `flags` (B); `threshold` (None
+    or the float the detections were filtered with)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def identity_values(counters, alpha):
+    """The identity metrics' arithmetic, host only: counters (A,S,6) integer counts in IDENTITY_COUNTERS order of A levels and any
+    number S of streams, alpha the A levels -> dict with the fields of `IdentityResult` except flags and threshold.  Counts are pooled
+    over the streams; float64 throughout: IDR = idtp / gt, IDP = idtp / pred, IDF1 = 2 idtp / (gt + pred), NaN without a denominator."""
+    c = np.asarray(counters, dtype=np.int64)
+    al = np.asarray(alpha, dtype=np.float64).reshape(-1)
+    if c.ndim != 3 or c.shape[2] != len(IDENTITY_COUNTERS) or c.shape[0] < 1 or al.shape[0] != c.shape[0]:
+        raise ValueError("identity_values: counters %s and alpha %s are not (A,S,%d) and (A)" % (c.shape, al.shape, len(IDENTITY_COUNTERS)))
+    pooled = c.sum(axis=1)
+    g = lambda k: pooled[:, IDENTITY_COUNTERS.index(k)]
+    idtp, gt, pred = g("idtp").astype(np.float64), g("gt").astype(np.float64), g("pred").astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        val = dict(idr=idtp / gt, idp=idtp / pred, idf1=2.0 * idtp / (gt + pred))
+    out = dict(alpha=al.copy(), counters=c, **val)
+    for k in ("idtp", "gt", "pred", "pairs"):
+        out[k] = g(k).copy()
+    out["idfn"], out["idfp"] = out["gt"] - out["idtp"], out["pred"] - out["idtp"]
+    return out
+
+
 class TrackScorer:
     """Matches the detections of `streams` sequences to their ground-truth objects frame by frame and keeps the score on the device
     (see the module docstring).  State (device tensors): counters (B,11) int64 in COUNTERS order, iou_sum (B) float64, the table of
@@ -489,6 +536,9 @@ class TrackScorer:
             if f & FLAG_HOTA:
                 raise RuntimeError("TrackScorer.hota: stream %d has a clip with more than max_gt_tracks=%d label ids, %d track ids or %d "
                                    "(label id, track id) pairs" % (b, self.T, SWEEP_TRACKS, HOTA_PAIRS))
+            if f & FLAG_IDENTITY:
+                raise RuntimeError("TrackScorer.identity: stream %d has a clip with more than max_gt_tracks=%d label ids, %d track ids or "
+                                   "%d (label id, track id) pairs" % (b, self.T, SWEEP_TRACKS, IDENTITY_PAIRS))
 
     def check(self):
         """Synchronises.  Raises RuntimeError naming the stream whose track table overflowed or whose sizes were out of range."""
@@ -606,3 +656,42 @@ class TrackScorer:
         if check:
             self._raise_on_flags(fl.tolist())
         return HotaResult(flags=fl, threshold=tau, **hota_values(counters, sums))
+
+    def identity(self, alphas=(0.5,), threshold=None, check=True):
+        """IDF1, IDP and IDR over the log (module docstring; definitions in include/rtk_score.h).  alphas: a float or a sequence of
+        1..63 floats, each finite and in (0, 1]: the IoU levels.  threshold as in `hota`: None, one launch; a float or a 0-dim
+        tensor, the detections whose track score is below it are removed, two launches (track scores, then the walk).  Then one
+        download.  The running state and the log are only read: scoring may go on.  check: raise (naming the stream) on any sticky
+        flag and on a clip that overflowed the tables; check=False returns the other streams' numbers (`flags` tells which to leave
+        out).  -> IdentityResult."""
+        if not self.logging:
+            raise RuntimeError("TrackScorer.identity: the scorer keeps no log (give sweep_frames and sweep_records)")
+        al = np.atleast_1d(np.asarray(alphas, dtype=np.float64))
+        if al.ndim != 1 or not 1 <= al.shape[0] <= 63:
+            raise ValueError("alphas=%r must be a float or a sequence of 1 to 63 floats" % (alphas,))
+        if not (np.isfinite(al) & (al > 0.0) & (al <= 1.0)).all():
+            raise ValueError("alphas=%r: every level must be finite and in (0, 1]" % (alphas,))
+        A, B, dev, nc = al.shape[0], self.B, self.counters.device, len(IDENTITY_COUNTERS)
+        lg = self._log_block()
+        lgp, st = ctypes.addressof(lg), _stream()
+        flags = self.flags.clone()
+        score = thr = None
+        if threshold is not None:
+            thr = torch.as_tensor(threshold, dtype=torch.float64).reshape(1).to(dev)
+            score = torch.zeros(B, self.R, dtype=torch.float64, device=dev)
+            _lib.call("rtk_score_track_means", B, lgp, score.data_ptr(), flags.data_ptr(), st)
+        levels = torch.from_numpy(al.copy()).to(dev)
+        c = torch.empty(A, B, nc, dtype=torch.int64, device=dev)
+        _lib.call("rtk_score_identity", B, self.T, lgp, None if score is None else score.data_ptr(), None if thr is None else thr.data_ptr(),
+                  levels.data_ptr(), A, c.data_ptr(), flags.data_ptr(), st)
+        parts = [c.reshape(-1), flags.long()]
+        if thr is not None:
+            parts.append(thr.view(torch.int64))
+        host = torch.cat(parts).cpu().numpy()
+        o = A * B * nc
+        counters = host[:o].reshape(A, B, nc).copy()
+        fl = host[o:o + B].copy()
+        tau = None if thr is None else float(host[o + B:].copy().view(np.float64)[0])
+        if check:
+            self._raise_on_flags(fl.tolist())
+        return IdentityResult(flags=fl, threshold=tau, **identity_values(counters, al))
