@@ -406,7 +406,11 @@ RTK_EXPORT int rtk_dbscan_batched(const rtk_track_frame_t *frame, float threshol
                                   int *obj, int *num_objects, int *flags, void *work, long long work_bytes, rtk_stream_t stream);
 
 /* rtk_object_descriptors: desc (B,K,141) of every object of every active stream (points in index order; two-pass population
- * variance).  Inactive streams carry their previous descriptors over: desc[b][:prev_count[b]] = desc_prev[b][:prev_count[b]]. */
+ * variance, both sums compensated: as accurate for an object of 500 points 80 m away as for one of two points at the origin).
+ * Inactive streams carry their previous descriptors over: desc[b][:prev_count[b]] = desc_prev[b][:prev_count[b]] bit for bit
+ * (prev_count clamped to [0, K]).  Nothing else is written: rows >= num_objects[b] of an active stream and rows >= prev_count[b] of an
+ * inactive one keep what the caller's buffer held (rtk_track_memory puts its survivors there; no reader looks past the counts).
+ * Only the first n_valid[b] columns of obj are read; num_objects[b] <= K is the caller's (rtk_dbscan_batched's) guarantee. */
 RTK_EXPORT int rtk_object_descriptors(const rtk_track_frame_t *frame, int K, const int *obj, const int *num_objects,
                                       const int *prev_count, const float *desc_prev, float *desc, rtk_stream_t stream);
 
@@ -423,7 +427,10 @@ RTK_EXPORT int rtk_affinity_pairs(int B, int K, const float *weights, const floa
  * (fresh from counter[b] in current-object order when unmatched or aff < 0.01, else the previous object's ID with conf = aff) and
  * point_track_id (B,N).  Writes object_ids / object_conf / indices1 (B,K) (-1 / 0 / -1 past num_objects), num_prev (B) = m_b,
  * counter (B) in place, and the next state ids (B,K), count (B).  Inactive streams: ids = prev_ids, count = prev_count, no objects.
- * scores: NULL, or (B, K+1, K+1): each stream's whole (m_b+1, n_b+1) Sinkhorn output (rtk_log_sinkhorn's `out`, row stride K+1).
+ * scores: NULL, or (B, K+1, K+1): each stream's whole (m_b+1, n_b+1) Sinkhorn output (rtk_log_sinkhorn's `out`, row stride K+1);
+ * nothing outside that block is written, and nothing at all for a stream that is inactive, reset, or has m_b = 0 or n_b = 0 (no
+ * plan is computed there).  aff is read inside the live (m_b, n_b) block only.  The threshold is the double 0.01 against the fp32
+ * aff widened: float32(0.01) itself is below it and starts a fresh track, as in the reference.
  * One workgroup per stream; its LDS holds the (K+1) x (K+1) table (about 66 KiB at K = 128). */
 RTK_EXPORT int rtk_associate_batched(int B, int N, int K, const unsigned char *active, const unsigned char *reset, const float *aff,
                                      const int *num_objects, const int *obj, const int *prev_ids, const int *prev_count, float alpha,

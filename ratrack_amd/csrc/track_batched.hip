@@ -137,9 +137,18 @@ extern "C" int rtk_dbscan_batched(const rtk_track_frame_t *frame, float threshol
 // rtk_object_descriptors: workgroup (b, y) handles the objects y, y + G, ... of stream b.  Per chunk of 256 columns the object's
 // members are compacted in column order into LDS; threads 0..127 keep the max of one prop channel, threads 128..135 the sum of one
 // of the 8 statistics channels (xyz, flow, RCS, v_r); a second pass sums the squared deviations from the mean (torch.var's
-// two-pass population variance).
+// two-pass population variance).  Both sums are compensated (comp_add): a plain fp32 running sum over an object of several hundred
+// points loses log2(n) bits, which the second pass squares when the object is far from the origin (80 m away, 1e-2 m across: a
+// variance 5e-5 off) -- the sums then are as good as the reference's pairwise ones whatever the object's size.
 // ------------------------------------------------------------------------------------------------
 #define DESC_G 16
+
+// acc += x with the rounding error of the addition carried in comp (Kahan); the build has contraction and fast-math off
+__device__ __forceinline__ void comp_add(float &acc, float &comp, float x) {
+    const float y = x - comp, t = acc + y;
+    comp = (t - acc) - y;
+    acc = t;
+}
 
 __device__ __forceinline__ float stat_channel(const rtk_track_frame_t &fr, int b, int s, int p) {
     return s < 3 ? bcn_at(fr.pc1, b, s, p) : (s < 6 ? bcn_at(fr.flow, b, s - 3, p) : bcn_at(fr.feature1, b, s - 6, p));
@@ -162,7 +171,7 @@ __global__ __launch_bounds__(256) void object_descriptors_kernel(const rtk_track
     const bool is_prop = t < 128, is_stat = t >= 128 && t < 136;
     const int s = t - 128;
     for (int k = blockIdx.y; k < nobj; k += gridDim.y) {
-        float acc = is_prop ? -INFINITY : 0.f, mean = 0.f;
+        float acc = is_prop ? -INFINITY : 0.f, comp = 0.f, mean = 0.f;
         int cnt = 0;
         for (int pass = 0; pass < 2; ++pass) {
             for (int base = 0; base < n; base += 256) {
@@ -174,12 +183,12 @@ __global__ __launch_bounds__(256) void object_descriptors_kernel(const rtk_track
                 __syncthreads();
                 if (pass == 0) {
                     if (is_prop) for (int q = 0; q < c; ++q) acc = fmaxf(acc, bcn_at(fr.prop, b, t, s_list[q]));
-                    else if (is_stat) for (int q = 0; q < c; ++q) acc += stat_channel(fr, b, s, s_list[q]);
+                    else if (is_stat) for (int q = 0; q < c; ++q) comp_add(acc, comp, stat_channel(fr, b, s, s_list[q]));
                     cnt += c;
                 } else if (is_stat) {
                     for (int q = 0; q < c; ++q) {
                         const float d = stat_channel(fr, b, s, s_list[q]) - mean;
-                        acc += d * d;
+                        comp_add(acc, comp, d * d);
                     }
                 }
                 __syncthreads();
@@ -191,7 +200,7 @@ __global__ __launch_bounds__(256) void object_descriptors_kernel(const rtk_track
                     mean = acc / (float)cnt;
                     dk[s < 3 ? s : 131 + s] = mean;          // centre (0..2) | mean flow (134..136) | mean (RCS, v_r) (137..138)
                 }
-                acc = 0.f;
+                acc = 0.f; comp = 0.f;
             } else if (is_stat && (s < 3 || s >= 6)) {
                 desc[base_b + (size_t)k * RTK_DESC + (s < 3 ? 3 + s : 133 + s)] = acc / (float)cnt;   // var xyz (3..5) | var (139..140)
             }
