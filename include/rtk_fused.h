@@ -122,6 +122,10 @@ RTK_EXPORT int rtk_pointwise_mlp_pair(int rows, int rows_per_sample, int nsrc, c
  * out (samples*npoint, out_pitch) receives 16*last.cout16 channels at out_offset.
  * src_nuniq / dst_nuniq (optional, (samples)): duplicate-row counters of the source level (q rows >= src_nuniq[b]
  * are read as row 0) and of the centroid level (centroids >= dst_nuniq[b] are skipped: neither computed nor written).
+ * What the entries may READ of those skipped centroids (this entry point and rtk_sa_scale_split; not the _serial ones): their
+ * prologue requests the idx and new_xyz rows of every wave's first group of centroids before dst_nuniq[b] has arrived, so rows of
+ * centroids in [dst_nuniq[b], npoint) may be loaded -- always inside the (samples, npoint) tables -- and are then discarded: no
+ * address and no output value is formed from them, whatever they hold (uninitialised memory included).
  * Non-finite inputs (this entry point and rtk_sa_scale_split): the ReLU and the max over the neighbours follow IEEE maxNum and drop a
  * NaN (the reference propagates it), so an output can be finite where the reference's is NaN; it is never non-finite where the
  * reference's is finite.  The cost volume and patch cost below propagate: non-finite exactly where the reference is. */
@@ -131,8 +135,8 @@ RTK_EXPORT int rtk_sa_scale(int samples, int n, int npoint, int nsample, const f
                             int out_pitch, int out_offset, const int *src_nuniq, const int *dst_nuniq,
                             rtk_stream_t stream);
 
-/* rtk_sa_scale with the tile loop as it was before it was software-pipelined (one unit's loads requested, waited for and used
- * before the next unit's go out).  Same arguments, bit-identical result; the comparison implementation of tests and timing tools,
+/* rtk_sa_scale with the prologue and the tile loop as they were before the loop was software-pipelined (one unit's loads requested,
+ * waited for and used before the next unit's go out; no row of a centroid >= dst_nuniq[b] is read).  Same arguments, bit-identical result; the comparison implementation of tests and timing tools,
  * not called by the package. */
 RTK_EXPORT int rtk_sa_scale_serial(int samples, int n, int npoint, int nsample, const float *xyz,
                                    const float *new_xyz, const int *idx, const float *q, int q_pitch, int c1_16,

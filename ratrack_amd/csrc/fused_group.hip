@@ -30,6 +30,15 @@ __device__ __forceinline__ f4 f4_relu(f4 a) { return (f4){fmaxf(a.x, 0.f), fmaxf
 #ifndef SA_MAX_WGS
 #define SA_MAX_WGS 1024
 #endif
+// How many units ahead of its use the pipelined loop requests a unit's centroid and ball index (the gathers stay one unit ahead).
+// 1: at the top of the unit before, needed behind that unit's layer 1 -- one dependent round trip per tile.  2: a whole tile earlier,
+// four more registers of state and a third copy of the loop body.  An instance may take 2 only where its code object keeps 0 scratch, 0
+// spills and <= 128 registers with it (sa_index_ahead, the place for an exception: today all five fit, 68 - 108 registers; the same
+// macro and rule in fused_split.hip).  Measured slower than 1 at every configuration: the default is 1.
+#ifndef SA_INDEX_AHEAD
+#define SA_INDEX_AHEAD 1
+#endif
+constexpr int sa_index_ahead(int ns, int v1, int v2, int v3) { return SA_INDEX_AHEAD == 2 ? 2 : 1; }
 struct SaParams {
     int samples, n, npoint;
     const float *xyz, *new_xyz;
@@ -67,15 +76,6 @@ __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
     // back-fills them, which spreads the live work evenly.
     int b, bx, nbx;
     rtk_decode_block(P.gx, b, bx, nbx);
-    const int dst_e = P.dst_nuniq ? __builtin_amdgcn_readfirstlane(P.dst_nuniq[b]) : P.npoint;
-    const int live_c = min(dst_e, P.npoint);                 // centroids >= live_c are duplicates of centroid 0: neither computed nor written
-    const int live_groups = (live_c + CPT - 1) / CPT;
-    if (bx * 4 >= live_groups) return;
-    for (int i = threadIdx.x; i < NF * 64; i += blockDim.x) s_w[i] = P.blob[i];
-    float w1[V1];
-#pragma unroll
-    for (int v = 0; v < V1; ++v) w1[v] = P.w1[v * 64 + lane];
-    __syncthreads();
     const int slot0 = j % NS;                         // neighbour slot of this lane within the first tile
     if constexpr (PIPE && TILES == 1) {
         // The serial loop below makes six dependent round trips per 16-position tile (src_nuniq + centroid, index, neighbour, q row +
@@ -84,10 +84,29 @@ __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
         // component 2 and select their constant afterwards (no branch around a load), and the gathers of unit u + 1 are in flight
         // under the MFMA chain of unit u: its ball index and centroid are requested at the top of u, its neighbour coordinate and q
         // row -- into registers of their own -- in front of u's layers 2 and 3.  Whether a next unit exists is wave-uniform; without
-        // one nothing is requested.  The lanes past live_c are redirected before every index load exactly as in the serial loop, so
-        // this loop reads the rows the serial one reads and no others.  Same operations on the same values: the same bits.
-        const int src_e = P.src_nuniq ? __builtin_amdgcn_readfirstlane(P.src_nuniq[b]) : 0x7fffffff;
+        // one nothing is requested.  The lanes past live_c are redirected before every index load exactly as in the serial loop.
+        // Same operations on the same values: the same bits.
+        //
+        // Prologue in two round trips (the serial one makes four: dst_nuniq -> fill and barrier -> src_nuniq, centroid, ball index ->
+        // gathers).  Trip 1 is everything whose address depends on no loaded value: both counters, this thread's words of the blob (into
+        // registers; stored to LDS behind the exit test), the offset weights, the bias fragments, and -- speculatively -- the
+        // UN-redirected centroid and ball index of the wave's first unit, the centroid clamped below npoint so that the address stays
+        // inside the tables whatever dst_nuniq holds.  A first unit wholly below live_c (wave-uniform) keeps them: they are what the
+        // redirected loads return.  Any other first unit discards them and loads again behind the redirection, so the kernel may READ
+        // ball and new_xyz rows of centroids in [live_c, npoint) but forms no address and no value from them.  Trip 2 is the gathers.
+        // A null counter reads a word that is always there (idx[0]) and is not used: no branch around a load.
+        constexpr int AH = sa_index_ahead(NS, V1, V2, V3);
+        constexpr int FILL = (NF * 64 + 255) / 256;         // words of the blob per thread
+        const int stride = nbx * 4;
+        int unit = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (an SGPR: the loop's branches are scalar)
         const int gc = g < 3 ? g : 2;
+        const int dst_w = *(P.dst_nuniq ? P.dst_nuniq + b : P.idx), src_w = *(P.src_nuniq ? P.src_nuniq + b : P.idx);
+        f4 blob_w[FILL];
+#pragma unroll
+        for (int k = 0; k < FILL; ++k) blob_w[k] = P.blob[min(k * 256 + (int)threadIdx.x, NF * 64 - 1)];
+        float w1[V1];
+#pragma unroll
+        for (int v = 0; v < V1; ++v) w1[v] = P.w1[v * 64 + lane];
         f4 b2[V3 ? V2 : 1], bl[VL];
         if constexpr (V3 != 0) {
 #pragma unroll
@@ -95,13 +114,24 @@ __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
         }
 #pragma unroll
         for (int v = 0; v < VL; ++v) bl[v] = bias_frag(V3 ? P.bias3 : P.bias2, v, g);
-        const int stride = nbx * 4;
-        int unit = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (an SGPR: the loop's branches are scalar)
+        const int c_s = b * P.npoint + min(unit * CPT + j / NS, P.npoint - 1);
+        const int id_s = P.idx[(long)c_s * NS + slot0];
+        const float cg_s = P.new_xyz[(long)c_s * 3 + gc];
+        __builtin_amdgcn_sched_barrier(0);      // (everything above is in flight before the first wait)
+        const int live_c = min(P.dst_nuniq ? __builtin_amdgcn_readfirstlane(dst_w) : P.npoint, P.npoint);
+        const int live_groups = (live_c + CPT - 1) / CPT;
+        if (bx * 4 >= live_groups) return;                     // (loads into registers may be outstanding, nothing else)
+        const int src_e = P.src_nuniq ? __builtin_amdgcn_readfirstlane(src_w) : 0x7fffffff;
+#pragma unroll
+        for (int k = 0; k < FILL; ++k)
+            if (k * 256 + (int)threadIdx.x < NF * 64) s_w[k * 256 + threadIdx.x] = blob_w[k];
+        __syncthreads();
         if (unit >= live_groups) return;                       // (no barrier follows)
-        // state of the unit in work (c, valid, cg and -- requested, not waited for -- nx, a1) and of the one after it (*_n)
-        int c, c_n = 0, id_n = 0;
-        bool valid, valid_n = false;
-        float cg, nx, cg_n = 0.f, nx_n = 0.f;
+        // state of the unit in work (c, valid, cg and -- requested, not waited for -- nx, a1), of the one after it (*_n) and, where the
+        // index is requested two units ahead (AH == 2), of the one after that (*_2: centroid and ball index only)
+        int c, c_n = 0, id_n = 0, c_2 = 0, id_2 = 0;
+        bool valid, valid_n = false, valid_2 = false;
+        float cg, nx, cg_n = 0.f, nx_n = 0.f, cg_2 = 0.f;
         f4 a1[V1], a1n[V1];
         auto centroid_of = [&](int u, int &cc, bool &vv) {        // global centroid index of this lane in unit u, redirected past live_c
             int cl = u * CPT + j / NS;
@@ -115,14 +145,21 @@ __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
 #pragma unroll
             for (int v = 0; v < V1; ++v) a[v] = *reinterpret_cast<const f4 *>(qrow + 16 * v);
         };
-        // one unit; MORE: another one follows, whose loads go out here.  (Two copies of the body, the steady state and the last unit,
-        // instead of a test inside one: behind a branch around a load the compiler has to wait as if the load had not been issued.)
-        auto tile = [&](auto more) {
-            constexpr bool MORE = decltype(more)::value;
-            if constexpr (MORE) {
-                centroid_of(unit + stride, c_n, valid_n);
-                id_n = P.idx[(long)c_n * NS + slot0];
-                cg_n = P.new_xyz[(long)c_n * 3 + gc];
+        auto request = [&](int u, int &cc, bool &vv, int &id, float &x) {      // centroid and ball index of unit u
+            centroid_of(u, cc, vv);
+            id = P.idx[(long)cc * NS + slot0];
+            x = P.new_xyz[(long)cc * 3 + gc];
+        };
+        // one unit; MORE: another one follows, whose gathers go out here; REQ: the centroid and ball index of the unit AH units ahead go
+        // out at the top (AH == 1: MORE's own, used behind layer 1 -- the one dependent round trip per tile; AH == 2: the unit after
+        // MORE's, a whole tile before its gathers need it).  (A copy of the body per combination -- the steady state, at AH == 2 the
+        // unit with one left, and the last unit -- instead of a test inside one: behind a branch around a load the compiler has to
+        // wait as if the load had not been issued.)
+        auto tile = [&](auto req, auto more) {
+            constexpr bool REQ = decltype(req)::value, MORE = decltype(more)::value;
+            if constexpr (REQ) {
+                if constexpr (AH == 2) request(unit + 2 * stride, c_2, valid_2, id_2, cg_2);
+                else request(unit + stride, c_n, valid_n, id_n, cg_n);
             }
             __builtin_amdgcn_sched_barrier(0);      // (the requests stay here: the scheduler otherwise moves them down to their first use)
             const float bop = g < 3 ? __fsub_rn(nx, cg) : 1.0f;
@@ -166,17 +203,45 @@ __global__ __launch_bounds__(256) void sa_scale_kernel(const SaParams P) {
                 for (int v = 0; v < VL; ++v) *reinterpret_cast<f4 *>(o + 16 * v) = best[v];
             }
         };
-        centroid_of(unit, c, valid);
-        cg = P.new_xyz[(long)c * 3 + gc];
-        gather(P.idx[(long)c * NS + slot0], nx, a1);
-        while (unit + stride < live_groups) {
-            tile(std::true_type{});
+        int id = id_s;
+        c = c_s; valid = true; cg = cg_s;
+        if ((unit + 1) * CPT > live_c) request(unit, c, valid, id, cg);      // (wave-uniform) a partial first unit: the dependent path
+        gather(id, nx, a1);
+        auto advance = [&]() {
             unit += stride; c = c_n; valid = valid_n; cg = cg_n; nx = nx_n;
             for (int v = 0; v < V1; ++v) a1[v] = a1n[v];      // (a rotation of registers; the trip count is a constant)
+        };
+        if constexpr (AH == 2) {
+            // the second unit's centroid and index travel with the first unit's gathers (no second unit: the first one's again, unused)
+            request(unit + stride < live_groups ? unit + stride : unit, c_n, valid_n, id_n, cg_n);
+            while (unit + 2 * stride < live_groups) {
+                tile(std::true_type{}, std::true_type{});
+                advance();
+                c_n = c_2; valid_n = valid_2; id_n = id_2; cg_n = cg_2;
+            }
+            if (unit + stride < live_groups) {
+                tile(std::false_type{}, std::true_type{});
+                advance();
+            }
+        } else {
+            while (unit + stride < live_groups) {
+                tile(std::true_type{}, std::true_type{});
+                advance();
+            }
         }
-        tile(std::false_type{});
+        tile(std::false_type{}, std::false_type{});
         return;
     }
+    // ---- the serial comparison kernel (rtk_sa_scale_serial; NS = 32 on either entry): prologue and loop as they were before ----
+    const int dst_e = P.dst_nuniq ? __builtin_amdgcn_readfirstlane(P.dst_nuniq[b]) : P.npoint;
+    const int live_c = min(dst_e, P.npoint);                 // centroids >= live_c are duplicates of centroid 0: neither computed nor written
+    const int live_groups = (live_c + CPT - 1) / CPT;
+    if (bx * 4 >= live_groups) return;
+    for (int i = threadIdx.x; i < NF * 64; i += blockDim.x) s_w[i] = P.blob[i];
+    float w1[V1];
+#pragma unroll
+    for (int v = 0; v < V1; ++v) w1[v] = P.w1[v * 64 + lane];
+    __syncthreads();
     for (int unit = bx * 4 + (threadIdx.x >> 6); unit < live_groups; unit += nbx * 4) {
         int cl = unit * CPT + (NS >= 16 ? 0 : j / NS);        // centroid of this lane within the sample
         const bool valid = cl < live_c;                       // (a group of 16 / NS centroids may straddle dst_nuniq)

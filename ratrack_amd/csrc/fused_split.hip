@@ -787,6 +787,15 @@ struct SaSplitParams {
 #ifndef SA_EPI_FENCE_ALL
 #define SA_EPI_FENCE_ALL 0
 #endif
+// How many units ahead of its use the pipelined loops request a unit's centroid and ball index (the gathers stay one unit ahead).
+// 1: at the top of the unit before, needed behind that unit's layer 1 -- one dependent round trip per tile.  2: a whole tile earlier,
+// five more registers of state and a third copy of the loop body.  An instance may take 2 only where its code object keeps 0 scratch, 0
+// spills and <= 128 registers with it (sa_split_index_ahead, the place for an exception: today all three fit, 128 / 128 / 120; the
+// same macro and rule in fused_group.hip).  Measured slower than 1 at every configuration: the default is 1.
+#ifndef SA_INDEX_AHEAD
+#define SA_INDEX_AHEAD 1
+#endif
+constexpr int sa_split_index_ahead(int ns, int c1) { return SA_INDEX_AHEAD == 2 ? 2 : 1; }
 // PIPE: the tile loop software-pipelined by one unit with its constants out of the loop (the first of the two loops below); false: the
 // loop as it was before (rtk_sa_scale_split_serial, the comparison implementation).  The two compute the same bits.
 template <int NS, int C1, bool PIPE>
@@ -800,36 +809,55 @@ __global__ __launch_bounds__(256, SA_SPLIT_WAVES) void sa_scale_split_kernel(con
     const int lane = threadIdx.x & 63, hh = lane >> 5, col = lane & 31, pp = col / NS, slot = col % NS;
     int b, bx, nbx;
     rtk_decode_block(P.gx, b, bx, nbx);
-    const int dst_e = P.dst_nuniq ? __builtin_amdgcn_readfirstlane(P.dst_nuniq[b]) : P.npoint;
-    const int live_c = min(dst_e, P.npoint);                      // centroids >= live_c are duplicates of centroid 0: neither computed nor written
-    const int live_units = (live_c + CPT - 1) / CPT;
-    if (bx * 4 >= live_units) return;
     __shared__ __attribute__((aligned(16))) float s_bias2[PIPE ? 64 : 4];     // PIPE: bias2 and the offset image [KS][64] behind the image
     __shared__ float s_w1[PIPE ? KS * 64 : 1];
-    for (int i = threadIdx.x; i < NFR * 64; i += blockDim.x) s_img[i] = P.image[i];
-    if constexpr (PIPE) {
-        if (threadIdx.x < 64) s_bias2[threadIdx.x] = P.bias2[threadIdx.x];
-        for (int i = threadIdx.x; i < KS * 64; i += blockDim.x) s_w1[i] = P.w1[i];
-    }
-    __syncthreads();
-    const int src_e = P.src_nuniq ? P.src_nuniq[b] : 0x7fffffff;
-    const float winv = ldc(P.wsc);
     if constexpr (PIPE) {
         // The serial loop below reloads the 2 VB1 offset weights of a lane and its eight bias2 fragments on every tile (the latter
         // only after the last layer-2 MFMA, waited for one by one) and makes three dependent round trips per tile: ball index ->
         // coordinates and q rows -> bias.  Here the offset image and bias2 live in LDS behind the split image (filled with it), and the gathers of unit u + 1 are in flight under unit u's layer 2: its ball index and centroid are requested at the top
         // of u, its neighbour coordinates and q rows -- into registers of their own, which become layer 1's accumulators at the top of
         // the next trip -- under u's layer-2 MFMAs (SA_GATHER_STEP).  Whether a next unit exists is wave-uniform; without one nothing is
-        // requested.  Lanes past live_c are redirected before every index load as in the serial loop: the same rows are read.
+        // requested.  Lanes past live_c are redirected before every index load as in the serial loop.
+        //
+        // Prologue in two round trips (the serial one makes four: dst_nuniq -> fill and barrier -> src_nuniq, centroid, ball index ->
+        // gathers).  Trip 1 is everything whose address depends on no loaded value: both counters, this thread's words of the image, the
+        // offset image and bias2 (into registers; stored to LDS behind the exit test), the weight scale, and -- speculatively -- the
+        // UN-redirected centroid and ball index of the wave's first unit, the centroid clamped below npoint so that the address stays
+        // inside the tables whatever dst_nuniq holds.  A first unit wholly below live_c (wave-uniform) keeps them: they are what the
+        // redirected loads return.  Any other first unit discards them and loads again behind the redirection, so the kernel may READ
+        // ball and new_xyz rows of centroids in [live_c, npoint) but forms no address and no value from them.  Trip 2 is the gathers.
+        // A null counter reads a word that is always there (idx[0]) and is not used: no branch around a load.
+        constexpr int AH = sa_split_index_ahead(NS, C1);
         const int stride = nbx * 4;
         int unit = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (an SGPR: the loop's branches are scalar)
+        const int dst_w = *(P.dst_nuniq ? P.dst_nuniq + b : P.idx), src_w = *(P.src_nuniq ? P.src_nuniq + b : P.idx);
+        static_assert(NFR * 64 == KS * 256 && KS * 64 <= 256, "the fill below: KS words of the image and one of w1 per thread");
+        f4 img_w[KS];
+#pragma unroll
+        for (int k = 0; k < KS; ++k) img_w[k] = P.image[k * 256 + threadIdx.x];
+        const float w1_w = P.w1[threadIdx.x & (KS * 64 - 1)], bias_w = P.bias2[threadIdx.x & 63];
+        const float winv = ldc(P.wsc);
+        const int c_s = b * P.npoint + min(unit * CPT + pp, P.npoint - 1);
+        const int id_s = P.idx[(long)c_s * NS + slot];
+        const float ca_s = P.new_xyz[(long)c_s * 3 + hh], cb_s = P.new_xyz[(long)c_s * 3 + 2];
+        __builtin_amdgcn_sched_barrier(0);      // (everything above is in flight before the first wait)
+        const int live_c = min(P.dst_nuniq ? __builtin_amdgcn_readfirstlane(dst_w) : P.npoint, P.npoint);
+        const int live_units = (live_c + CPT - 1) / CPT;
+        if (bx * 4 >= live_units) return;                     // (loads into registers may be outstanding, nothing else)
+        const int src_e = P.src_nuniq ? src_w : 0x7fffffff;
+#pragma unroll
+        for (int k = 0; k < KS; ++k) s_img[k * 256 + threadIdx.x] = img_w[k];
+        if (threadIdx.x < KS * 64) s_w1[threadIdx.x] = w1_w;
+        if (threadIdx.x < 64) s_bias2[threadIdx.x] = bias_w;
+        __syncthreads();
         if (unit >= live_units) return;                       // (no barrier follows)
         // A lane's two operands of the offset layer are (dx, dz) (hh = 0) or (dy, 1) (hh = 1): it loads component hh and component 2 of
         // the neighbour and of the centroid -- every lane both, the lanes hh = 1 select their constant afterwards.
-        // State of the unit in work (c, valid, ca, cb and -- requested, not waited for -- na, nb, a) and of the one after it (*_n).
-        int c, c_n = 0, id_n = 0;
-        bool valid, valid_n = false;
-        float ca, cb, na, nb, ca_n = 0.f, cb_n = 0.f, na_n = 0.f, nb_n = 0.f;
+        // State of the unit in work (c, valid, ca, cb and -- requested, not waited for -- na, nb, a), of the one after it (*_n) and,
+        // where the index is requested two units ahead (AH == 2), of the one after that (*_2: centroid and ball index only).
+        int c, c_n = 0, id_n = 0, c_2 = 0, id_2 = 0;
+        bool valid, valid_n = false, valid_2 = false;
+        float ca, cb, na, nb, ca_n = 0.f, cb_n = 0.f, na_n = 0.f, nb_n = 0.f, ca_2 = 0.f, cb_2 = 0.f;
         f16v a[VB1], an[VB1];
         auto centroid_of = [&](int u, int &cc, bool &vv) {        // global centroid index of this lane in unit u, redirected past live_c
             int cl = u * CPT + pp;
@@ -849,15 +877,22 @@ __global__ __launch_bounds__(256, SA_SPLIT_WAVES) void sa_scale_split_kernel(con
                     r[v][4 * q] = t.x; r[v][4 * q + 1] = t.y; r[v][4 * q + 2] = t.z; r[v][4 * q + 3] = t.w;
                 }
         };
-        // one unit; MORE: another one follows, whose loads go out here.  (Two copies of the body, the steady state and the last unit,
-        // instead of a test inside one: behind a branch around a load the compiler has to wait as if the load had not been issued.)
-        auto tile = [&](auto more) {
-            constexpr bool MORE = decltype(more)::value;
+        auto request = [&](int u, int &cc, bool &vv, int &id, float &xa, float &xb) {      // centroid and ball index of unit u
+            centroid_of(u, cc, vv);
+            id = P.idx[(long)cc * NS + slot];
+            xa = P.new_xyz[(long)cc * 3 + hh]; xb = P.new_xyz[(long)cc * 3 + 2];
+        };
+        // one unit; MORE: another one follows, whose gathers go out here; REQ: the centroid and ball index of the unit AH units ahead go
+        // out at the top (AH == 1: MORE's own, used behind layer 1 -- the one dependent round trip per tile; AH == 2: the unit after
+        // MORE's, a whole tile before its gathers need it).  (A copy of the body per combination -- the steady state, at AH == 2 the
+        // unit with one left, and the last unit -- instead of a test inside one: behind a branch around a load the compiler has to
+        // wait as if the load had not been issued.)
+        auto tile = [&](auto req, auto more) {
+            constexpr bool REQ = decltype(req)::value, MORE = decltype(more)::value;
             constexpr int GS = KS == 4 ? SA_GATHER_STEP : 0;
-            if constexpr (MORE) {
-                centroid_of(unit + stride, c_n, valid_n);
-                id_n = P.idx[(long)c_n * NS + slot];
-                ca_n = P.new_xyz[(long)c_n * 3 + hh]; cb_n = P.new_xyz[(long)c_n * 3 + 2];
+            if constexpr (REQ) {
+                if constexpr (AH == 2) request(unit + 2 * stride, c_2, valid_2, id_2, ca_2, cb_2);
+                else request(unit + stride, c_n, valid_n, id_n, ca_n, cb_n);
             }
             __builtin_amdgcn_sched_barrier(0);      // (the requests stay here: the scheduler otherwise moves them down to their first use)
             const float b0 = __fsub_rn(na, ca), dz = __fsub_rn(nb, cb);
@@ -922,17 +957,44 @@ __global__ __launch_bounds__(256, SA_SPLIT_WAVES) void sa_scale_split_kernel(con
                 }
             }
         };
-        centroid_of(unit, c, valid);
-        ca = P.new_xyz[(long)c * 3 + hh]; cb = P.new_xyz[(long)c * 3 + 2];
-        gather(P.idx[(long)c * NS + slot], na, nb, a);
-        while (unit + stride < live_units) {
-            tile(std::true_type{});
+        int id = id_s;
+        c = c_s; valid = true; ca = ca_s; cb = cb_s;
+        if ((unit + 1) * CPT > live_c) request(unit, c, valid, id, ca, cb);      // (wave-uniform) a partial first unit: the dependent path
+        gather(id, na, nb, a);
+        auto advance = [&]() {
             unit += stride; c = c_n; valid = valid_n; ca = ca_n; cb = cb_n; na = na_n; nb = nb_n;
             for (int v = 0; v < VB1; ++v) a[v] = an[v];       // (a rotation of registers; the trip count is a constant)
+        };
+        if constexpr (AH == 2) {
+            // the second unit's centroid and index travel with the first unit's gathers (no second unit: the first one's again, unused)
+            request(unit + stride < live_units ? unit + stride : unit, c_n, valid_n, id_n, ca_n, cb_n);
+            while (unit + 2 * stride < live_units) {
+                tile(std::true_type{}, std::true_type{});
+                advance();
+                c_n = c_2; valid_n = valid_2; id_n = id_2; ca_n = ca_2; cb_n = cb_2;
+            }
+            if (unit + stride < live_units) {
+                tile(std::false_type{}, std::true_type{});
+                advance();
+            }
+        } else {
+            while (unit + stride < live_units) {
+                tile(std::true_type{}, std::true_type{});
+                advance();
+            }
         }
-        tile(std::false_type{});
+        tile(std::false_type{}, std::false_type{});
         return;
     }
+    // ---- the serial comparison kernel (rtk_sa_scale_split_serial): prologue and loop as they were before the pipelined one ----
+    const int dst_e = P.dst_nuniq ? __builtin_amdgcn_readfirstlane(P.dst_nuniq[b]) : P.npoint;
+    const int live_c = min(dst_e, P.npoint);                      // centroids >= live_c are duplicates of centroid 0: neither computed nor written
+    const int live_units = (live_c + CPT - 1) / CPT;
+    if (bx * 4 >= live_units) return;
+    for (int i = threadIdx.x; i < NFR * 64; i += blockDim.x) s_img[i] = P.image[i];
+    __syncthreads();
+    const int src_e = P.src_nuniq ? P.src_nuniq[b] : 0x7fffffff;
+    const float winv = ldc(P.wsc);
     for (int unit = bx * 4 + (threadIdx.x >> 6); unit < live_units; unit += nbx * 4) {
         int cl = unit * CPT + pp;                                  // centroid of this lane within the sample
         const bool valid = cl < live_c;
