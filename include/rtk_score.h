@@ -39,6 +39,7 @@ extern "C" {
 #define RTK_SCORE_FLAG_TABLE 64      /* rtk_track_score_memory: a table_count outside [num_objects, Kobj] (clamped) */
 #define RTK_SCORE_FLAG_HOTA 128      /* rtk_score_hota: a clip with more labels, track ids or pairs than its tables hold (outputs unspecified) */
 #define RTK_SCORE_FLAG_IDENTITY 256  /* rtk_score_identity: the same, of its tables */
+#define RTK_SCORE_FLAG_OPTIMAL 512   /* rtk_score_replay_optimal: a frame with more candidate pairs than RTK_SCORE_PAIR_EDGES (outputs unspecified) */
 
 /* LDS bytes of one workgroup for these sizes (host functions: no device is touched). */
 RTK_EXPORT int rtk_gt_objects_lds_bytes(int K, int N);
@@ -322,6 +323,78 @@ RTK_EXPORT int rtk_score_identity_lds_bytes(int T);
 RTK_EXPORT int rtk_score_identity(int B, int T, const rtk_score_log_t *log, const double *rec_score /* (B,R) or NULL */,
                                   const double *threshold /* device scalar, or NULL: nothing removed */, const double *alphas /* device, (count) */,
                                   int count, long long *counters /* (count,B,6) */, int *flags /* (B) */, rtk_stream_t stream);
+
+/* ---- Per-frame optimal matching at an IoU threshold (csrc/track_score_pairs.hip, csrc/track_optimal.hip, csrc/lds_assignment.h,
+ *      TrackScorer(sweep_pairs=...), TrackScorer.sweep(matching="optimal"), TrackScorer.clear_optimal) ------------------------------
+ *
+ * Everything above rests on rtk_track_score's matching rule: each detection takes its single best object, first come first served,
+ * no threshold, no second choice.  The KITTI / AB3DMOT evaluation matches otherwise: per frame ONE ASSIGNMENT of detections to
+ * ground-truth objects that refuses pairs below an IoU threshold, and on top of it id switches, fragmentations, MT / ML and the
+ * sweep over recall levels.  This section is that matching scheme on the reference's point IoU, at a threshold THE CALLER CHOOSES
+ * (there is no default: the threshold of the reference's evaluation is not known).  It is still NOT a reproduction of the reference
+ * README's table, whose threshold and evaluator are not distributed; HOTA and IDF1 stay under the greedy rule.
+ *
+ * The main log keeps only each detection's best object, from which no assignment can be computed afterwards; the pair log keeps
+ * every overlap.  Per frame of the main log (same frame index), for every detection i and kept object j with common > 0, in
+ * (i, then j) order: */
+typedef struct {
+    int Q;                        /* pairs per stream */
+    int *cursor;                  /* (B) pairs logged so far */
+    int *frame_pair;              /* (B,F,2) first pair | pair count of the frame in the main log's slot of the same index */
+    int *pair_key;                /* (B,Q) i << 8 | j: i the detection's index in the frame, j the index into the frame's kept labels */
+    int *pair_common;             /* (B,Q) the pair's `common` count (> 0) */
+    int *rec_size;                /* (B,R) the detection's point count, aligned with the main log's records */
+    int *label_size;              /* (B,R) the kept object's size, aligned with the main log's label entries */
+} rtk_score_pairs_t;
+
+/* rtk_track_score_logged (mem == NULL) or rtk_track_score_memory with a log, bit for bit -- every counter, state tensor, output and
+ * tensor of rtk_score_log_t -- in the same single launch, which also appends the frame's pairs.  A frame is logged whole or not at
+ * all: the fit test of the main log gains "its pairs fit Q", and a frame that does not fit is in neither log and raises
+ * RTK_SCORE_FLAG_LOG (the only way the main log can differ from rtk_track_score_logged's).  Every word has one writer (detection i's
+ * thread writes row i's pairs behind an ordered prefix of the rows' pair counts) and plain stores: the same bits on every run.  LDS:
+ * rtk_track_score_lds_bytes / rtk_track_score_memory_lds_bytes, nothing more.  The caller zero-initialises the block; only this
+ * entry point writes it. */
+RTK_EXPORT int rtk_track_score_pairs(const rtk_track_score_in_t *in, const rtk_track_score_state_t *state, const rtk_track_score_out_t *out,
+                                     const rtk_score_log_t *log, const rtk_score_memory_t *mem /* NULL: no track memory */,
+                                     const rtk_score_pairs_t *pairs, rtk_stream_t stream);
+
+/* The replay under the optimal matching, per (stream, threshold t), frames in log order:
+ *   removal      the sweep's: a detection whose track score is < t is removed (equal stays).
+ *   candidates   every logged pair (i, j, c) whose detection remains and whose IoU = (double)c / (double)(|i| + |j| - c) -- the
+ *                logged integers, as rtk_track_score computes it -- is >= min_iou (float64 >=: an IoU equal to min_iou stays).  A
+ *                pair whose denominator is not positive is no candidate (coincident points count once per PAIR, so c can exceed
+ *                a size, and the IoU can exceed 1).
+ *   assignment   la_solve (csrc/lds_assignment.h) with rows = detections, columns = kept objects and weight
+ *                (1 << 23) + min(floor(iou * 65536), 65536): an IoU above 1 weighs as 1.  With at most 64 columns the IoU parts sum to at most 2^22, so the optimum is "most
+ *                matches first, then the largest quantised IoU sum": the KITTI cost matrix with its max_cost sentinel.  The total
+ *                weight is tp * 2^23 + iou_q: tp, fp, fn and iou_q are unique even where the optimal matching is not; which
+ *                matching comes out is the solver's documented choice (rows enter in order, ties go to the smaller column).
+ *   counters     frames | gt | pred (the remaining detections) | tp | fp | fn | idsw | frag | tracks | mt | pt | ml.  The per-clip
+ *                track table is rtk_track_score's (append on first sight, 0.8 / 0.2 at the clip's close, idsw against the entry's
+ *                last matched track id; clips still open are closed at the end).  frag += 1 for an entry that is matched now, was
+ *                matched at some earlier frame, and was seen but unmatched in its previous seen frame.
+ *   outputs      iou_q (count,B) int64 the sum of the quantised IoUs of the matches; iou_sum (count,B) float64 the matched IoUs
+ *                added in kept-object order, frames in order, from 0; tp_mask as rtk_score_replay writes it (index 0 only).
+ * Integers and ordered float64 sums only: the same bits on every run. */
+#define RTK_SCORE_OPTIMAL_COUNTERS 12
+/* Most candidate pairs of one frame: the edges of the assignment, sized from the LDS budget. */
+#define RTK_SCORE_PAIR_EDGES 2048
+
+/* LDS bytes of one workgroup of rtk_score_replay_optimal for T track-table entries (a host function: no device is touched); -1 for a
+ * T below 1.  Built for two capacities, 1024 and the largest that fits RTK_SCORE_LDS_LIMIT; a T takes the smaller one that holds it:
+ * this is that instance's figure, or for a larger T what its tables would need. */
+RTK_EXPORT int rtk_score_optimal_lds_bytes(int T);
+
+/* Grid (stream, threshold index), one wave each; the arguments rtk_score_replay takes, plus the pair log, min_iou (finite, > 0),
+ * iou_q and flags.  The log is walked with rtk_score_replay's clamps, and a pair whose indices, sizes or count do not describe its
+ * frame is skipped, so a foreign buffer is never read out of bounds.  A frame of stream b with more candidates than
+ * RTK_SCORE_PAIR_EDGES raises RTK_SCORE_FLAG_OPTIMAL in flags[b] (or-ed in; nothing else of flags is touched): that stream's outputs
+ * are then unspecified but written, the other streams are unaffected.  A T whose tables do not fit RTK_SCORE_LDS_LIMIT is refused. */
+RTK_EXPORT int rtk_score_replay_optimal(int B, int T, const rtk_score_log_t *log, const rtk_score_pairs_t *pairs, const double *rec_score,
+                                        const double *thresholds, const int *reached, int count, double min_iou,
+                                        long long *counters /* (count,B,12) */, long long *iou_q /* (count,B) */,
+                                        double *iou_sum /* (count,B) */, unsigned char *tp_mask /* NULL or (B,R) */, int *flags /* (B) */,
+                                        rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -103,6 +103,10 @@ class ScoreMemory(ctypes.Structure):
     _fields_ = [(n, _p) for n in ("table_ids", "table_count", "row_track", "labelled_coasted")]
 
 
+class ScorePairs(ctypes.Structure):
+    _fields_ = [("Q", _i)] + [(n, _p) for n in ("cursor", "frame_pair", "pair_key", "pair_common", "rec_size", "label_size")]
+
+
 # ---- include/rtk_train.h --------------------------------------------------------------------------------------------------------
 
 class BnFin(ctypes.Structure):
@@ -141,13 +145,13 @@ STRUCTS = {
     "rtk_gt_boxes_t": GtBoxes, "rtk_gt_in_t": GtIn, "rtk_gt_out_t": GtOut, "rtk_eval_in_t": EvalIn,
     "rtk_gt_objects_in_t": GtObjectsIn, "rtk_gt_objects_out_t": GtObjectsOut, "rtk_track_score_in_t": ScoreIn,
     "rtk_track_score_state_t": ScoreState, "rtk_track_score_out_t": ScoreOut, "rtk_score_log_t": ScoreLog,
-    "rtk_score_memory_t": ScoreMemory,
+    "rtk_score_memory_t": ScoreMemory, "rtk_score_pairs_t": ScorePairs,
     "rtk_bn_fin_t": BnFin, "rtk_tn_job_t": TnJob, "rtk_pack_job_t": PackJob, "rtk_inverse_index_job_t": InverseIndexJob,
     "rtk_pool_src_t": PoolSrc, "rtk_pw_operand_t": PwOperand, "rtk_pw_wgrad_job_t": PwWgradJob,
 }
 
 # name -> argtypes.  A struct pointer that callers pass as ctypes.addressof() is _p; one they pass as an array or byref() is typed.
-# The argument blocks of rtk_gt.h and rtk_score.h (GtIn, GtOut, EvalIn, GtObjectsIn, ..., ScoreOut, ScoreLog, ScoreMemory) and rtk_track_frame_t go by
+# The argument blocks of rtk_gt.h and rtk_score.h (GtIn, GtOut, EvalIn, GtObjectsIn, ..., ScoreOut, ScoreLog, ScoreMemory, ScorePairs) and rtk_track_frame_t go by
 # address; the *_lds_bytes are host functions that return a byte count.
 SIGNATURES = {
     # ---- include/rtk_pointnet2.h
@@ -223,6 +227,9 @@ SIGNATURES = {
     "rtk_score_hota": [_i, _i, _p, _p, _p, _i, _p, _p, _p, _p],
     "rtk_score_identity_lds_bytes": [_i],
     "rtk_score_identity": [_i, _i, _p, _p, _p, _p, _i, _p, _p, _p],
+    "rtk_track_score_pairs": [_p, _p, _p, _p, _p, _p, _p],
+    "rtk_score_optimal_lds_bytes": [_i],
+    "rtk_score_replay_optimal": [_i, _i, _p, _p, _p, _p, _p, _i, _d, _p, _p, _p, _p, _p, _p],
     # ---- include/rtk_train.h
     "rtk_bn_train_stats": [_i] * 5 + [_p] * 3 + [_p],
     "rtk_bn_relu_fwd": [_i] * 5 + [_p, _p, _i, _p, _p],

@@ -13,6 +13,16 @@ __device__ __forceinline__ float bcn_at(const rtk_bcn_view_t &v, int b, int c, i
 // a count read from the device, brought into [0, hi]
 __device__ __forceinline__ int count_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
+// the sum of x over the lanes up to and including this one (an ordered prefix: lane order is the order of the sum)
+__device__ __forceinline__ int wave_inclusive_scan(int x, int lane) {
+#pragma unroll
+    for (int o = 1; o < RTK_WAVE; o <<= 1) {
+        const int y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    return x;
+}
+
 // one frame of the batched tracker (rtk_track_frame_t): does stream b take part, and how many of its N columns are points
 __device__ __forceinline__ bool stream_active(const rtk_track_frame_t &fr, int b) { return !fr.active || fr.active[b]; }
 

@@ -1,6 +1,6 @@
 // track_score_body.h -- the LDS layout, the body and the argument checks of the scoring kernels: rtk_track_score and
-// rtk_track_score_logged (track_score.hip) and rtk_track_score_memory (track_score_memory.hip) instantiate the one body, each kernel
-// behind a __global__ wrapper of its own in the file of its entry point.
+// rtk_track_score_logged (track_score.hip), rtk_track_score_memory (track_score_memory.hip) and rtk_track_score_pairs
+// (track_score_pairs.hip) instantiate the one body, each kernel behind a __global__ wrapper of its own in the file of its entry point.
 #pragma once
 #include <math.h>
 
@@ -27,10 +27,17 @@ static inline size_t ts_score_memory_lds(int Kobj, int K, int N) { return ts_sco
 // MEM: the record (prev_gt_id, prev_count, and mm.row_track beside them) covers every row of the tracker's new table, not only this
 // frame's detections -- thread r gives row r >= P the label id of the old record's first row with the same track id (a scan of at
 // most Kobj words of LDS), thread 0 counts the labelled ones.  Without MEM `mm` is not read.
-template <bool LOG, bool MEM>
+// PAIRS (only with LOG): the frame's (detection, kept object) pairs with common > 0 are appended to the pair log (rtk_score_pairs_t)
+// in (i, then j) order -- thread i counts row i's pairs, an ordered prefix over the rows (a wave scan, the four wave totals through
+// scal[4..7], one barrier more) gives every row its place and the frame its pair count, which joins the fit test; thread i then writes
+// its row's pairs and its size, thread j the j-th kept object's size, thread 0 the frame's slot and the cursor.  Without PAIRS `pr` is
+// not read and the body is what it was.
+static_assert(RTK_SCORE_MAX_OBJECTS <= TS_THREADS, "PAIRS: one thread per detection row");
+template <bool LOG, bool MEM, bool PAIRS = false>
 __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in, const rtk_track_score_state_t &st,
                                                  const rtk_track_score_out_t &out, const rtk_score_log_t &lg,
-                                                 const rtk_score_memory_t &mm) {
+                                                 const rtk_score_memory_t &mm, const rtk_score_pairs_t &pr = rtk_score_pairs_t{}) {
+    static_assert(LOG || !PAIRS, "the pair log goes with the main log");
     extern __shared__ __attribute__((aligned(16))) unsigned char ts_smem[];
     const int b = blockIdx.x, t = threadIdx.x, lane = t & (RTK_WAVE - 1), wave = t / RTK_WAVE;
     const int N = in.N, Kobj = in.Kobj, K = in.K, T = in.T, W = (N + 31) / 32;
@@ -75,6 +82,8 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
         log_l = lg.cursor[b * 4 + 2];
         log_fits = log_f >= 0 && log_f < lg.F && log_r >= 0 && log_r <= lg.R - P && log_l >= 0 && log_l <= lg.R - G;
     }
+    int log_q = 0, pair_at = 0, pair_total = 0;      // PAIRS: the pair cursor, the first pair of this thread's row, the frame's pairs
+    if (PAIRS) log_q = pr.cursor[b];
 
     if (t < 8) scal[t] = 0;
     for (int i = t; i < Kobj; i += TS_THREADS) {
@@ -151,6 +160,24 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
     }
     __syncthreads();
 
+    // ---- PAIRS: the rows' pair counts, their ordered prefix, and whether the frame's pairs fit ----
+    if (PAIRS) {
+        int mine = 0;
+        if (t < P) {
+            for (int j = 0; j < G; ++j) mine += common[t * K + j] > 0 ? 1 : 0;
+        }
+        const int upto = wave_inclusive_scan(mine, lane);
+        if (lane == RTK_WAVE - 1) scal[4 + wave] = upto;      // 4..7: free since the reset's barrier
+        __syncthreads();
+        for (int w = 0; w < TS_WAVES; ++w) {
+            const int total = scal[4 + w];
+            if (w < wave) pair_at += total;
+            pair_total += total;
+        }
+        pair_at += upto - mine;
+        log_fits = log_fits && log_q >= 0 && log_q <= pr.Q - pair_total;
+    }
+
     // ---- every prediction's best object: strict > from 0, the first of equals ----
     for (int i = t; i < P; i += TS_THREADS) {
         int bj = -1;
@@ -168,10 +195,21 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
             lg.rec_conf[r] = lg.object_conf[ob + i];
             lg.rec_best[r] = bj >= 0 ? glabel[bj] : -1;
             lg.rec_iou[r] = bi;
+            if (PAIRS) {
+                pr.rec_size[r] = psize[i];
+                size_t q = (size_t)b * pr.Q + log_q + pair_at;
+                for (int j = 0; j < G; ++j) {
+                    const int c = common[i * K + j];
+                    if (c > 0) { pr.pair_key[q] = (i << 8) | j; pr.pair_common[q] = c; ++q; }
+                }
+            }
         }
     }
     if (LOG && log_fits) {
-        for (int j = t; j < G; j += TS_THREADS) lg.label[(size_t)b * lg.R + log_l + j] = glabel[j];
+        for (int j = t; j < G; j += TS_THREADS) {
+            lg.label[(size_t)b * lg.R + log_l + j] = glabel[j];
+            if (PAIRS) pr.label_size[(size_t)b * lg.R + log_l + j] = gsize[j];
+        }
     }
     // ---- which table entry holds each kept object's label id ----
     for (int e = t; e < used; e += TS_THREADS) {
@@ -231,6 +269,11 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
                 int *fr = lg.frame + ((size_t)b * lg.F + log_f) * 4;
                 fr[0] = log_r; fr[1] = log_l; fr[2] = P | (reset ? 65536 : 0); fr[3] = G;
                 lg.cursor[b * 4 + 0] = log_f + 1; lg.cursor[b * 4 + 1] = log_r + P; lg.cursor[b * 4 + 2] = log_l + G;
+                if (PAIRS) {
+                    pr.frame_pair[((size_t)b * lg.F + log_f) * 2 + 0] = log_q;
+                    pr.frame_pair[((size_t)b * lg.F + log_f) * 2 + 1] = pair_total;
+                    pr.cursor[b] = log_q + pair_total;
+                }
             } else {
                 flags |= RTK_SCORE_FLAG_LOG;
             }

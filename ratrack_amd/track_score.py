@@ -92,8 +92,26 @@ assignment), but under this module's log -- a detection's best object only -- an
 use box IoU at 0.5 and are not these.  The definitions are in include/rtk_score.h; the device delivers integers, `identity_values`
 is the arithmetic.
 
+Optimal matching.  Everything above rests on `update`'s rule (best object, first come first served, no threshold).  The KITTI /
+AB3DMOT evaluation matches otherwise: per frame ONE ASSIGNMENT of detections to ground-truth objects that refuses pairs below an IoU
+threshold.  `TrackScorer(..., sweep_pairs=Q)` makes the scoring launch also log every (detection, kept object) pair with a common
+point (at most Q per stream; a frame whose pairs do not fit is in neither log and raises FLAG_LOG), and then
+
+    sw  = scorer.sweep(matching="optimal", min_iou=0.25)      # SweepResult, with frag and iou_q
+    op  = scorer.clear_optimal(min_iou=0.25, threshold=sw.best["threshold"])
+
+replay the log under that scheme: per frame the remaining detections and the kept objects are matched by an exact maximum-weight
+assignment (csrc/lds_assignment.h) over the pairs with IoU >= min_iou, weight 2^23 + floor(IoU * 65536) -- most matches first, then
+the largest quantised IoU sum --; idsw, the per-clip track table and MT / PT / ML are counted as `update` counts them, and frag counts
+an object matched again after a frame in which it was seen but unmatched.  tp, fp, fn and iou_q are unique; where several matchings
+are optimal the solver's documented choice (rows in order, ties to the smaller column) is taken.  `min_iou` has no default: the
+threshold of the reference's evaluation is not known.  THIS IS THE KITTI / AB3DMOT MATCHING SCHEME ON THE REFERENCE'S POINT IoU AT A
+THRESHOLD THE CALLER CHOOSES; it is still not a reproduction of the reference README's numbers, whose threshold and evaluator are not
+distributed.  HOTA and IDF1 stay under the greedy rule.  The greedy path is untouched: without `sweep_pairs` the scorer issues the
+launches it always issued.
+
 Nothing here synchronises with the device except `GtObjects.check()`, `TrackScorer.check()`, `TrackScorer.result()`,
-`TrackScorer.sweep()`, `TrackScorer.hota()` and `TrackScorer.identity()`.
+`TrackScorer.sweep()`, `TrackScorer.hota()`, `TrackScorer.identity()` and `TrackScorer.clear_optimal()`.
 """
 import ctypes
 
@@ -101,7 +119,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .abi import GtBoxes, GtObjectsIn, GtObjectsOut, ScoreIn, ScoreLog, ScoreMemory, ScoreOut, ScoreState, stream as _stream, view as _view
+from .abi import GtBoxes, GtObjectsIn, GtObjectsOut, ScoreIn, ScoreLog, ScoreMemory, ScoreOut, ScorePairs, ScoreState, stream as _stream, view as _view
 from .gt_device import _flag_bytes, _n_valid
 
 LDS_LIMIT = 65536                      # RTK_SCORE_LDS_LIMIT
@@ -120,6 +138,9 @@ HOTA_PAIRS = 1024                      # RTK_SCORE_HOTA_PAIRS
 FLAG_IDENTITY = 256                    # RTK_SCORE_FLAG_IDENTITY
 IDENTITY_COUNTERS = ("frames", "clips", "gt", "pred", "idtp", "pairs")
 IDENTITY_PAIRS = 1024                  # RTK_SCORE_ID_PAIRS
+FLAG_OPTIMAL = 512                     # RTK_SCORE_FLAG_OPTIMAL
+OPTIMAL_COUNTERS = ("frames", "gt", "pred", "tp", "fp", "fn", "idsw", "frag", "tracks", "mt", "pt", "ml")
+PAIR_EDGES = 2048                      # RTK_SCORE_PAIR_EDGES
 
 
 # ---- what fits -------------------------------------------------------------------------------------------------------------
@@ -256,7 +277,10 @@ class SweepResult:
     smota (NaN at index 0), motp, moda, recall, precision.  amota, samota, amotp.  `best`: dict of the level of the largest MOTA
     (level, threshold, mota, moda, recall, precision, mt_fraction, pt_fraction, ml_fraction and the raw counts), None when no level
     was reached.  `unfiltered`: the pooled index-0 counts and iou_sum.  `counters` (L+1,B,11) int64 and `iou_sums` (L+1,B) float64 per
-    stream; `flags` (B)."""
+    stream; `flags` (B).  `matching` "greedy" or "optimal" and `min_iou` (None for greedy).  Under the optimal matching also `frag`
+    (L+1) int64, the pooled fragmentations per level, and `iou_q` (L+1) int64, the pooled sums of the matches' IoUs quantised to
+    1/65536 (both 0 past `reached`), with `frag_streams` and `iou_q_streams` (L+1,B) per stream; under the greedy rule they are
+    None.  MOTP is iou_sum / tp under either."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -313,6 +337,35 @@ def sweep_values(counters, iou_sums, thresholds, reached, levels):
         best = dict(counts(best), level=best, threshold=float(out["thresholds"][best]), mota=float(mota[best]), moda=float(moda[best]),
                     smota=float(smota[best]), motp=float(motp[best]), recall=float(recall[best]), precision=float(precision[best]), **frac)
     out["best"] = best
+    return out
+
+
+def optimal_values(counters, iou_sum):
+    """(..., 12) integer counts in OPTIMAL_COUNTERS order and (...) float64 IoU sums -> dict of float64 arrays: mota, moda, recall,
+    precision, motp (iou_sum / tp) and the mt / pt / ml fractions of tracks.  A ratio without a denominator is NaN."""
+    c = np.asarray(counters, dtype=np.float64)
+    g = lambda k: c[..., OPTIMAL_COUNTERS.index(k)]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return dict(mota=1.0 - (g("fn") + g("fp") + g("idsw")) / g("gt"), moda=1.0 - (g("fn") + g("fp")) / g("gt"),
+                    recall=g("tp") / g("gt"), precision=g("tp") / g("pred"), motp=np.asarray(iou_sum, dtype=np.float64) / g("tp"),
+                    mt_fraction=g("mt") / g("tracks"), pt_fraction=g("pt") / g("tracks"), ml_fraction=g("ml") / g("tracks"))
+
+
+def optimal_sweep_values(counters, iou_q, iou_sums, thresholds, reached, levels):
+    """The sweep's arithmetic under the optimal matching, host only: counters (levels+1,B,12) in OPTIMAL_COUNTERS order, iou_q
+    (levels+1,B) int64 and iou_sums (levels+1,B) float64 -> `sweep_values` of the eleven shared counters (the same formulas: MOTP is
+    iou_sum / tp) plus frag and iou_q pooled per level (0 past `reached`) and per stream."""
+    L = int(levels)
+    c12 = np.asarray(counters, dtype=np.int64).reshape(L + 1, -1, len(OPTIMAL_COUNTERS))
+    iq = np.asarray(iou_q, dtype=np.int64).reshape(L + 1, -1)
+    out = sweep_values(c12[:, :, [OPTIMAL_COUNTERS.index(k) for k in COUNTERS]], iou_sums, thresholds, reached, L)
+    live = np.arange(L + 1) <= int(reached)
+    frag_streams = c12[:, :, OPTIMAL_COUNTERS.index("frag")].copy()
+    out.update(frag=np.where(live, frag_streams.sum(axis=1), 0), iou_q=np.where(live, iq.sum(axis=1), 0), frag_streams=frag_streams,
+               iou_q_streams=iq.copy())
+    if out["best"] is not None:
+        out["best"].update(frag=int(out["frag"][out["best"]["level"]]), iou_q=int(out["iou_q"][out["best"]["level"]]))
+    out["unfiltered"].update(frag=int(out["frag"][0]), iou_q=int(out["iou_q"][0]))
     return out
 
 
@@ -407,10 +460,17 @@ class TrackScorer:
     the table of a `BatchedTracker(max_age=...)` (module docstring).  prev_gt_id (B,Kobj) is then the label id of every row of the
     record and prev_count its row count; two more state tensors sit next to them: row_track (B,Kobj) int32, the track id of every
     row of the record (-1 past prev_count), and labelled_coasted (B) int32, the record's rows past its frame's detections that carry
-    a label id.  `update` takes the table from the StepResult, `update_raw` as table_ids= / table_count=."""
+    a label id.  `update` takes the table from the StepResult, `update_raw` as table_ids= / table_count=.
+
+    sweep_pairs: None (today's object and launches), or Q, which needs sweep_frames / sweep_records: `update` / `update_raw` then
+    also append every (detection, kept object) pair with a common point to the pair log, at most Q per stream (rtk_track_score_pairs,
+    with and without track_memory), for `sweep(matching="optimal")` and `clear_optimal`.  A frame whose pairs do not fit is logged in
+    neither log (FLAG_LOG).  The pair log (device tensors): pair_cursor (B) int32; pair_frame (B,F,2) int32 first pair | pair count;
+    pair_key (B,Q) int32 detection index << 8 | kept-object index; pair_common (B,Q) int32; log_size, log_label_size (B,R) int32, the
+    point counts of the logged detections and kept objects."""
 
     def __init__(self, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, device="cuda", sweep_frames=None, sweep_records=None,
-                 track_memory=False):
+                 track_memory=False, sweep_pairs=None):
         self.B, self.Kobj, self.K, self.T = int(streams), int(max_objects), int(max_boxes), int(max_gt_tracks)
         if self.T < 1:
             raise ValueError("max_gt_tracks=%d must be at least 1" % self.T)
@@ -422,6 +482,13 @@ class TrackScorer:
             if self.F < 1 or self.R < 1 or self.B * max(self.F * 4, self.R) >= 2 ** 31:
                 raise ValueError("TrackScorer: sweep_frames=%d, sweep_records=%d must be at least 1 (and the log below 2^31 entries)"
                                  % (self.F, self.R))
+        self.pairs = sweep_pairs is not None
+        if self.pairs:
+            if not self.logging:
+                raise ValueError("TrackScorer: sweep_pairs=%r needs the log (give sweep_frames and sweep_records)" % (sweep_pairs,))
+            self.Q = int(sweep_pairs)
+            if self.Q < 1 or self.B * self.Q >= 2 ** 31:
+                raise ValueError("TrackScorer: sweep_pairs=%d must be at least 1 (and the pair log below 2^31 entries)" % self.Q)
         self.track_memory = bool(track_memory)
         check_fit(self.K, 1, self.Kobj, self.track_memory)
         B, z = self.B, lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
@@ -439,10 +506,18 @@ class TrackScorer:
             self.log_label, self.log_track, self.log_best = z(B, self.R), z(B, self.R), z(B, self.R)
             self.log_conf = torch.zeros(B, self.R, dtype=torch.float32, device=device)
             self.log_iou = torch.zeros(B, self.R, dtype=torch.float64, device=device)
+        if self.pairs:
+            self.pair_cursor, self.pair_frame = z(B), z(B, self.F, 2)
+            self.pair_key, self.pair_common = z(B, self.Q), z(B, self.Q)
+            self.log_size, self.log_label_size = z(B, self.R), z(B, self.R)
 
     def _log_block(self, object_conf=None):
         return ScoreLog(self.F, self.R, object_conf, self.log_cursor.data_ptr(), self.log_frame.data_ptr(), self.log_label.data_ptr(),
                         self.log_track.data_ptr(), self.log_best.data_ptr(), self.log_conf.data_ptr(), self.log_iou.data_ptr())
+
+    def _pair_block(self):
+        return ScorePairs(self.Q, self.pair_cursor.data_ptr(), self.pair_frame.data_ptr(), self.pair_key.data_ptr(), self.pair_common.data_ptr(),
+                          self.log_size.data_ptr(), self.log_label_size.data_ptr())
 
     def update(self, out, gobj, reset=None, active=None):
         """out: a `tracker.StepResult`; gobj: the GtObjects of the same frame (its n_valid is used).  active None: the mask the step
@@ -503,9 +578,15 @@ class TrackScorer:
                        self.prev_count.data_ptr(), self.prev_gt.data_ptr(), self.flags.data_ptr())
         o = ScoreOut(pred_gt_slot.data_ptr(), pred_gt_id.data_ptr(), gt_pred.data_ptr(), iou.data_ptr(), aff_target.data_ptr(),
                      aff_defined.data_ptr())
+        mm = None
         if self.track_memory:
             table_ids, table_count = as32(table_ids), as32(table_count)
             mm = ScoreMemory(table_ids.data_ptr(), table_count.data_ptr(), self.row_track.data_ptr(), self.labelled_coasted.data_ptr())
+        if self.pairs:
+            lg, pr = self._log_block(object_conf.data_ptr()), self._pair_block()
+            _lib.call("rtk_track_score_pairs", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), ctypes.addressof(lg),
+                      None if mm is None else ctypes.addressof(mm), ctypes.addressof(pr), _stream())
+        elif self.track_memory:
             lg = self._log_block(object_conf.data_ptr()) if self.logging else None
             _lib.call("rtk_track_score_memory", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o),
                       None if lg is None else ctypes.addressof(lg), ctypes.addressof(mm), _stream())
@@ -530,7 +611,8 @@ class TrackScorer:
                 raise RuntimeError("TrackScorer: stream %d has a table_count outside [num_objects, max_objects=%d]" % (b, self.Kobj))
             if f & FLAG_LOG:
                 raise RuntimeError("TrackScorer: stream %d has a frame that did not fit its log of sweep_frames=%d frames and "
-                                   "sweep_records=%d records and was not logged (raise them)" % (b, self.F, self.R))
+                                   "sweep_records=%d records%s and was not logged (raise them)"
+                                   % (b, self.F, self.R, " or its pair log of sweep_pairs=%d pairs" % self.Q if self.pairs else ""))
             if f & FLAG_SWEEP:
                 raise RuntimeError("TrackScorer.sweep: stream %d has more than %d track ids in one clip" % (b, SWEEP_TRACKS))
             if f & FLAG_HOTA:
@@ -539,6 +621,9 @@ class TrackScorer:
             if f & FLAG_IDENTITY:
                 raise RuntimeError("TrackScorer.identity: stream %d has a clip with more than max_gt_tracks=%d label ids, %d track ids or "
                                    "%d (label id, track id) pairs" % (b, self.T, SWEEP_TRACKS, IDENTITY_PAIRS))
+            if f & FLAG_OPTIMAL:
+                raise RuntimeError("TrackScorer: stream %d has a frame with more than %d candidate (detection, object) pairs for the optimal "
+                                   "matching" % (b, PAIR_EDGES))
 
     def check(self):
         """Synchronises.  Raises RuntimeError naming the stream whose track table overflowed or whose sizes were out of range."""
@@ -576,16 +661,40 @@ class TrackScorer:
         overall.update({k: float(v) for k, v in values_from_counters(total, total_iou).items()})
         return dict(per_stream=per, overall=overall, flags=flags.copy())
 
-    def sweep(self, levels=40, check=True):
+    def _optimal_args(self, what, min_iou):
+        """The checks `sweep(matching="optimal")` and `clear_optimal` share -> min_iou as a float."""
+        if not self.pairs:
+            raise RuntimeError("TrackScorer.%s: the optimal matching needs the pair log (give sweep_pairs)" % what)
+        if min_iou is None:
+            raise ValueError("TrackScorer.%s: the optimal matching needs an explicit min_iou in (0, 1]: the threshold of the reference's "
+                             "evaluation is not known, so there is no default" % what)
+        m = float(min_iou)
+        if not (np.isfinite(m) and 0.0 < m <= 1.0):
+            raise ValueError("TrackScorer.%s: min_iou=%r outside (0, 1]" % (what, min_iou))
+        need = _lib._fn("rtk_score_optimal_lds_bytes")(self.T)
+        if need < 0 or need > LDS_LIMIT:
+            raise ValueError("TrackScorer.%s: max_gt_tracks=%d needs %d bytes of LDS per stream for the optimal matching, the limit is %d"
+                             % (what, self.T, need, LDS_LIMIT))
+        return m
+
+    def sweep(self, levels=40, check=True, matching="greedy", min_iou=None):
         """sAMOTA / AMOTA / AMOTP over the log (module docstring): track scores, the unfiltered replay, a sort of the true
         positives' scores, the threshold walk and the replay at every threshold on the device -- five launches of this library plus
         torch's sort -- then one download.  The running state and the log are only read: scoring may go on.  check: raise (naming the
-        stream) on any sticky flag, a frame that did not fit the log among them.  -> SweepResult."""
+        stream) on any sticky flag, a frame that did not fit the log among them.  matching "greedy": `update`'s rule, today's call.
+        "optimal": both replays match every frame by an exact assignment over the logged pairs with IoU >= min_iou (module docstring);
+        it needs the pair log (sweep_pairs) and an explicit min_iou in (0, 1] -- there is no default.  -> SweepResult."""
+        if matching not in ("greedy", "optimal"):
+            raise ValueError("TrackScorer.sweep: matching=%r is neither \"greedy\" nor \"optimal\"" % (matching,))
         if not self.logging:
             raise RuntimeError("TrackScorer.sweep: the scorer keeps no log (give sweep_frames and sweep_records)")
         L = int(levels)
         if not 1 <= L <= 65534:
             raise ValueError("levels=%d outside [1, 65534]" % L)
+        if matching == "optimal":
+            return self._sweep_optimal(L, check, self._optimal_args("sweep", min_iou))
+        if min_iou is not None:
+            raise ValueError("TrackScorer.sweep: min_iou=%r goes with matching=\"optimal\"; the greedy rule has no threshold" % (min_iou,))
         B, dev, nc = self.B, self.counters.device, len(COUNTERS)
         lg = self._log_block()
         lgp, st = ctypes.addressof(lg), _stream()
@@ -616,7 +725,83 @@ class TrackScorer:
         k, fl = int(host[o + L + 1]), host[o + L + 2:].copy()
         if check:
             self._raise_on_flags(fl.tolist())
-        return SweepResult(flags=fl, **sweep_values(counters, iou_sums, thresholds, k, L))
+        return SweepResult(flags=fl, matching="greedy", min_iou=None, frag=None, iou_q=None, frag_streams=None, iou_q_streams=None,
+                           **sweep_values(counters, iou_sums, thresholds, k, L))
+
+    def _replay_optimal(self, lgp, prp, score, thr, reached, count, min_iou, mask, flags, st):
+        B, dev = self.B, self.counters.device
+        c = torch.empty(count, B, len(OPTIMAL_COUNTERS), dtype=torch.int64, device=dev)
+        iq = torch.empty(count, B, dtype=torch.int64, device=dev)
+        q = torch.empty(count, B, dtype=torch.float64, device=dev)
+        _lib.call("rtk_score_replay_optimal", B, self.T, lgp, prp, score.data_ptr(), thr.data_ptr(), None if reached is None else reached.data_ptr(),
+                  count, min_iou, c.data_ptr(), iq.data_ptr(), q.data_ptr(), None if mask is None else mask.data_ptr(), flags.data_ptr(), st)
+        return c, iq, q
+
+    def _sweep_optimal(self, L, check, min_iou):
+        """`sweep` under the optimal matching: track means, the unfiltered optimal replay with the mask, the sort, the existing
+        threshold walk and the optimal replay at the thresholds; one download."""
+        B, dev, nc = self.B, self.counters.device, len(OPTIMAL_COUNTERS)
+        lg, pr = self._log_block(), self._pair_block()
+        lgp, prp, st = ctypes.addressof(lg), ctypes.addressof(pr), _stream()
+        score = torch.zeros(B, self.R, dtype=torch.float64, device=dev)
+        flags = self.flags.clone()
+        _lib.call("rtk_score_track_means", B, lgp, score.data_ptr(), flags.data_ptr(), st)
+        mask = torch.zeros(B, self.R, dtype=torch.uint8, device=dev)
+        minus = torch.full((1,), float("-inf"), dtype=torch.float64, device=dev)
+        c0, _, _ = self._replay_optimal(lgp, prp, score, minus, None, 1, min_iou, mask, flags, st)
+        ordered = torch.where(mask.bool(), score, minus).reshape(-1).sort(descending=True).values
+        n, gt = mask.sum(dtype=torch.int64).reshape(1), c0[0, :, OPTIMAL_COUNTERS.index("gt")].sum().reshape(1)
+        thr = torch.empty(L + 1, dtype=torch.float64, device=dev)
+        reached = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.call("rtk_score_thresholds", ordered.data_ptr(), n.data_ptr(), gt.data_ptr(), L, thr.data_ptr(), reached.data_ptr(), st)
+        c, iq, q = self._replay_optimal(lgp, prp, score, thr, reached, L + 1, min_iou, None, flags, st)
+        host = torch.cat([c.reshape(-1), iq.reshape(-1), q.reshape(-1).view(torch.int64), thr.view(torch.int64), reached.long(),
+                          flags.long()]).cpu().numpy()
+        o = (L + 1) * B * nc
+        c12 = host[:o].reshape(L + 1, B, nc).copy()
+        iou_q = host[o:o + (L + 1) * B].reshape(L + 1, B).copy()
+        o += (L + 1) * B
+        iou_sums = host[o:o + (L + 1) * B].copy().view(np.float64).reshape(L + 1, B)
+        o += (L + 1) * B
+        thresholds = host[o:o + L + 1].copy().view(np.float64)
+        k, fl = int(host[o + L + 1]), host[o + L + 2:].copy()
+        if check:
+            self._raise_on_flags(fl.tolist())
+        return SweepResult(flags=fl, matching="optimal", min_iou=min_iou, **optimal_sweep_values(c12, iou_q, iou_sums, thresholds, k, L))
+
+    def clear_optimal(self, min_iou, threshold=None, check=True):
+        """The one operating point under the optimal matching (module docstring): every logged detection (threshold None, one launch)
+        or those whose track score is not below `threshold` (a float or a 0-dim tensor, two launches), matched frame by frame by an
+        exact assignment over the logged pairs with IoU >= min_iou (explicit, in (0, 1]).  Then one download; the running state and
+        the logs are only read.  -> dict: `per_stream` {name: (B) array} and `overall` {name: number} with the OPTIMAL_COUNTERS,
+        iou_q, iou_sum and the ratios mota, moda, recall, precision, motp (iou_sum / tp), mt_fraction, pt_fraction, ml_fraction (NaN
+        without a denominator); `flags` (B); `min_iou`, `threshold`."""
+        m = self._optimal_args("clear_optimal", min_iou)
+        B, dev, nc = self.B, self.counters.device, len(OPTIMAL_COUNTERS)
+        lg, pr = self._log_block(), self._pair_block()
+        lgp, prp, st = ctypes.addressof(lg), ctypes.addressof(pr), _stream()
+        score = torch.zeros(B, self.R, dtype=torch.float64, device=dev)
+        flags = self.flags.clone()
+        thr = torch.full((1,), float("-inf"), dtype=torch.float64, device=dev)
+        if threshold is not None:
+            thr = torch.as_tensor(threshold, dtype=torch.float64).reshape(1).to(dev)
+            _lib.call("rtk_score_track_means", B, lgp, score.data_ptr(), flags.data_ptr(), st)
+        c, iq, q = self._replay_optimal(lgp, prp, score, thr, None, 1, m, None, flags, st)
+        host = torch.cat([c.reshape(-1), iq.reshape(-1), q.reshape(-1).view(torch.int64), thr.view(torch.int64), flags.long()]).cpu().numpy()
+        counters = host[:B * nc].reshape(B, nc).copy()
+        iou_q = host[B * nc:B * nc + B].copy()
+        iou_sum = host[B * nc + B:B * nc + 2 * B].copy().view(np.float64)
+        tau = float(host[B * nc + 2 * B:B * nc + 2 * B + 1].copy().view(np.float64)[0])
+        fl = host[B * nc + 2 * B + 1:].copy()
+        if check:
+            self._raise_on_flags(fl.tolist())
+        per = {k: counters[:, i] for i, k in enumerate(OPTIMAL_COUNTERS)}
+        per.update(iou_q=iou_q, iou_sum=iou_sum, **optimal_values(counters, iou_sum))
+        total = counters.sum(0)
+        total_iou = float(np.cumsum(iou_sum)[-1]) if B else 0.0          # cumsum: one addition after the other, in stream order
+        overall = {k: int(total[i]) for i, k in enumerate(OPTIMAL_COUNTERS)}
+        overall.update(iou_q=int(iou_q.sum()), iou_sum=total_iou, **{k: float(v) for k, v in optimal_values(total, total_iou).items()})
+        return dict(per_stream=per, overall=overall, flags=fl, min_iou=m, threshold=None if threshold is None else tau)
 
     def hota(self, alphas=19, threshold=None, check=True):
         """HOTA, DetA, AssA and LocA over the log (module docstring; definitions in include/rtk_score.h) at `alphas` levels
