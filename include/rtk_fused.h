@@ -441,6 +441,37 @@ RTK_EXPORT int rtk_associate_batched(int B, int N, int K, const unsigned char *a
                                      int iters, int *counter, int *ids, int *count, int *object_ids, float *object_conf, int *indices1,
                                      int *num_prev, int *point_track_id, float *scores, rtk_stream_t stream);
 
+/* rtk_associate_optimal: rtk_associate_batched with the decision replaced by an EXACT maximum-weight one-to-one assignment
+ * (csrc/track_assign.hip, csrc/lds_assignment.h: la_solve_dense) -- issued INSTEAD of it, never with it; no Sinkhorn runs.  The live
+ * sizes are rtk_associate_batched's: m_b = prev_count[b] clamped to [0, K], 0 on a reset stream; n_b = num_objects[b] clamped to [0, K].
+ *   admissible  pair (i, j), i < m_b, j < n_b, is admissible iff (double)aff[b][i][j] >= min_affinity.  A NaN is not admissible.
+ *               min_affinity lies in [0.01, 1]; outside that range, or a NaN, the call is refused.  0.01 is the reference's confidence
+ *               threshold: as in rtk_associate_batched float32(0.01) itself is below the double 0.01 and is not admissible.
+ *   weight      an admissible pair weighs (int)(aff * 268435456.0f) (2^28, truncated; the product is exact in fp32, so the weight is a
+ *               function of the aff word alone): between 2 684 354 and 2^28 for an aff in [0.01, 1].  An aff above 1 (no sigmoid gives
+ *               one) weighs as 1.  An inadmissible pair weighs 0 and is no edge.
+ *   decision    previous rows are the rows and current objects the columns of one assignment problem per stream.  The matching
+ *               takes every row and every column at most once, uses admissible pairs only, and has the largest total weight any such
+ *               matching can have; that total is unique.  Where several matchings reach it the choice is a deterministic function of
+ *               the weight block (rows enter in index order, ties go to the smaller column index); nothing more is promised about it.
+ *   outputs     exactly rtk_associate_batched's.  Object j matched to row i: indices1 = i, object_ids = prev_ids[i], object_conf =
+ *               the aff word of the pair (at least the gate, hence != 0: the "matched" rule of rtk_track_memory holds as written).
+ *               An unmatched object: indices1 = -1, object_conf = 0, a fresh ID from counter[b] in current-object order.  Rows past
+ *               n_b: -1 / 0 / -1.  num_prev = m_b, count = n_b, ids[j] = object_ids[j] for j < n_b (rows past n_b are not written),
+ *               counter in place, point_track_id (B,N) = the ID of the point's object (obj in [0, n_b)) or -1.  With m_b = 0 or
+ *               n_b = 0 no solve runs and every object is fresh.  Inactive streams: ids = prev_ids (all K rows), count = m_b before
+ *               the reset rule (prev_count clamped), num_prev = 0, no objects, point_track_id = -1, counter untouched.
+ *   total       NULL, or (B) long long: the matching's weight; 0 where no solve ran; untouched for an inactive stream.
+ * aff is read inside the live (m_b, n_b) block only.  Plain stores only: two runs give the same bits.  One one-wave workgroup per
+ * stream; its LDS holds the K x K weight block, the solver's tables (K + 5 K words) and the K new IDs: rtk_associate_optimal_lds_bytes(K),
+ * 160 752 bytes at K = 197 = rtk_track_max_objects(). */
+RTK_EXPORT int rtk_associate_optimal(int B, int N, int K, const unsigned char *active, const unsigned char *reset, const float *aff,
+                                     const int *num_objects, const int *obj, const int *prev_ids, const int *prev_count,
+                                     double min_affinity, int *counter, int *ids, int *count, int *object_ids, float *object_conf,
+                                     int *indices1, int *num_prev, int *point_track_id, long long *total, rtk_stream_t stream);
+/* The dynamic LDS of one workgroup of rtk_associate_optimal at K object slots, in bytes (a host function); -1 for a K below 1. */
+RTK_EXPORT int rtk_associate_optimal_lds_bytes(int K);
+
 /* rtk_track_memory: track memory (a lost track coasts for up to max_age frames) -- the state advance of a tracker that keeps lost
  * tracks, issued after rtk_associate_batched on the same stream.  The table of a stream (ids, desc, age, hits, its row count `count`,
  * and n_det = how many of its leading rows are the last active frame's detections; the rows after them are coasted tracks) is

@@ -207,6 +207,8 @@ SIGNATURES = {
     "rtk_object_descriptors": [_p, _i, _p, _p, _p, _p, _p, _p],
     "rtk_affinity_pairs": [_i, _i] + [_p] * 7 + [_p],
     "rtk_associate_batched": [_i] * 3 + [_p] * 7 + [_f, _i] + [_p] * 9 + [_p],
+    "rtk_associate_optimal": [_i] * 3 + [_p] * 7 + [_d] + [_p] * 9 + [_p],
+    "rtk_associate_optimal_lds_bytes": [_i],
     "rtk_track_memory": [_i] * 3 + [_p] * 21 + [_p],
     "rtk_track_memory_motion": [_i] * 3 + [_f] + [_p] * 24 + [_p],
     "rtk_track_max_objects": [],

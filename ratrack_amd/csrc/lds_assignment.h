@@ -164,3 +164,102 @@ __device__ inline long long la_solve(int R, int C, int E, const int *ekey, const
     }
     return la_wave_sum(sum);
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// la_solve_dense -- the same problem on a DENSE block of weights (track_assign.hip: the batched tracker's exact association).  An
+// R x C block as an edge list costs la_solve 4 E ints of LDS, 256 KiB at 128 x 128; here the block itself is the adjacency:
+// w[i * ld + j] is the weight of pair (row i, column j), 0 = no edge.
+//
+// The method is la_solve's, statement for statement: successive shortest augmenting paths with potentials on cost = -weight, every
+// row owning a private "stays unmatched" column of cost 0; rows enter in index order; the nearest column wins, ties go to the smaller
+// column index, and a private column that is no farther than the nearest column ends the search.  So the matching is the one la_solve
+// leaves for the edge set {(i, j, w[i * ld + j]) : w > 0}, and it depends on nothing but the block.
+// What differs is who holds what.  Lane t owns the columns j = t, t + 64, ...: their dist, way and done words are read and written by
+// that lane alone, and one pass over a lane's columns both relaxes them from the row just reached and finds the lane's nearest, so a
+// search round is one pass (ceil(C / 64) reads of w, v, dist, done per lane), one wave reduction and two broadcast reads (cp of the
+// chosen column, u of its row) -- and no barrier: during a search u, v, cp and w are only read.  The three barriers per row stand
+// between the search, the move of the potentials (which reads cp), the flip of the path (which writes cp) and the next row.
+// Exact and bounded as la_solve is: integers only, potentials in [-W, 0], distances in [0, 2 W]; a search makes at most C + 1 rounds
+// (counted), there are R searches, a flip makes at most C steps (counted).
+//
+// The contract.
+//   * called by all 64 lanes of a one-wave workgroup (blockDim.x == RTK_WAVE) with identical arguments, from uniform control flow;
+//     it synchronises with __syncthreads() and every lane returns the same value: the weight of the matching;
+//   * w: in LDS, only read; rows i < R, columns j < C, row stride ld >= C; every word is 0 or in (0, 2^29); R >= 0, C >= 0;
+//   * work: la_dense_words(R, C) ints of LDS that do not overlap w; what they held is lost.  After the call cp (work +
+//     la_dense_cp_offset(R, C)) holds the row matched to every column, -1 for none;
+//   * no floating point, no scratch, no inline assembly, no global memory.
+// ------------------------------------------------------------------------------------------------------------------------------------
+// u [R] | v, dist, way, cp, done [C] each
+__host__ __device__ constexpr int la_dense_words(int R, int C) { return R + 5 * C; }
+__host__ __device__ constexpr int la_dense_cp_offset(int R, int C) { return R + 3 * C; }
+
+__device__ inline long long la_solve_dense(int R, int C, const int *w, int ld, int *work) {
+    const int t = threadIdx.x;
+    int *u = work, *v = u + R, *dist = v + C, *way = dist + C, *cp = way + C, *done = cp + C;
+    for (int j = t; j < C; j += RTK_WAVE) { v[j] = 0; cp[j] = -1; }
+    __syncthreads();
+    for (int r = 0; r < R; ++r) {
+        // u[r] = min(0, min over the row's edges of cost - v) = -(the largest weight + v, at least 0); the lane's columns start a search
+        const int *wr = w + (size_t)r * ld;
+        int most = 0;
+        for (int j = t; j < C; j += RTK_WAVE) {
+            const int wj = wr[j];
+            if (wj > 0) most = max(most, wj + v[j]);
+            dist[j] = LA_INF; done[j] = 0;
+        }
+        const int ur = (int)la_wave_min((unsigned long long)(LA_INF - most)) - LA_INF;
+        int i = r, ui = ur, base = 0, jin = -1;      // the row just reached, its potential and distance, the column it was reached through
+        int dd = LA_INF, jdd = -1;                   // the nearest private column of a row of the tree, and the column THAT row was reached through
+        int D = 0, jend = -1;                        // the search's result: the final distance and the column the flip starts at (-1: nothing flips)
+        for (int round = 0; round <= C; ++round) {
+            if (base - ui < dd) { dd = base - ui; jdd = jin; }      // row i could end the path by staying unmatched
+            const int *wi = w + (size_t)i * ld;
+            unsigned long long near = ((unsigned long long)LA_INF << 32) | 0xffffffffu;
+            for (int j = t; j < C; j += RTK_WAVE) {
+                if (done[j]) continue;
+                int d = dist[j];
+                const int wj = wi[j];
+                if (wj > 0) {
+                    const int nd = base + (-wj - ui - v[j]);
+                    if (nd < d) { d = nd; dist[j] = nd; way[j] = jin; }
+                }
+                if (d != LA_INF) near = min(near, ((unsigned long long)(unsigned)d << 32) | (unsigned)j);
+            }
+            near = la_wave_min(near);
+            const int d = (int)(near >> 32), j = (int)(unsigned)near;
+            if (d == LA_INF || dd <= d) { D = dd; jend = jdd; break; }      // nothing left to reach, or a private column is no farther
+            const int owner = cp[j];
+            if ((j & (RTK_WAVE - 1)) == t) done[j] = 1;                     // the column's own lane: no other reads the word
+            if (owner < 0) { D = d; jend = j; break; }
+            i = owner; ui = u[owner]; base = d; jin = j;
+        }
+        __syncthreads();
+        // ---- the tree's potentials move by what the search still had to go from each of them ----
+        for (int j = t; j < C; j += RTK_WAVE) {
+            if (!done[j]) continue;
+            const int gap = D - dist[j], owner = cp[j];
+            v[j] -= gap;
+            if (owner >= 0) u[owner] += gap;      // one row per column: no two lanes meet
+        }
+        if (t == 0) u[r] = ur + D;                // r owns no column yet: no lane above wrote it
+        __syncthreads();
+        // ---- and the path is flipped, from its free end back to r (ending at a private column: from the column its row gives up) ----
+        if (t == 0) {
+            int j = jend;
+            for (int step = 0; step < C && j >= 0; ++step) {
+                const int jp = way[j];
+                cp[j] = jp < 0 ? r : cp[jp];
+                j = jp;
+            }
+        }
+        __syncthreads();
+    }
+    // ---- the weight of the matching, column by column ----
+    long long sum = 0;
+    for (int j = t; j < C; j += RTK_WAVE) {
+        const int i = cp[j];
+        if (i >= 0) sum += w[(size_t)i * ld + j];
+    }
+    return la_wave_sum(sum);
+}

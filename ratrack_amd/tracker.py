@@ -122,7 +122,10 @@ class StepResult:
     With `BatchedTracker(motion="flow")` (else None): object_velocity (B,K,3): the velocity of object j's track after this frame's
     measurement, metres per frame in the sensor frame (0 past num_objects and on an inactive stream); table_velocity (B,K,3): the
     velocity of every row of the table this step wrote, aligned with `table_ids` (0 past `table_count`) -- a view of the tracker's
-    own buffer, overwritten when `table_ids` is."""
+    own buffer, overwritten when `table_ids` is.
+    With `BatchedTracker(assign="optimal")` (else None): assign_total (B,) int64: the weight of the stream's matching, the sum of
+    (int)(aff * 2^28) over its matched pairs; 0 where nothing was associated (no previous or no current objects); an inactive stream
+    keeps the value of its last active frame (0 before the first) -- the tracker's own buffer, overwritten by the next step."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -215,11 +218,24 @@ def check_motion(motion, motion_beta, memory, memory_name):
         raise ValueError("motion_beta=%r without motion: there is no velocity to smooth (give motion=\"flow\")" % (motion_beta,))
 
 
+def check_assign(assign, min_affinity):
+    """The `assign` / `min_affinity` keywords of a tracker: raises ValueError on a value or a combination that means nothing."""
+    if assign not in ("sinkhorn", "optimal"):
+        raise ValueError("assign=%r: \"sinkhorn\" (the reference's decision: log-Sinkhorn, then the mutual best match) or \"optimal\" "
+                         "(an exact maximum-weight one-to-one assignment of the affinities at or above min_affinity)" % (assign,))
+    ok = isinstance(min_affinity, (int, float)) and not isinstance(min_affinity, bool) and 0.01 <= float(min_affinity) <= 1.0
+    if not ok:
+        raise ValueError("min_affinity=%r: a number in [0.01, 1] (0.01 is the reference's confidence threshold)" % (min_affinity,))
+    if assign == "sinkhorn" and float(min_affinity) != 0.01:
+        raise ValueError("min_affinity=%r without assign=\"optimal\": the reference's decision has the one threshold 0.01" % (min_affinity,))
+
+
 class BatchedTracker:
     """Tracks `streams` independent sequences in lockstep (see the module docstring)."""
 
     def __init__(self, net, streams, max_objects=128, iters=500, alpha=0.9, eps=1.5, threshold=0.5, train_mode=False,
-                 static_state=False, graph=False, graph_warmup=2, engine=None, max_age=None, motion=None, motion_beta=1.0):
+                 static_state=False, graph=False, graph_warmup=2, engine=None, max_age=None, motion=None, motion_beta=1.0,
+                 assign="sinkhorn", min_affinity=0.01):
         """train_mode: accept a train-mode net -- for a caller that runs the backbone itself and uses `associate` and the state only
         (track_train.SequenceTrainer); `step()` stays the eval-mode path.
         static_state: this frame's objects are always written to slot 0 of `desc` / `ids` / `count` and the previous objects read
@@ -244,10 +260,21 @@ class BatchedTracker:
         (module docstring; rules in include/rtk_fused.h, rtk_track_memory_motion, which replaces rtk_track_memory).
         motion_beta in (0, 1]: the weight of this frame's measured flow in an inherited track's velocity, v + beta (flow - v); a
         fresh track starts at its flow.  The default 1.0 makes the velocity the last measured mean flow: tracking quality has not
-        been measured on real sequences here, so no smoothing default can be justified.  A launch constant, like max_age."""
+        been measured on real sequences here, so no smoothing default can be justified.  A launch constant, like max_age.
+        assign: "sinkhorn" (default): the reference's decision -- `iters` log-Sinkhorn iterations with dustbin `alpha`, then the
+        mutual best match (rtk_associate_batched): the tracker as it is without the keyword, the same buffers and launches;
+        `StepResult.assign_total` is None.  "optimal": rtk_associate_optimal in its place (csrc/track_assign.hip; rules in
+        include/rtk_fused.h) -- previous rows and current objects are matched one to one so that the affinities of the matched pairs,
+        each quantised to (int)(aff * 2^28), have the largest sum any one-to-one matching of the pairs with aff >= min_affinity can
+        have; `iters` and `alpha` are ignored.  The same number of launches, the same outputs: graph, static_state, max_age, motion,
+        TrackerPipeline and write_results work unchanged.  `StepResult.assign_total` (B,) int64 is that sum per stream.
+        min_affinity in [0.01, 1] (needs assign="optimal"): the gate below which a pair is never matched; the default 0.01 is the
+        reference's confidence threshold.  Both are launch constants, like max_age."""
         if max_age is not None and (isinstance(max_age, bool) or not isinstance(max_age, int) or max_age < 0):
             raise ValueError("max_age=%r: None (no track memory) or an integer >= 0 (frames a lost track is kept)" % (max_age,))
         check_motion(motion, motion_beta, max_age, "max_age")
+        check_assign(assign, min_affinity)
+        self.assign, self.min_affinity = assign, float(min_affinity)
         if net.training and not train_mode:
             raise ValueError("BatchedTracker runs the eval-mode (fused) backbone: call net.eval() first")
         kmax = max_objects_limit()
@@ -277,6 +304,8 @@ class BatchedTracker:
         self.vel = None
         if motion is not None:         # every row's velocity, metres per frame
             self.vel = torch.zeros(2, B, K, 3, device=dev)
+        # the weight of every stream's matching (assign="optimal"): the kernel leaves an inactive stream's word as it is
+        self.assign_total = torch.zeros(B, dtype=torch.int64, device=dev) if assign == "optimal" else None
         self.cur = 0
         self._work = None
         self.last = None
@@ -387,10 +416,17 @@ class BatchedTracker:
         _lib.call("rtk_affinity_pairs", B, K, self.weights.data_ptr(), desc_prev.data_ptr(), self.count[prev].data_ptr(), reset.data_ptr(),
                   desc.data_ptr(), num.data_ptr(), aff.data_ptr(), st)
         object_ids, object_conf, indices1, num_prev, point_track_id = i32(B, K), torch.empty(B, K, device=dev), i32(B, K), i32(B), i32(B, N)
-        _lib.call("rtk_associate_batched", B, N, K, active.data_ptr(), reset.data_ptr(), aff.data_ptr(), num.data_ptr(), obj.data_ptr(),
-                  self.ids[prev].data_ptr(), self.count[prev].data_ptr(), self.alpha, self.iters, self.counter.data_ptr(),
-                  self.ids[cur].data_ptr(), self.count[cur].data_ptr(), object_ids.data_ptr(), object_conf.data_ptr(), indices1.data_ptr(),
-                  num_prev.data_ptr(), point_track_id.data_ptr(), None, st)
+        assign_total = self.assign_total
+        if self.assign == "optimal":
+            _lib.call("rtk_associate_optimal", B, N, K, active.data_ptr(), reset.data_ptr(), aff.data_ptr(), num.data_ptr(), obj.data_ptr(),
+                      self.ids[prev].data_ptr(), self.count[prev].data_ptr(), self.min_affinity, self.counter.data_ptr(),
+                      self.ids[cur].data_ptr(), self.count[cur].data_ptr(), object_ids.data_ptr(), object_conf.data_ptr(),
+                      indices1.data_ptr(), num_prev.data_ptr(), point_track_id.data_ptr(), assign_total.data_ptr(), st)
+        else:
+            _lib.call("rtk_associate_batched", B, N, K, active.data_ptr(), reset.data_ptr(), aff.data_ptr(), num.data_ptr(), obj.data_ptr(),
+                      self.ids[prev].data_ptr(), self.count[prev].data_ptr(), self.alpha, self.iters, self.counter.data_ptr(),
+                      self.ids[cur].data_ptr(), self.count[cur].data_ptr(), object_ids.data_ptr(), object_conf.data_ptr(), indices1.data_ptr(),
+                      num_prev.data_ptr(), point_track_id.data_ptr(), None, st)
         memory = dict(object_hits=None, object_gap=None, num_coasted=None, prev_age=None, table_ids=None, table_count=None,
                       object_velocity=None, table_velocity=None)
         if self.motion is not None:
@@ -420,7 +456,7 @@ class BatchedTracker:
         out = StepResult(flow=flow, cls=cls, h=self.h, point_track_id=point_track_id, num_objects=num, object_ids=object_ids,
                          object_conf=object_conf, _indices1=indices1, aff=aff, num_prev=num_prev, flags=flags, labels=labels, obj=obj,
                          descriptors=desc, desc_prev=desc_prev, active=active, pc1=pc1, feature1=feature1, prop=prop, max_objects=K, _cache=None,
-                         **memory)
+                         assign_total=assign_total, **memory)
         self.last = out
         return out
 
