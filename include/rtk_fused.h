@@ -218,7 +218,8 @@ RTK_EXPORT int rtk_cost_volume_split_term(int samples, int n1, int n2, const flo
                                           const float *bias2, const float *bias3, const rtk_layer_t *wn, float *out, int out_pitch,
                                           int workgroups, rtk_stream_t stream);
 /* rtk_sa_scale for the scales whose MLP is offset layer (c1 = 32 or 64 channels) + ONE layer c1 -> 64, nsample 16 or 32 (sa2 scale 1,
- * sa3 scales 0 and 1 of the PNHead): same arguments, the layer as its split image + inverse scale (rtk_pack_split_layer(64, c1, ...)) + fp32 bias. */
+ * sa3 scales 0 and 1 of the PNHead): same arguments, the layer as its split image + inverse scale (rtk_pack_split_layer(64, c1, ...)) + fp32 bias.
+ * (A sample whose q rows span 2^32 bytes or more, n * q_pitch * 4, is computed by the serial loop: same bits.) */
 RTK_EXPORT int rtk_sa_scale_split(int samples, int n, int npoint, int nsample, const float *xyz, const float *new_xyz,
                                   const int *idx, const float *q, int q_pitch, int c1, const float *w1xyz_packed,
                                   const void *split_image, const float *image_scale, const float *bias2, float *out, int out_pitch,

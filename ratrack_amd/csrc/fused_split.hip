@@ -766,8 +766,9 @@ struct SaSplitParams {
 };
 
 // Register budget: four waves per SIMD (<= 128 registers), which is what the launcher's grid gives anyway (SA_WGS_TARGET workgroups of
-// four waves on 1024 SIMDs).  The pipelined loop holds the next unit's q rows (32 registers at C1 = 64) and coordinates next to the
-// tile in work: 122 / 127 / 116 registers, no scratch.  (Five waves, <= 96 registers, held the serial loop -- 94 / 94 / 76 -- and was
+// four waves on 1024 SIMDs).  The pipelined loop held the next unit's q rows (32 registers at C1 = 64) and coordinates next to the
+// tile in work: 122 / 127 / 116 registers, no scratch; with the rows staged in LDS (SaRows) one 32-channel block of them is in registers
+// under the epilogue only: 106 / 108 / 98.  (Five waves, <= 96 registers, held the serial loop -- 94 / 94 / 76 -- and was
 // chosen when an SA wave fitted on a SIMD next to a 404-register forward cost volume; that kernel now allocates CV_FWD_VGPRS and shares
 // its SIMDs with nothing.  Under that cap the pipelined loop spills 45 / 71 / 10 registers.  The first capped build computed wrong
 // maxima: see the epilogue.)
@@ -779,10 +780,16 @@ struct SaSplitParams {
 #endif
 // The k-step of layer 2 behind which the pipelined loop requests the next unit's rows at C1 = 64 (four k-steps; at C1 = 32 they go
 // out in front of layer 2).  Behind step 1 a quarter of the tile's activations is dead and the rows fit: in front of layer 2 the
-// 64-channel shapes spill 2 / 11 registers.  <16, 64> also needs its epilogue fenced off from layer 2 (else the scheduler hoists the
-// eight bias reads and the first block's maximum over the last MFMAs: 6 - 11 registers spilled); SA_EPI_FENCE_ALL fences every shape.
+// 64-channel shapes spilled 2 / 11 registers when the rows went into registers.  (Through LDS step 0 fits as well and measures the
+// same.)  <16, 64> also needs its epilogue fenced off from layer 2 (else the scheduler hoists the eight bias reads and the first
+// block's maximum over the last MFMAs: 6 - 11 registers spilled); SA_EPI_FENCE_ALL fences every shape.
 #ifndef SA_GATHER_STEP
 #define SA_GATHER_STEP 1
+#endif
+// C1 = 64, rows through LDS: the k-step behind which round 0 of the next unit's rows is read and round 1 requested (3: the last MFMA;
+// 2, with SA_GATHER_STEP 0 or 1, measures the same: tools/experiments/sa_ablate.py, profiles/sa_rows_lds_schedules.txt).
+#ifndef SA_ROWS_READ_STEP
+#define SA_ROWS_READ_STEP 3
 #endif
 #ifndef SA_EPI_FENCE_ALL
 #define SA_EPI_FENCE_ALL 0
@@ -796,6 +803,73 @@ struct SaSplitParams {
 #define SA_INDEX_AHEAD 1
 #endif
 constexpr int sa_split_index_ahead(int ns, int c1) { return SA_INDEX_AHEAD == 2 ? 2 : 1; }
+
+// ---- the q rows of the pipelined loop through LDS -----------------------------------------------------------------------------------
+// The tile layout gives a lane 32 bytes of its own position's q row per load instruction: 32 partial cache lines per instruction, the
+// four instructions of a 32-channel block sweeping the same 32 lines while they are in flight (the pattern layer 1 of the cost volume
+// and the patch kernel had: CvRowsRequest above, pt_rows_request in fused_patch.hip).  Here a 32-channel block of the 32 rows of a unit
+// -- 128 contiguous bytes per position -- is one ROUND: four global_load_lds of 16 bytes per lane into the wave's own 4 KiB slab,
+// instruction T serving positions 8 T .. 8 T + 7, lane L chunk L & 7 of position 8 T + (L >> 3): eight lines per instruction, each
+// fetched once.  C1 / 32 rounds per unit share the slab, one after the other.  Slot s of a position's 128 bytes holds source chunk
+// s ^ sa_rows_swz(position), so that the 16 lanes a ds_read_b128 serves together hit 16 different 16-byte bank groups.
+constexpr int SA_ROWS_F4 = 32 * 8;                                 // f4 per wave: 32 positions x 8 slots of 16 bytes
+constexpr int sa_rows_swz(int pos) { return (pos >> 1) & 7; }
+constexpr int sa_rows_slot(int pos, int chunk) { return pos * 8 + (chunk ^ sa_rows_swz(pos)); }      // f4 index in the slab
+// Every chunk, both halves of the columns, for the two ways the 32 columns of one hh may be cut into groups of 16: consecutive columns,
+// and the lane groups ds_read_b128 is served in on gfx950 ({0-3, 12-15, 20-27} and {4-11, 16-19, 28-31}).  64 banks of four bytes are
+// 16 groups of 16 bytes.
+constexpr bool sa_rows_conflict_free() {
+    constexpr int served[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27}, {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
+    for (int chunk = 0; chunk < 8; ++chunk)
+        for (int g = 0; g < 2; ++g) {
+            unsigned seen_a = 0u, seen_b = 0u;
+            for (int k = 0; k < 16; ++k) {
+                const unsigned a = 1u << (sa_rows_slot(16 * g + k, chunk) & 15), bgrp = 1u << (sa_rows_slot(served[g][k], chunk) & 15);
+                if ((seen_a & a) || (seen_b & bgrp)) return false;
+                seen_a |= a; seen_b |= bgrp;
+            }
+        }
+    return true;
+}
+static_assert(sa_rows_conflict_free(), "a ds_read_b128 of the staged rows must touch 16 different bank groups per lane group");
+static_assert(sa_rows_swz(31) < 8 && sa_rows_slot(31, 7) < SA_ROWS_F4, "a position's chunks stay inside its own 128 bytes of the slab");
+// Which instances take their rows through LDS (the others keep the direct gather): the place for an exception.
+constexpr bool sa_split_rows_lds(int ns, int c1) { return true; }
+struct SaRows {
+    const char *q;                 // row 0, first column, of this workgroup's sample (uniform; byte offsets from here are 32-bit)
+    f4 *slab;                      // this wave's 4 KiB
+    unsigned ro[4];                // instruction T: byte offset of position 8 T + (lane >> 3)'s row plus this lane's (swizzled) source chunk
+    // rowoff: byte offset of the row of this lane's position (lane col and lane 32 + col hold the same)
+    __device__ __forceinline__ void offsets(unsigned rowoff, int lane) {
+#pragma unroll
+        for (int T = 0; T < 4; ++T)
+            ro[T] = (unsigned)__shfl((int)rowoff, 8 * T + (lane >> 3), 64) + ((unsigned)((lane & 7) ^ ((4 * T + (lane >> 4)) & 7)) << 4);
+    }
+    // round R of the unit whose offsets are held.  DRAIN: reads of the slab may still be in flight (the round before was read just now).
+    template <int R, bool DRAIN>
+    __device__ __forceinline__ void request() const {
+        if constexpr (DRAIN) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // (uniform 64-bit base) + (32-bit per-lane offset), the round's 128 bytes in the offset: it stays below n * q_pitch * 4 < 2^32
+#pragma unroll
+        for (int T = 0; T < 4; ++T)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(q + (ro[T] + 128u * R)),
+                                             (__attribute__((address_space(3))) void *)(slab + T * 64), 16, 0, 0);
+    }
+    // this lane's four slots of the round that was requested last: channels 32 R + 8 q + 4 hh .. + 3 at r[4 q ..]
+    __device__ __forceinline__ void read(int col, int hh, f16v &r) const {
+        // The round has landed.  vmcnt(0) waits for every load outstanding, so nothing younger than the round may be in flight that the
+        // wave does not need here anyway: the coordinates that travel with round 0 are as old as it; the next unit's centroid and ball
+        // index (requested at the top of a tile, two units ahead with SA_INDEX_AHEAD 2) are consumed at SA_GATHER_STEP, before any
+        // read, or older than the round; the epilogue's stores come behind the last read.  A request moved between a round and its read
+        // would be waited for here.
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const f4 t = slab[sa_rows_slot(col, 2 * q4 + hh)];
+            r[4 * q4] = t.x; r[4 * q4 + 1] = t.y; r[4 * q4 + 2] = t.z; r[4 * q4 + 3] = t.w;
+        }
+    }
+};
 // PIPE: the tile loop software-pipelined by one unit with its constants out of the loop (the first of the two loops below); false: the
 // loop as it was before (rtk_sa_scale_split_serial, the comparison implementation).  The two compute the same bits.
 template <int NS, int C1, bool PIPE>
@@ -811,12 +885,19 @@ __global__ __launch_bounds__(256, SA_SPLIT_WAVES) void sa_scale_split_kernel(con
     rtk_decode_block(P.gx, b, bx, nbx);
     __shared__ __attribute__((aligned(16))) float s_bias2[PIPE ? 64 : 4];     // PIPE: bias2 and the offset image [KS][64] behind the image
     __shared__ float s_w1[PIPE ? KS * 64 : 1];
+    constexpr bool ROWS = PIPE && sa_split_rows_lds(NS, C1);                  // the q rows through LDS (SaRows): a slab per wave
+    __shared__ __attribute__((aligned(16))) f4 s_rows[ROWS ? 4 * SA_ROWS_F4 : 1];
+    static_assert(VB1 <= 2, "the schedule below: the last round is read behind the epilogue, the one before it behind layer 2");
     if constexpr (PIPE) {
         // The serial loop below reloads the 2 VB1 offset weights of a lane and its eight bias2 fragments on every tile (the latter
         // only after the last layer-2 MFMA, waited for one by one) and makes three dependent round trips per tile: ball index ->
-        // coordinates and q rows -> bias.  Here the offset image and bias2 live in LDS behind the split image (filled with it), and the gathers of unit u + 1 are in flight under unit u's layer 2: its ball index and centroid are requested at the top
-        // of u, its neighbour coordinates and q rows -- into registers of their own, which become layer 1's accumulators at the top of
-        // the next trip -- under u's layer-2 MFMAs (SA_GATHER_STEP).  Whether a next unit exists is wave-uniform; without one nothing is
+        // coordinates and q rows -> bias.  Here the offset image and bias2 live in LDS behind the split image (filled with it), and the
+        // gathers of unit u + 1 are in flight under unit u's layer 2: its ball index and centroid are requested at the top of u, its
+        // neighbour coordinates and q rows -- into registers of their own, which become layer 1's accumulators at the top of the next
+        // trip -- under u's layer-2 MFMAs (SA_GATHER_STEP).  ROWS: the q rows are requested there as DMA into the wave's slab (SaRows),
+        // one 32-channel block per round; the last round is read into those registers inside the epilogue, in front of its stores, the
+        // one before it (C1 = 64) behind layer 2's last MFMAs, where the next round is requested.  Every round requested is read in the
+        // same unit: a wave never exits with a DMA outstanding.  Whether a next unit exists is wave-uniform; without one nothing is
         // requested.  Lanes past live_c are redirected before every index load as in the serial loop.
         //
         // Prologue in two round trips (the serial one makes four: dst_nuniq -> fill and barrier -> src_nuniq, centroid, ball index ->
@@ -877,6 +958,15 @@ __global__ __launch_bounds__(256, SA_SPLIT_WAVES) void sa_scale_split_kernel(con
                     r[v][4 * q] = t.x; r[v][4 * q + 1] = t.y; r[v][4 * q + 2] = t.z; r[v][4 * q + 3] = t.w;
                 }
         };
+        // ROWS: the coordinates as plain loads, the rows as DMA requests (duplicate source rows alias row 0 before the offset is formed)
+        SaRows rw;
+        rw.q = reinterpret_cast<const char *>(P.q + (long)b * P.n * P.q_pitch);
+        rw.slab = s_rows + (ROWS ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * SA_ROWS_F4 : 0);      // (an SGPR: the DMA's LDS base is scalar)
+        auto gather_xyz = [&](int id, float &xa, float &xb) {
+            const long src = (long)b * P.n + id;
+            xa = P.xyz[src * 3 + hh]; xb = P.xyz[src * 3 + 2];
+        };
+        auto row_offset = [&](int id) { return (unsigned)(id < src_e ? id : 0) * ((unsigned)P.q_pitch * 4u); };
         auto request = [&](int u, int &cc, bool &vv, int &id, float &xa, float &xb) {      // centroid and ball index of unit u
             centroid_of(u, cc, vv);
             id = P.idx[(long)cc * NS + slot];
@@ -928,7 +1018,17 @@ __global__ __launch_bounds__(256, SA_SPLIT_WAVES) void sa_scale_split_kernel(con
 #undef RTK_SA_MM
                 if (MORE && s == GS) {
                     __builtin_amdgcn_sched_barrier(0);
-                    gather(id_n, na_n, nb_n, an);
+                    if constexpr (ROWS) {
+                        gather_xyz(id_n, na_n, nb_n);
+                        rw.offsets(row_offset(id_n), lane);
+                        rw.template request<0, false>();      // (the slab's last reads were layer 1's operands: returned long ago)
+                    } else gather(id_n, na_n, nb_n, an);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (ROWS && MORE && VB1 == 2 && s == SA_ROWS_READ_STEP) {      // round 0 into registers h has left, round 1 out
+                    __builtin_amdgcn_sched_barrier(0);
+                    rw.read(col, hh, an[0]);
+                    rw.template request<1, true>();
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -943,24 +1043,50 @@ __global__ __launch_bounds__(256, SA_SPLIT_WAVES) void sa_scale_split_kernel(con
                                           *reinterpret_cast<const f4 *>(s_bias2 + 32 * v + 8 * q + 4 * hh));
             const int qo = 2 * ((col >> 3) & 1) + ((col >> 2) & 1);
             float *o = P.out + (long)c * P.out_pitch + P.out_offset + 4 * hh + 8 * qo;
+            // the next unit's last round, covered by the reductions; in front of the stores, whose return its wait would otherwise include
+            auto rows_last = [&]() {
+                if constexpr (ROWS && MORE) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    rw.read(col, hh, an[VB1 - 1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
             if constexpr (NS == 32) {
                 f4 t[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) t[q] = wave_max_pair16(m[0][q], m[1][q], kinf);
                 const f4 r = relu_med4(row_max16_transpose4(t[0], t[1], t[2], t[3]), kinf);
+                rows_last();
                 if (valid && (col & 3) == 0) *reinterpret_cast<f4 *>(o + 32 * ((col >> 4) & 1)) = r;
             } else {
+                f4 r[2];
 #pragma unroll
-                for (int v = 0; v < 2; ++v) {
-                    const f4 r = relu_med4(row_max16_transpose4(m[v][0], m[v][1], m[v][2], m[v][3]), kinf);
-                    if (valid && (col & 3) == 0) *reinterpret_cast<f4 *>(o + 32 * v) = r;
-                }
+                for (int v = 0; v < 2; ++v) r[v] = relu_med4(row_max16_transpose4(m[v][0], m[v][1], m[v][2], m[v][3]), kinf);
+                rows_last();
+#pragma unroll
+                for (int v = 0; v < 2; ++v)
+                    if (valid && (col & 3) == 0) *reinterpret_cast<f4 *>(o + 32 * v) = r[v];
             }
         };
         int id = id_s;
         c = c_s; valid = true; ca = ca_s; cb = cb_s;
         if ((unit + 1) * CPT > live_c) request(unit, c, valid, id, ca, cb);      // (wave-uniform) a partial first unit: the dependent path
-        gather(id, na, nb, a);
+        if constexpr (ROWS) {
+            // the first unit's rows: round 0 through the slab; at C1 = 64 the second block travels beside it as plain loads (the slab holds
+            // one round, and a second round behind the first would be a third round trip)
+            gather_xyz(id, na, nb);
+            rw.offsets(row_offset(id), lane);
+            rw.template request<0, false>();
+            if constexpr (VB1 == 2) {
+                const float *qrow = reinterpret_cast<const float *>(rw.q + row_offset(id)) + 32 + 4 * hh;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f4 t = *reinterpret_cast<const f4 *>(qrow + 8 * q);
+                    a[1][4 * q] = t.x; a[1][4 * q + 1] = t.y; a[1][4 * q + 2] = t.z; a[1][4 * q + 3] = t.w;
+                }
+            }
+            rw.read(col, hh, a[0]);
+        } else gather(id, na, nb, a);
         auto advance = [&]() {
             unit += stride; c = c_n; valid = valid_n; ca = ca_n; cb = cb_n; na = na_n; nb = nb_n;
             for (int v = 0; v < VB1; ++v) a[v] = an[v];       // (a rotation of registers; the trip count is a constant)
@@ -1231,6 +1357,13 @@ static int sa_scale_split_launch(int samples, int n, int npoint, int nsample, co
     RTK_REQUIRE(q_pitch % 4 == 0 && out_pitch % 4 == 0 && out_offset % 4 == 0, "sa_scale_split: pitches/offset must be multiples of 4");
     RTK_REQUIRE((long)samples * npoint * nsample < 0x7fffffffL && (long)samples * n < 0x7fffffffL && samples <= 65535,
                 "sa_scale_split: problem too large for 32-bit indexing");
+    RTK_REQUIRE(q_pitch >= c1, "sa_scale_split: q_pitch is smaller than the row's %d channels", c1);
+    // the pipelined loop addresses a sample's q rows by 32-bit byte offsets (SaRows); the serial one serves whatever they cannot reach
+    if constexpr (PIPE) {
+        if ((double)n * q_pitch * 4.0 >= 4294967296.0)
+            return sa_scale_split_launch<false>(samples, n, npoint, nsample, xyz, new_xyz, idx, q, q_pitch, c1, w1xyz_packed, split_image, image_scale,
+                                                bias2, out, out_pitch, out_offset, src_nuniq, dst_nuniq, stream);
+    }
     SaSplitParams P;
     P.samples = samples; P.n = n; P.npoint = npoint;
     P.xyz = xyz; P.new_xyz = new_xyz; P.idx = idx; P.q = q; P.q_pitch = q_pitch; P.w1 = w1xyz_packed;
