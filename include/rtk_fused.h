@@ -252,7 +252,11 @@ RTK_EXPORT int rtk_prepare_inputs(int b, int n, const float *pc1, const float *p
 RTK_EXPORT int rtk_fps_centroids(int b, int n, int npoint, const float *xyz, int *idx, float *new_xyz, int *nuniq,
                                  int *tie, const int *n_valid, float *snap, int *first_tie, rtk_stream_t stream);
 
-/* rtk_knn_point over padded batches: only points[b][0 .. n_valid[b]) are candidates (n_valid (B) int32, >= k). */
+/* rtk_knn_point over padded batches: only points[b][0 .. n_valid[b]) are candidates (n_valid (B) int32; n_valid[b] >= n: all n rows).
+ * A sample with FEWER valid points than neighbours asked for, n_valid[b] < k, takes rows [0, k) as its candidates: the caller's padding
+ * rows n_valid[b] .. k-1 take part with the coordinates they hold (copies of row 0 under vod_gt.pad_frame_pairs: they tie with row 0
+ * and follow it in index order), so the k indices written are always distinct rows below max(n_valid[b], k).  n_valid == NULL:
+ * rtk_knn_point. */
 RTK_EXPORT int rtk_knn_point_masked(int b, int s, int n, int k, const float *query, const float *points, int64_t *idx,
                                     const int *n_valid, rtk_stream_t stream);
 
@@ -328,7 +332,9 @@ RTK_EXPORT int rtk_ball_query_pair(int b, int n, int npoint, float radius1, int 
 
 /* rtk_three_nn restricted to the non-duplicate unknown rows (rows >= unknown_nuniq[b] are not computed) and aware of
  * duplicate known rows (known rows >= known_nuniq[b] are copies of known row 0: only the unique prefix is scanned,
- * the result is identical to the full scan).  Either counter may be NULL. */
+ * the result is identical to the full scan).  Either counter may be NULL.
+ * Rows are written in whole chunks of 64 queries: rows [unknown_nuniq[b], roundup(unknown_nuniq[b], 64)) below n are written too (valid
+ * indices and distances, which no consumer may rely on); rows at or past roundup(unknown_nuniq[b], 64) keep the caller's bits. */
 RTK_EXPORT int rtk_three_nn_masked(int b, int n, int m, const float *unknown, const float *known, float *dist2, int *idx,
                                    const int *unknown_nuniq, const int *known_nuniq, rtk_stream_t stream);
 
