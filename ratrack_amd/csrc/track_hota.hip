@@ -9,66 +9,15 @@
 // As in track_sweep.hip the log holds a few detections per frame and the kernel is latency bound and kept simple: whatever has an
 // order (the greedy pass, the pair insertions, the four sums) is one thread in that order; the lanes fetch, probe, look up and compute
 // the quotients.  Integers and fixed-order float64 sums only: the same bits on every run, and the bits of a host loop written from
-// the definitions.  The frame clamps, the hash and the track table's probe are track_sweep.hip's, restated here because that file's
-// kernels are pinned as they are.
+// the definitions.  The frame decode, the track table and the pair list are score_log_walk.h's.
 #include <math.h>
 
-#include "batch_common.h"
-#include "rtk_common.h"
-#include "rtk_score.h"
+#include "score_log_walk.h"
 
-#define HT_EMPTY ((int)0x80000000)      // no track id (ids are >= -1 in every producer of the log)
-#define HT_SLOTS (RTK_SCORE_SWEEP_TRACKS + RTK_SCORE_SWEEP_TRACKS / 2)      // the track table: a third stays empty, linear probing
+#define HT_SLOTS LW_SLOTS                                                   // the track table
 #define HT_PSLOTS (2 * RTK_SCORE_HOTA_PAIRS)                                // the pair lookup: half stays empty
 #define HT_SLOT_BITS 12                                                     // a pair's key: label entry << 12 | track slot
 static_assert(HT_SLOTS <= (1 << HT_SLOT_BITS), "a track slot must fit the pair key");
-
-struct ht_frame_t { int rec, lab, P, G, reset; };
-
-// a frame slot of the log, its counts brought into what the stream's log can hold: a foreign buffer is never read out of bounds
-__device__ __forceinline__ ht_frame_t ht_frame(const rtk_score_log_t &lg, int b, int f) {
-    const int4 w = *reinterpret_cast<const int4 *>(lg.frame + ((size_t)b * lg.F + f) * 4);
-    ht_frame_t fr;
-    fr.reset = (w.z >> 16) & 1;
-    fr.P = count_clamp(w.z & 0xffff, RTK_SCORE_MAX_OBJECTS);
-    fr.G = count_clamp(w.w, RTK_SCORE_MAX_BOXES);
-    fr.rec = count_clamp(w.x, lg.R - fr.P);
-    fr.lab = count_clamp(w.y, lg.R - fr.G);
-    if (fr.rec < 0) { fr.rec = 0; fr.P = 0; }
-    if (fr.lab < 0) { fr.lab = 0; fr.G = 0; }
-    return fr;
-}
-
-__device__ __forceinline__ unsigned ht_hash(int id) { return ((unsigned)id * 2654435761u) >> 8; }
-
-// the track table's slot of `id`, claimed on first sight (at most RTK_SCORE_SWEEP_TRACKS ids, so a probe sequence ends).  -1: no
-// room -- lanes that lose a slot to one another count twice for a moment, so a clip within a wave's width of the limit may be refused
-// as well; it is never accepted wrongly.
-__device__ __forceinline__ int ht_track_slot(int *key, int *used, int id) {
-    unsigned h = ht_hash(id) % HT_SLOTS;
-    for (int probe = 0; probe < HT_SLOTS; ++probe, h = (h + 1) % HT_SLOTS) {
-        int k = key[h];
-        if (k == id) return (int)h;
-        if (k != HT_EMPTY) continue;
-        if (atomicAdd(used, 1) >= RTK_SCORE_SWEEP_TRACKS) return -1;
-        k = atomicCAS(&key[h], HT_EMPTY, id);
-        if (k == HT_EMPTY) return (int)h;
-        atomicSub(used, 1);
-        if (k == id) return (int)h;      // another lane claimed the slot for the same id: one slot per id
-    }
-    return -1;
-}
-
-// the pair lookup: ptab holds pair indices (-1 empty), the keys live in the insertion-ordered list.  -> the pair's index or -1
-__device__ __forceinline__ int ht_pair_find(const int *ptab, const int *pkey, int key) {
-    unsigned h = ht_hash(key) % HT_PSLOTS;
-    for (int probe = 0; probe < HT_PSLOTS; ++probe, h = (h + 1) % HT_PSLOTS) {
-        const int p = ptab[h];
-        if (p < 0) return -1;
-        if (pkey[p] == key) return p;
-    }
-    return -1;
-}
 
 // LDS: riou[MAX_OBJECTS], quot[3][WAVE] f64 | label table key, cg [T] | track table key, ct [HT_SLOTS] | pair list key, n [PAIRS] |
 // pair lookup [2 PAIRS] | rj, rslot [MAX_OBJECTS] | glabel, gpred, entry, gpair [MAX_BOXES] | 8 scalars
@@ -94,21 +43,21 @@ __global__ __launch_bounds__(RTK_WAVE) void hota_kernel(int T, const rtk_score_l
     const double alpha = (double)(a + 1) / (double)(A + 1);
     const bool filter = rec_score != nullptr && threshold != nullptr;
     const double tau = filter ? *threshold : 0.0;
-    const int frames = count_clamp(lg.cursor[b * 4 + 0], lg.F);
+    const int frames = lw_frames(lg, b);
     const size_t rb = (size_t)b * lg.R;
     // thread 0's running values
     long long c_frames = 0, c_clips = 0, c_gt = 0, c_pred = 0, c_tp = 0, c_pairs = 0;
     double s_ass = 0.0, s_re = 0.0, s_pr = 0.0, s_loc = 0.0;
     int used = 0, npairs = 0;      // uniform: thread 0 publishes them through scal
 
-    for (int h = t; h < HT_SLOTS; h += RTK_WAVE) { tkey[h] = HT_EMPTY; tct[h] = 0; }
+    for (int h = t; h < HT_SLOTS; h += RTK_WAVE) { tkey[h] = LW_EMPTY; tct[h] = 0; }
     for (int h = t; h < HT_PSLOTS; h += RTK_WAVE) ptab[h] = -1;
     if (t < 8) scal[t] = 0;
     __syncthreads();
 
     for (int f = 0; f <= frames; ++f) {
-        ht_frame_t fr = {};
-        if (f < frames) fr = ht_frame(lg, b, f);
+        lw_frame_t fr = {};
+        if (f < frames) fr = lw_frame(lg, b, f);
         if ((f == frames || fr.reset) && f > 0) {
             // ---- the clip closes: the lanes compute a wave's width of quotients, thread 0 adds them in the pairs' order ----
             for (int base = 0; base < npairs; base += RTK_WAVE) {
@@ -132,7 +81,7 @@ __global__ __launch_bounds__(RTK_WAVE) void hota_kernel(int T, const rtk_score_l
                 }
                 __syncthreads();
             }
-            for (int h = t; h < HT_SLOTS; h += RTK_WAVE) { tkey[h] = HT_EMPTY; tct[h] = 0; }
+            for (int h = t; h < HT_SLOTS; h += RTK_WAVE) { tkey[h] = LW_EMPTY; tct[h] = 0; }
             for (int h = t; h < HT_PSLOTS; h += RTK_WAVE) ptab[h] = -1;
             if (t == 0) {
                 c_clips += 1; c_pairs += npairs;
@@ -157,12 +106,12 @@ __global__ __launch_bounds__(RTK_WAVE) void hota_kernel(int T, const rtk_score_l
         __syncthreads();
         for (int i = t; i < fr.P; i += RTK_WAVE) {
             const size_t r = rb + fr.rec + i;
-            const bool stays = !filter || !(rec_score[r] < tau);      // a score equal to the threshold stays
+            const bool stays = !filter || lw_stays(rec_score[r], tau);
             const int lab = lg.rec_best[r];
             const double iou = lg.rec_iou[r];
             int j = -1, s = -1;
             if (stays) {
-                s = ht_track_slot(tkey, &scal[HT_S_TRACKS], lg.rec_track[r]);
+                s = lw_track_slot<true>(tkey, &scal[HT_S_TRACKS], lg.rec_track[r]);
                 if (s >= 0) atomicAdd(&tct[s], 1); else scal[HT_S_OVERFLOW] = 1;
                 if (lab != -1 && iou >= alpha) {
                     for (int k = fr.G - 1; k >= 0; --k)
@@ -205,7 +154,7 @@ __global__ __launch_bounds__(RTK_WAVE) void hota_kernel(int T, const rtk_score_l
         for (int j = t; j < fr.G; j += RTK_WAVE) {
             const int i = gpred[j];
             if (i < 0 || entry[j] < 0 || rslot[i] < 0) continue;
-            gpair[j] = ht_pair_find(ptab, pkey, (entry[j] << HT_SLOT_BITS) | rslot[i]);
+            gpair[j] = lw_pair_find<HT_PSLOTS>(ptab, pkey, (entry[j] << HT_SLOT_BITS) | rslot[i]);
         }
         __syncthreads();
         // ---- and thread 0 counts them, new pairs appended in detection order ----
@@ -217,11 +166,7 @@ __global__ __launch_bounds__(RTK_WAVE) void hota_kernel(int T, const rtk_score_l
                 if (p < 0) {
                     if (npairs >= RTK_SCORE_HOTA_PAIRS) { scal[HT_S_OVERFLOW] = 1; continue; }
                     p = npairs++;
-                    const int key = (entry[j] << HT_SLOT_BITS) | rslot[i];
-                    pkey[p] = key; pn[p] = 0;
-                    unsigned h = ht_hash(key) % HT_PSLOTS;
-                    while (ptab[h] >= 0) h = (h + 1) % HT_PSLOTS;      // at most PAIRS of 2 PAIRS slots are taken
-                    ptab[h] = p;
+                    lw_pair_append<HT_PSLOTS>(ptab, pkey, pn, p, (entry[j] << HT_SLOT_BITS) | rslot[i]);      // at most PAIRS of 2 PAIRS slots are taken
                 }
                 pn[p] += 1;
             }
@@ -242,17 +187,13 @@ __global__ __launch_bounds__(RTK_WAVE) void hota_kernel(int T, const rtk_score_l
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static bool ht_log_ok(const rtk_score_log_t *lg) {
-    return lg && lg->F >= 1 && lg->R >= 1 && lg->cursor && lg->frame && lg->label && lg->rec_track && lg->rec_best && lg->rec_conf && lg->rec_iou;
-}
-
 extern "C" int rtk_score_hota(int B, int T, const rtk_score_log_t *lg, const double *rec_score, const double *threshold, int alphas,
                               long long *counters, double *sums, int *flags, rtk_stream_t stream) {
     RTK_REQUIRE(B >= 1 && B <= 65535 && T >= 1 && alphas >= 1 && alphas <= 63, "score_hota: bad sizes B=%d T=%d alphas=%d", B, T, alphas);
     const size_t lds = ht_lds(T);
     RTK_REQUIRE(lds <= RTK_SCORE_LDS_LIMIT, "score_hota: T=%d label-table entries need %zu bytes of LDS per stream, the limit is %d", T, lds,
                 RTK_SCORE_LDS_LIMIT);
-    RTK_REQUIRE(ht_log_ok(lg), "score_hota: null or empty log");
+    RTK_REQUIRE(lw_log_ok(lg), "score_hota: null or empty log");
     RTK_REQUIRE(counters && sums && flags, "score_hota: null output");
     (void)hipFuncSetAttribute((const void *)hota_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RTK_SCORE_LDS_LIMIT);
     hota_kernel<<<dim3(B, alphas), RTK_WAVE, lds, (hipStream_t)stream>>>(T, *lg, rec_score, threshold, counters, sums, flags);

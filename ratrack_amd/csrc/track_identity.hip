@@ -11,67 +11,17 @@
 // (the label table, the pair insertions) is one thread in that order; the lanes fetch, probe and look up, and solve the assignment
 // together.  Integers only: the same numbers on every run.  gt and pred are running sums, so the tables carry neither per-id counts
 // nor float64 scratch, and every table of the walk except the pair list is dead when a clip closes: the solver works in their place.
-// The frame clamps, the hash and the probes are track_hota.hip's, restated here because that file's kernel is pinned as it is.
-#include "batch_common.h"
+// The frame decode, the track table and the pair list are score_log_walk.h's.
 #include "lds_assignment.h"
-#include "rtk_common.h"
-#include "rtk_score.h"
+#include "score_log_walk.h"
 
-#define ID_EMPTY ((int)0x80000000)      // no track id (ids are >= -1 in every producer of the log)
-#define ID_SLOTS (RTK_SCORE_SWEEP_TRACKS + RTK_SCORE_SWEEP_TRACKS / 2)      // the track table: a third stays empty, linear probing
+#define ID_SLOTS LW_SLOTS                                                   // the track table
 #define ID_PSLOTS (2 * RTK_SCORE_ID_PAIRS)                                  // the pair lookup: half stays empty
 #define ID_SLOT_BITS LA_COL_BITS                                            // a pair's key: label entry << 12 | track slot
 #define ID_SLOT_MASK ((1 << ID_SLOT_BITS) - 1)
 #define ID_MAX_FRAMES (1 << 28)                                             // a pair's weight is at most the frames of its clip
 static_assert(ID_SLOTS <= (1 << ID_SLOT_BITS), "a track slot must fit the pair key");
 static_assert(RTK_SCORE_ID_PAIRS <= (1 << ID_SLOT_BITS), "a compacted track index must fit the pair key");
-
-struct id_frame_t { int rec, lab, P, G, reset; };
-
-// a frame slot of the log, its counts brought into what the stream's log can hold: a foreign buffer is never read out of bounds
-__device__ __forceinline__ id_frame_t id_frame(const rtk_score_log_t &lg, int b, int f) {
-    const int4 w = *reinterpret_cast<const int4 *>(lg.frame + ((size_t)b * lg.F + f) * 4);
-    id_frame_t fr;
-    fr.reset = (w.z >> 16) & 1;
-    fr.P = count_clamp(w.z & 0xffff, RTK_SCORE_MAX_OBJECTS);
-    fr.G = count_clamp(w.w, RTK_SCORE_MAX_BOXES);
-    fr.rec = count_clamp(w.x, lg.R - fr.P);
-    fr.lab = count_clamp(w.y, lg.R - fr.G);
-    if (fr.rec < 0) { fr.rec = 0; fr.P = 0; }
-    if (fr.lab < 0) { fr.lab = 0; fr.G = 0; }
-    return fr;
-}
-
-__device__ __forceinline__ unsigned id_hash(int id) { return ((unsigned)id * 2654435761u) >> 8; }
-
-// the track table's slot of `id`, claimed on first sight (at most RTK_SCORE_SWEEP_TRACKS ids, so a probe sequence ends).  -1: no
-// room -- lanes that lose a slot to one another count twice for a moment, so a clip within a wave's width of the limit may be refused
-// as well; it is never accepted wrongly.
-__device__ __forceinline__ int id_track_slot(int *key, int *used, int id) {
-    unsigned h = id_hash(id) % ID_SLOTS;
-    for (int probe = 0; probe < ID_SLOTS; ++probe, h = (h + 1) % ID_SLOTS) {
-        int k = key[h];
-        if (k == id) return (int)h;
-        if (k != ID_EMPTY) continue;
-        if (atomicAdd(used, 1) >= RTK_SCORE_SWEEP_TRACKS) return -1;
-        k = atomicCAS(&key[h], ID_EMPTY, id);
-        if (k == ID_EMPTY) return (int)h;
-        atomicSub(used, 1);
-        if (k == id) return (int)h;      // another lane claimed the slot for the same id: one slot per id
-    }
-    return -1;
-}
-
-// the pair lookup: ptab holds pair indices (-1 empty), the keys live in the insertion-ordered list.  -> the pair's index or -1
-__device__ __forceinline__ int id_pair_find(const int *ptab, const int *pkey, int key) {
-    unsigned h = id_hash(key) % ID_PSLOTS;
-    for (int probe = 0; probe < ID_PSLOTS; ++probe, h = (h + 1) % ID_PSLOTS) {
-        const int p = ptab[h];
-        if (p < 0) return -1;
-        if (pkey[p] == key) return p;
-    }
-    return -1;
-}
 
 // LDS, in ints.  The pair list (key, n) comes first and lives through the clip's close; behind it EITHER the walk's tables -- label
 // table [TCAP] | track table [ID_SLOTS] | pair lookup [ID_PSLOTS] | rkey, rpair [MAX_OBJECTS] | glabel, entry [MAX_BOXES] | 8 scalars --
@@ -109,19 +59,19 @@ __global__ __launch_bounds__(RTK_WAVE) void identity_kernel(int T, const rtk_sco
     const double alpha = alphas[a];
     const bool filter = rec_score != nullptr && threshold != nullptr;
     const double tau = filter ? *threshold : 0.0;
-    const int frames = count_clamp(lg.cursor[b * 4 + 0], lg.F);
+    const int frames = lw_frames(lg, b);
     const size_t rb = (size_t)b * lg.R;
     long long c_frames = 0, c_clips = 0, c_gt = 0, c_pred = 0, c_idtp = 0, c_pairs = 0;      // uniform: every lane counts them alike
     int used = 0, npairs = 0, overflow = 0;      // uniform: thread 0 publishes them through scal
 
-    for (int h = t; h < ID_SLOTS; h += RTK_WAVE) tkey[h] = ID_EMPTY;
+    for (int h = t; h < ID_SLOTS; h += RTK_WAVE) tkey[h] = LW_EMPTY;
     for (int h = t; h < ID_PSLOTS; h += RTK_WAVE) ptab[h] = -1;
     if (t < 8) scal[t] = 0;
     __syncthreads();
 
     for (int f = 0; f <= frames; ++f) {
-        id_frame_t fr = {};
-        if (f < frames) fr = id_frame(lg, b, f);
+        lw_frame_t fr = {};
+        if (f < frames) fr = lw_frame(lg, b, f);
         if ((f == frames || fr.reset) && f > 0) {
             // ---- the clip closes.  The tracks that appear in a pair are numbered 0, 1, ... in the order of their first pair: the
             //      track table gives way to "first pair of this slot", the pair lookup to that pair's number ----
@@ -148,7 +98,7 @@ __global__ __launch_bounds__(RTK_WAVE) void identity_kernel(int T, const rtk_sco
             c_idtp += la_solve(used, ncols, npairs, pkey, pn, work);
             c_clips += 1; c_pairs += npairs;
             __syncthreads();
-            for (int h = t; h < ID_SLOTS; h += RTK_WAVE) tkey[h] = ID_EMPTY;
+            for (int h = t; h < ID_SLOTS; h += RTK_WAVE) tkey[h] = LW_EMPTY;
             for (int h = t; h < ID_PSLOTS; h += RTK_WAVE) ptab[h] = -1;
             if (t < 8) scal[t] = 0;
             used = 0; npairs = 0;
@@ -183,10 +133,10 @@ __global__ __launch_bounds__(RTK_WAVE) void identity_kernel(int T, const rtk_sco
             bool stays = false;
             if (i < fr.P) {
                 const size_t r = rb + fr.rec + i;
-                stays = !filter || !(rec_score[r] < tau);      // a score equal to the threshold stays
+                stays = !filter || lw_stays(rec_score[r], tau);
                 int key = -1;
                 if (stays) {
-                    const int s = id_track_slot(tkey, &scal[ID_S_TRACKS], lg.rec_track[r]);
+                    const int s = lw_track_slot<true>(tkey, &scal[ID_S_TRACKS], lg.rec_track[r]);
                     if (s < 0) scal[ID_S_OVERFLOW] = 1;
                     const int lab = lg.rec_best[r];
                     if (s >= 0 && lab != -1 && lg.rec_iou[r] >= alpha) {
@@ -197,7 +147,7 @@ __global__ __launch_bounds__(RTK_WAVE) void identity_kernel(int T, const rtk_sco
                     }
                 }
                 rkey[i] = key;
-                rpair[i] = key < 0 ? -1 : id_pair_find(ptab, pkey, key);
+                rpair[i] = key < 0 ? -1 : lw_pair_find<ID_PSLOTS>(ptab, pkey, key);
             }
             c_pred += __popcll(__ballot(stays));
         }
@@ -219,10 +169,7 @@ __global__ __launch_bounds__(RTK_WAVE) void identity_kernel(int T, const rtk_sco
                 if (p < 0) {
                     if (npairs >= RTK_SCORE_ID_PAIRS) { scal[ID_S_OVERFLOW] = 1; continue; }
                     p = npairs++;
-                    pkey[p] = key; pn[p] = 0;
-                    unsigned h = id_hash(key) % ID_PSLOTS;
-                    while (ptab[h] >= 0) h = (h + 1) % ID_PSLOTS;      // at most PAIRS of 2 PAIRS slots are taken
-                    ptab[h] = p;
+                    lw_pair_append<ID_PSLOTS>(ptab, pkey, pn, p, key);      // at most PAIRS of 2 PAIRS slots are taken
                 }
                 pn[p] += 1;
             }
@@ -241,10 +188,6 @@ __global__ __launch_bounds__(RTK_WAVE) void identity_kernel(int T, const rtk_sco
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static bool id_log_ok(const rtk_score_log_t *lg) {
-    return lg && lg->F >= 1 && lg->R >= 1 && lg->cursor && lg->frame && lg->label && lg->rec_track && lg->rec_best && lg->rec_conf && lg->rec_iou;
-}
-
 extern "C" int rtk_score_identity_lds_bytes(int T) {
     if (T < 1 || T > (1 << 24)) return -1;
     return (int)id_lds(T);
@@ -257,7 +200,7 @@ extern "C" int rtk_score_identity(int B, int T, const rtk_score_log_t *lg, const
     const size_t lds = id_lds(T);
     RTK_REQUIRE(lds <= RTK_SCORE_LDS_LIMIT, "score_identity: T=%d label-table entries need %zu bytes of LDS per stream, the limit is %d", T, lds,
                 RTK_SCORE_LDS_LIMIT);
-    RTK_REQUIRE(id_log_ok(lg), "score_identity: null or empty log");
+    RTK_REQUIRE(lw_log_ok(lg), "score_identity: null or empty log");
     RTK_REQUIRE(lg->F <= ID_MAX_FRAMES, "score_identity: a log of F=%d frames per stream, the limit is %d", lg->F, ID_MAX_FRAMES);
     RTK_REQUIRE(alphas && counters && flags, "score_identity: null levels or null output");
     if (T <= ID_TCAP_SMALL)

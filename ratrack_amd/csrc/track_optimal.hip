@@ -9,37 +9,15 @@
 //
 // As in track_sweep.hip the log holds a few detections per frame and the kernel is latency bound and kept simple: whatever has an
 // order (the IoU sum, the track table) is one thread in that order; the lanes fetch, test the pairs and solve the assignment together.
-// Integers and one fixed-order float64 sum: the same bits on every run.  The frame clamps are track_sweep.hip's, restated here because
-// that file's kernels are pinned as they are.
+// Integers and one fixed-order float64 sum: the same bits on every run.  The frame decode of the two logs is score_log_walk.h's.
 #include <math.h>
 
-#include "batch_common.h"
 #include "lds_assignment.h"
-#include "rtk_common.h"
-#include "rtk_score.h"
+#include "score_log_walk.h"
 
 #define OP_WEIGHT_ONE (1 << 23)      // a match; the quantised IoUs of a frame sum to at most MAX_BOXES * 65536 = 2^22 below it
 static_assert(RTK_SCORE_MAX_BOXES * 65536 < OP_WEIGHT_ONE && OP_WEIGHT_ONE + 65536 < (1 << 29), "the weights of one frame: la_solve's range");
 static_assert(RTK_SCORE_MAX_BOXES <= (1 << 8) && RTK_SCORE_MAX_BOXES <= (1 << LA_COL_BITS), "a kept-object index must fit the pair key");
-
-struct op_frame_t { int rec, lab, P, G, reset, pair, pairs; };
-
-// a frame slot of the two logs, its counts brought into what the stream's logs can hold: a foreign buffer is never read out of bounds
-__device__ __forceinline__ op_frame_t op_frame(const rtk_score_log_t &lg, const rtk_score_pairs_t &pr, int b, int f) {
-    const int4 w = *reinterpret_cast<const int4 *>(lg.frame + ((size_t)b * lg.F + f) * 4);
-    op_frame_t fr;
-    fr.reset = (w.z >> 16) & 1;
-    fr.P = count_clamp(w.z & 0xffff, RTK_SCORE_MAX_OBJECTS);
-    fr.G = count_clamp(w.w, RTK_SCORE_MAX_BOXES);
-    fr.rec = count_clamp(w.x, lg.R - fr.P);
-    fr.lab = count_clamp(w.y, lg.R - fr.G);
-    if (fr.rec < 0) { fr.rec = 0; fr.P = 0; }
-    if (fr.lab < 0) { fr.lab = 0; fr.G = 0; }
-    const int *fp = pr.frame_pair + ((size_t)b * lg.F + f) * 2;
-    fr.pairs = count_clamp(fp[1], pr.Q);
-    fr.pair = count_clamp(fp[0], pr.Q - fr.pairs);
-    return fr;
-}
 
 // LDS, in ints: miou[MAX_BOXES] f64 | edge key, weight [PAIR_EDGES] | the solver's tables (MAX_OBJECTS rows, MAX_BOXES columns,
 // PAIR_EDGES edges) | track table key, last, seen, matched, gap [TCAP] | rstay, rtrack [MAX_OBJECTS] | glabel, entry, gpred
@@ -65,7 +43,7 @@ enum { OP_S_MT = 0, OP_S_PT = 1, OP_S_ML = 2, OP_S_USED = 3, OP_S_EDGES = 4, OP_
 
 // the IoU of a logged pair of frame `fr` and its place in the assignment, or false: the pair does not describe its frame, its
 // detection was removed, or its IoU is below min_iou
-__device__ __forceinline__ bool op_candidate(const rtk_score_pairs_t &pr, const op_frame_t &fr, size_t rb, size_t qb, int p, const int *rstay,
+__device__ __forceinline__ bool op_candidate(const rtk_score_pairs_t &pr, const lw_pair_frame_t &fr, size_t rb, size_t qb, int p, const int *rstay,
                                              double min_iou, int *row, int *col, double *iou) {
     const int key = pr.pair_key[qb + fr.pair + p], c = pr.pair_common[qb + fr.pair + p];
     const int i = key >> 8, j = key & 255;
@@ -104,7 +82,7 @@ __global__ __launch_bounds__(RTK_WAVE) void optimal_replay_kernel(int T, const r
         return;
     }
     const double tau = thresholds[x];
-    const int frames = count_clamp(lg.cursor[b * 4 + 0], lg.F);
+    const int frames = lw_frames(lg, b);
     // uniform running values: every lane counts them alike
     long long c_frames = 0, c_gt = 0, c_pred = 0, c_tp = 0, c_iouq = 0;
     // thread 0's running values
@@ -115,8 +93,8 @@ __global__ __launch_bounds__(RTK_WAVE) void optimal_replay_kernel(int T, const r
     __syncthreads();
 
     for (int f = 0; f <= frames; ++f) {
-        op_frame_t fr = {};
-        if (f < frames) fr = op_frame(lg, pr, b, f);
+        lw_pair_frame_t fr = {};
+        if (f < frames) fr = lw_pair_frame(lg, pr, b, f);
         if (f == frames || fr.reset) {
             // ---- the clip closes ----
             int mt = 0, pt = 0, ml = 0;
@@ -151,7 +129,7 @@ __global__ __launch_bounds__(RTK_WAVE) void optimal_replay_kernel(int T, const r
             bool stays = false;
             if (i < fr.P) {
                 const size_t r = rb + fr.rec + i;
-                stays = !(rec_score[r] < tau);      // a score equal to the threshold stays
+                stays = lw_stays(rec_score[r], tau);
                 rstay[i] = stays ? 1 : 0;
                 rtrack[i] = lg.rec_track[r];
             }
@@ -240,10 +218,6 @@ __global__ __launch_bounds__(RTK_WAVE) void optimal_replay_kernel(int T, const r
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static bool op_log_ok(const rtk_score_log_t *lg) {
-    return lg && lg->F >= 1 && lg->R >= 1 && lg->cursor && lg->frame && lg->label && lg->rec_track && lg->rec_best && lg->rec_conf && lg->rec_iou;
-}
-
 extern "C" int rtk_score_optimal_lds_bytes(int T) {
     if (T < 1 || T > (1 << 24)) return -1;
     return (int)op_lds(T);
@@ -259,7 +233,7 @@ extern "C" int rtk_score_replay_optimal(int B, int T, const rtk_score_log_t *lg,
                 "score_replay_optimal: T=%d track-table entries need %zu bytes of LDS per stream, the limit is %d (at most T=%d)", T, lds,
                 RTK_SCORE_LDS_LIMIT, OP_TCAP_LARGE);
     RTK_REQUIRE(min_iou > 0.0 && min_iou < INFINITY, "score_replay_optimal: min_iou=%g must be finite and above 0", min_iou);
-    RTK_REQUIRE(op_log_ok(lg), "score_replay_optimal: null or empty log");
+    RTK_REQUIRE(lw_log_ok(lg), "score_replay_optimal: null or empty log");
     RTK_REQUIRE(pr && pr->Q >= 1 && pr->cursor && pr->frame_pair && pr->pair_key && pr->pair_common && pr->rec_size && pr->label_size,
                 "score_replay_optimal: null or empty pair log");
     RTK_REQUIRE(rec_score && thresholds && counters && iou_q && iou_sum && flags, "score_replay_optimal: null argument");

@@ -9,83 +9,41 @@
 //
 // The log holds a few detections per frame, so all three are latency bound and kept simple: whatever has an order (the sums, the
 // greedy pass, the table) is one thread in that order; the lanes only fetch, probe and look up.  Integer sums and fixed-order float64
-// sums only: the same bits on every run, and the bits of a host loop written from the definitions.
+// sums only: the same bits on every run, and the bits of a host loop written from the definitions.  The frame decode and the track
+// table are score_log_walk.h's.
 #include <math.h>
 
-#include "batch_common.h"
-#include "rtk_common.h"
-#include "rtk_score.h"
+#include "score_log_walk.h"
 
 #define SW_THREADS 256
-#define SW_EMPTY ((int)0x80000000)      // no track id (ids are >= -1 in every producer of the log)
-
-struct sw_frame_t { int rec, lab, P, G, reset; };
-
-// a frame slot of the log, its counts brought into what the stream's log can hold (a log is only ever written by ts_logged_kernel,
-// which keeps these bounds; the clamps keep a foreign buffer from being read out of bounds)
-__device__ __forceinline__ sw_frame_t sw_frame(const rtk_score_log_t &lg, int b, int f) {
-    const int4 w = *reinterpret_cast<const int4 *>(lg.frame + ((size_t)b * lg.F + f) * 4);
-    sw_frame_t fr;
-    fr.reset = (w.z >> 16) & 1;
-    fr.P = count_clamp(w.z & 0xffff, RTK_SCORE_MAX_OBJECTS);
-    fr.G = count_clamp(w.w, RTK_SCORE_MAX_BOXES);
-    fr.rec = count_clamp(w.x, lg.R - fr.P);
-    fr.lab = count_clamp(w.y, lg.R - fr.G);
-    if (fr.rec < 0) { fr.rec = 0; fr.P = 0; }
-    if (fr.lab < 0) { fr.lab = 0; fr.G = 0; }
-    return fr;
-}
-
-__device__ __forceinline__ unsigned sw_hash(int id) { return ((unsigned)id * 2654435761u) >> 8; }
 
 // ------------------------------------------------------------------------------------------------
 // rtk_score_track_means
 // ------------------------------------------------------------------------------------------------
-// LDS: sum[H] f64 | key[H], cnt[H] i32 | slot[MAX_OBJECTS] i32 | 2 scalars.  H = 1.5 * RTK_SCORE_SWEEP_TRACKS slots (48 KB), linear
-// probing.
-#define SW_SLOTS (RTK_SCORE_SWEEP_TRACKS + RTK_SCORE_SWEEP_TRACKS / 2)
-
-// the slot of `id`; with INSERT an empty slot is claimed for it (at most RTK_SCORE_SWEEP_TRACKS ids: a third of the table stays
-// empty, so a probe sequence ends).  -1: not there / no room -- lanes that lose a slot to one another count twice for a moment, so
-// a clip within a wave's width of the limit may be refused as well; it is never accepted wrongly.
-template <bool INSERT>
-__device__ __forceinline__ int sw_slot(int *key, int *used, int id) {
-    unsigned h = sw_hash(id) % SW_SLOTS;
-    for (int probe = 0; probe < SW_SLOTS; ++probe, h = (h + 1) % SW_SLOTS) {
-        int k = key[h];
-        if (k == id) return (int)h;
-        if (k != SW_EMPTY) continue;
-        if (!INSERT) return -1;
-        if (atomicAdd(used, 1) >= RTK_SCORE_SWEEP_TRACKS) return -1;
-        k = atomicCAS(&key[h], SW_EMPTY, id);
-        if (k == SW_EMPTY) return (int)h;
-        atomicSub(used, 1);
-        if (k == id) return (int)h;      // another lane claimed the slot for the same id: one slot per id
-    }
-    return -1;
-}
+// LDS: sum[H] f64 | key[H], cnt[H] i32 | slot[MAX_OBJECTS] i32 | 2 scalars.  H = LW_SLOTS (48 KB), the track table of score_log_walk.h.
+#define SW_SLOTS LW_SLOTS
 
 __global__ __launch_bounds__(SW_THREADS) void sweep_means_kernel(const rtk_score_log_t lg, double *rec_score, int *flags) {
     __shared__ double sum[SW_SLOTS];
     __shared__ int key[SW_SLOTS], cnt[SW_SLOTS], slot[RTK_SCORE_MAX_OBJECTS], scal[2];      // scal: 0 ids in the table | 1 overflow
     const int b = blockIdx.x, t = threadIdx.x;
-    const int frames = count_clamp(lg.cursor[b * 4 + 0], lg.F);
+    const int frames = lw_frames(lg, b);
     const size_t rb = (size_t)b * lg.R;
-    for (int h = t; h < SW_SLOTS; h += SW_THREADS) { key[h] = SW_EMPTY; cnt[h] = 0; sum[h] = 0.0; }
+    for (int h = t; h < SW_SLOTS; h += SW_THREADS) { key[h] = LW_EMPTY; cnt[h] = 0; sum[h] = 0.0; }
     if (t < 2) scal[t] = 0;
     __syncthreads();
     int clip_rec = 0, end_rec = 0;      // the open clip's first record, and one past the last record walked
     for (int f = 0; f <= frames; ++f) {
-        sw_frame_t fr = {};
-        if (f < frames) fr = sw_frame(lg, b, f);
+        lw_frame_t fr = {};
+        if (f < frames) fr = lw_frame(lg, b, f);
         if (f == frames || fr.reset) {
             // ---- the clip closes: every record of it receives its track's score, the table empties ----
             for (int r = clip_rec + t; r < end_rec; r += SW_THREADS) {
-                const int s = sw_slot<false>(key, scal, lg.rec_track[rb + r]);
+                const int s = lw_track_slot<false>(key, scal, lg.rec_track[rb + r]);
                 if (s >= 0) rec_score[rb + r] = sum[s] / (double)cnt[s];
             }
             __syncthreads();
-            for (int h = t; h < SW_SLOTS; h += SW_THREADS) { key[h] = SW_EMPTY; cnt[h] = 0; sum[h] = 0.0; }
+            for (int h = t; h < SW_SLOTS; h += SW_THREADS) { key[h] = LW_EMPTY; cnt[h] = 0; sum[h] = 0.0; }
             if (t == 0) scal[0] = 0;
             __syncthreads();
             clip_rec = end_rec;
@@ -93,7 +51,7 @@ __global__ __launch_bounds__(SW_THREADS) void sweep_means_kernel(const rtk_score
         }
         // ---- the frame's detections: the lanes find the slots, thread 0 adds in detection order ----
         for (int i = t; i < fr.P; i += SW_THREADS) {
-            const int s = sw_slot<true>(key, scal, lg.rec_track[rb + fr.rec + i]);
+            const int s = lw_track_slot<true>(key, scal, lg.rec_track[rb + fr.rec + i]);
             slot[i] = s;
             if (s < 0) scal[1] = 1;
         }
@@ -172,7 +130,7 @@ __global__ __launch_bounds__(RTK_WAVE) void sweep_replay_kernel(int T, const rtk
         return;
     }
     const double tau = thresholds[x];
-    const int frames = count_clamp(lg.cursor[b * 4 + 0], lg.F);
+    const int frames = lw_frames(lg, b);
     // thread 0's running values
     long long c_frames = 0, c_gt = 0, c_pred = 0, c_tp = 0, c_idsw = 0, c_tracks = 0, c_mt = 0, c_pt = 0, c_ml = 0;
     double iou_sum = 0.0;
@@ -181,8 +139,8 @@ __global__ __launch_bounds__(RTK_WAVE) void sweep_replay_kernel(int T, const rtk
     __syncthreads();
 
     for (int f = 0; f <= frames; ++f) {
-        sw_frame_t fr = {};
-        if (f < frames) fr = sw_frame(lg, b, f);
+        lw_frame_t fr = {};
+        if (f < frames) fr = lw_frame(lg, b, f);
         if (f == frames || fr.reset) {
             // ---- the clip closes ----
             int mt = 0, pt = 0, ml = 0;
@@ -216,7 +174,7 @@ __global__ __launch_bounds__(RTK_WAVE) void sweep_replay_kernel(int T, const rtk
         for (int i = t; i < fr.P; i += RTK_WAVE) {
             const size_t r = rb + fr.rec + i;
             const int lab = lg.rec_best[r];
-            const bool stays = !(rec_score[r] < tau);      // a score equal to the threshold stays
+            const bool stays = lw_stays(rec_score[r], tau);
             int j = -1;
             if (stays && lab != -1) {
                 for (int k = fr.G - 1; k >= 0; --k)
@@ -277,13 +235,9 @@ __global__ __launch_bounds__(RTK_WAVE) void sweep_replay_kernel(int T, const rtk
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static bool sw_log_ok(const rtk_score_log_t *lg) {
-    return lg && lg->F >= 1 && lg->R >= 1 && lg->cursor && lg->frame && lg->label && lg->rec_track && lg->rec_best && lg->rec_conf && lg->rec_iou;
-}
-
 extern "C" int rtk_score_track_means(int B, const rtk_score_log_t *lg, double *rec_score, int *flags, rtk_stream_t stream) {
     RTK_REQUIRE(B >= 1 && B <= 65535, "score_track_means: B=%d streams", B);
-    RTK_REQUIRE(sw_log_ok(lg), "score_track_means: null or empty log");
+    RTK_REQUIRE(lw_log_ok(lg), "score_track_means: null or empty log");
     RTK_REQUIRE(rec_score && flags, "score_track_means: null output");
     sweep_means_kernel<<<B, SW_THREADS, 0, (hipStream_t)stream>>>(*lg, rec_score, flags);
     RTK_CHECK_LAUNCH("score_track_means");
@@ -306,7 +260,7 @@ extern "C" int rtk_score_replay(int B, int T, const rtk_score_log_t *lg, const d
     const size_t lds = sw_replay_lds(T);
     RTK_REQUIRE(lds <= RTK_SCORE_LDS_LIMIT, "score_replay: T=%d track-table entries need %zu bytes of LDS per stream, the limit is %d", T, lds,
                 RTK_SCORE_LDS_LIMIT);
-    RTK_REQUIRE(sw_log_ok(lg), "score_replay: null or empty log");
+    RTK_REQUIRE(lw_log_ok(lg), "score_replay: null or empty log");
     RTK_REQUIRE(rec_score && thresholds && counters && iou_sum, "score_replay: null argument");
     (void)hipFuncSetAttribute((const void *)sweep_replay_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RTK_SCORE_LDS_LIMIT);
     sweep_replay_kernel<<<dim3(B, count), RTK_WAVE, lds, (hipStream_t)stream>>>(T, *lg, rec_score, thresholds, reached, counters, iou_sum,

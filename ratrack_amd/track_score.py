@@ -251,15 +251,22 @@ class MatchResult:
         self.__dict__.update(kw)
 
 
+def _clear_values(names, counters, iou_sum, iou_key):
+    """The CLEAR-MOT ratios of (..., len(names)) integer counts in `names` order and (...) float64 IoU sums, iou_sum / tp under `iou_key`."""
+    c = np.asarray(counters, dtype=np.float64)
+    g = lambda k: c[..., names.index(k)]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        val = dict(mota=1.0 - (g("fn") + g("fp") + g("idsw")) / g("gt"), moda=1.0 - (g("fn") + g("fp")) / g("gt"),
+                   recall=g("tp") / g("gt"), precision=g("tp") / g("pred"), mt_fraction=g("mt") / g("tracks"),
+                   pt_fraction=g("pt") / g("tracks"), ml_fraction=g("ml") / g("tracks"))
+        val[iou_key] = np.asarray(iou_sum, dtype=np.float64) / g("tp")
+    return val
+
+
 def values_from_counters(counters, iou_sum):
     """(..., 11) integer counts in COUNTERS order and (...) float64 IoU sums -> dict of float64 arrays: mota, moda, recall, precision,
     mt_fraction, pt_fraction, ml_fraction (of tracks; the counts keep the names mt, pt, ml) and mean_iou.  A ratio without a denominator is NaN."""
-    c = np.asarray(counters, dtype=np.float64)
-    g = lambda k: c[..., COUNTERS.index(k)]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return dict(mota=1.0 - (g("fn") + g("fp") + g("idsw")) / g("gt"), moda=1.0 - (g("fn") + g("fp")) / g("gt"),
-                    recall=g("tp") / g("gt"), precision=g("tp") / g("pred"), mt_fraction=g("mt") / g("tracks"),
-                    pt_fraction=g("pt") / g("tracks"), ml_fraction=g("ml") / g("tracks"), mean_iou=np.asarray(iou_sum, dtype=np.float64) / g("tp"))
+    return _clear_values(COUNTERS, counters, iou_sum, "mean_iou")
 
 
 def classify_tracks(seen, matched):
@@ -343,12 +350,7 @@ def sweep_values(counters, iou_sums, thresholds, reached, levels):
 def optimal_values(counters, iou_sum):
     """(..., 12) integer counts in OPTIMAL_COUNTERS order and (...) float64 IoU sums -> dict of float64 arrays: mota, moda, recall,
     precision, motp (iou_sum / tp) and the mt / pt / ml fractions of tracks.  A ratio without a denominator is NaN."""
-    c = np.asarray(counters, dtype=np.float64)
-    g = lambda k: c[..., OPTIMAL_COUNTERS.index(k)]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return dict(mota=1.0 - (g("fn") + g("fp") + g("idsw")) / g("gt"), moda=1.0 - (g("fn") + g("fp")) / g("gt"),
-                    recall=g("tp") / g("gt"), precision=g("tp") / g("pred"), motp=np.asarray(iou_sum, dtype=np.float64) / g("tp"),
-                    mt_fraction=g("mt") / g("tracks"), pt_fraction=g("pt") / g("tracks"), ml_fraction=g("ml") / g("tracks"))
+    return _clear_values(OPTIMAL_COUNTERS, counters, iou_sum, "motp")
 
 
 def optimal_sweep_values(counters, iou_q, iou_sums, thresholds, reached, levels):
@@ -439,6 +441,18 @@ def identity_values(counters, alpha):
     for k in ("idtp", "gt", "pred", "pairs"):
         out[k] = g(k).copy()
     out["idfn"], out["idfp"] = out["gt"] - out["idtp"], out["pred"] - out["idtp"]
+    return out
+
+
+def _download(tensors):
+    """Device tensors of 8-byte elements (int64, float64; a narrower integer is widened by the caller) -> host arrays of the same
+    shapes and dtypes, through one concatenation and one `.cpu()`: the one synchronising copy of a call."""
+    host = torch.cat([x.reshape(-1).view(torch.int64) for x in tensors]).cpu().numpy()
+    out, o = [], 0
+    for x in tensors:
+        a = host[o:o + x.numel()].copy()
+        out.append((a.view(np.float64) if x.dtype == torch.float64 else a).reshape(tuple(x.shape)))
+        o += x.numel()
     return out
 
 
@@ -634,17 +648,9 @@ class TrackScorer:
         -> dict: `per_stream` {name: (B) array} and `overall` {name: number} with the COUNTERS, `iou_sum` and the values of
         `values_from_counters`; `flags` (B).  check: raise (naming the stream) if a stream's table overflowed or its sizes were out
         of range -- nothing is truncated silently."""
-        B, T = self.B, self.T
-        parts = [self.counters.reshape(-1), self.iou_sum.view(torch.int64), self.table_used.long(), self.flags.long(),
-                 self.table_seen.reshape(-1).long(), self.table_matched.reshape(-1).long()]
-        host = torch.cat(parts).cpu().numpy()
-        nc = len(COUNTERS)
-        counters = host[:B * nc].reshape(B, nc).copy()
-        o = B * nc
-        iou_sum = host[o:o + B].copy().view(np.float64)
-        used, flags = host[o + B:o + 2 * B], host[o + 2 * B:o + 3 * B]
-        seen = host[o + 3 * B:o + 3 * B + B * T].reshape(B, T)
-        matched = host[o + 3 * B + B * T:].reshape(B, T)
+        B = self.B
+        counters, iou_sum, used, flags, seen, matched = _download([self.counters, self.iou_sum, self.table_used.long(), self.flags.long(),
+                                                                   self.table_seen.long(), self.table_matched.long()])
         if check:
             self._raise_on_flags(flags.tolist())
         for b in range(B):
@@ -659,7 +665,7 @@ class TrackScorer:
         overall = {k: int(total[i]) for i, k in enumerate(COUNTERS)}
         overall["iou_sum"] = total_iou
         overall.update({k: float(v) for k, v in values_from_counters(total, total_iou).items()})
-        return dict(per_stream=per, overall=overall, flags=flags.copy())
+        return dict(per_stream=per, overall=overall, flags=flags)
 
     def _optimal_args(self, what, min_iou):
         """The checks `sweep(matching="optimal")` and `clear_optimal` share -> min_iou as a float."""
@@ -692,41 +698,50 @@ class TrackScorer:
         if not 1 <= L <= 65534:
             raise ValueError("levels=%d outside [1, 65534]" % L)
         if matching == "optimal":
-            return self._sweep_optimal(L, check, self._optimal_args("sweep", min_iou))
+            m = self._optimal_args("sweep", min_iou)
+            pr = self._pair_block()
+            prp = ctypes.addressof(pr)
+            replay = lambda lgp, score, thr, reached, count, mask, flags, st: self._replay_optimal(lgp, prp, score, thr, reached, count, m, mask,
+                                                                                                  flags, st)
+            fl, val = self._sweep(L, check, replay, OPTIMAL_COUNTERS, optimal_sweep_values)
+            return SweepResult(flags=fl, matching="optimal", min_iou=m, **val)
         if min_iou is not None:
             raise ValueError("TrackScorer.sweep: min_iou=%r goes with matching=\"optimal\"; the greedy rule has no threshold" % (min_iou,))
-        B, dev, nc = self.B, self.counters.device, len(COUNTERS)
+        fl, val = self._sweep(L, check, self._replay_greedy, COUNTERS, sweep_values)
+        return SweepResult(flags=fl, matching="greedy", min_iou=None, frag=None, iou_q=None, frag_streams=None, iou_q_streams=None, **val)
+
+    def _sweep(self, L, check, replay, names, values):
+        """The sweep under either matching: track means, the unfiltered replay with the mask, the sort, the threshold walk and the
+        replay at the thresholds; one download.  replay(lgp, score, thr, reached, count, mask, flags, st) -> the replay's device
+        outputs, the counters (count,B,len(names)) first; values(*those on the host, thresholds, reached, L) -> the result's fields.
+        -> (flags, fields)."""
+        B, dev = self.B, self.counters.device
         lg = self._log_block()
         lgp, st = ctypes.addressof(lg), _stream()
         score = torch.zeros(B, self.R, dtype=torch.float64, device=dev)
         flags = self.flags.clone()
         _lib.call("rtk_score_track_means", B, lgp, score.data_ptr(), flags.data_ptr(), st)
-        c0 = torch.empty(1, B, nc, dtype=torch.int64, device=dev)
-        q0 = torch.empty(1, B, dtype=torch.float64, device=dev)
         mask = torch.zeros(B, self.R, dtype=torch.uint8, device=dev)
         minus = torch.full((1,), float("-inf"), dtype=torch.float64, device=dev)
-        _lib.call("rtk_score_replay", B, self.T, lgp, score.data_ptr(), minus.data_ptr(), None, 1, c0.data_ptr(), q0.data_ptr(),
-                  mask.data_ptr(), st)
+        c0 = replay(lgp, score, minus, None, 1, mask, flags, st)[0]
         ordered = torch.where(mask.bool(), score, minus).reshape(-1).sort(descending=True).values
-        n, gt = mask.sum(dtype=torch.int64).reshape(1), c0[0, :, COUNTERS.index("gt")].sum().reshape(1)
+        n, gt = mask.sum(dtype=torch.int64).reshape(1), c0[0, :, names.index("gt")].sum().reshape(1)
         thr = torch.empty(L + 1, dtype=torch.float64, device=dev)
         reached = torch.empty(1, dtype=torch.int32, device=dev)
         _lib.call("rtk_score_thresholds", ordered.data_ptr(), n.data_ptr(), gt.data_ptr(), L, thr.data_ptr(), reached.data_ptr(), st)
-        c = torch.empty(L + 1, B, nc, dtype=torch.int64, device=dev)
-        q = torch.empty(L + 1, B, dtype=torch.float64, device=dev)
-        _lib.call("rtk_score_replay", B, self.T, lgp, score.data_ptr(), thr.data_ptr(), reached.data_ptr(), L + 1, c.data_ptr(), q.data_ptr(),
-                  None, st)
-        host = torch.cat([c.reshape(-1), q.reshape(-1).view(torch.int64), thr.view(torch.int64), reached.long(), flags.long()]).cpu().numpy()
-        o = (L + 1) * B * nc
-        counters = host[:o].reshape(L + 1, B, nc).copy()
-        iou_sums = host[o:o + (L + 1) * B].copy().view(np.float64).reshape(L + 1, B)
-        o += (L + 1) * B
-        thresholds = host[o:o + L + 1].copy().view(np.float64)
-        k, fl = int(host[o + L + 1]), host[o + L + 2:].copy()
+        outs = replay(lgp, score, thr, reached, L + 1, None, flags, st)
+        *outs, thresholds, k, fl = _download(list(outs) + [thr, reached.long(), flags.long()])
         if check:
             self._raise_on_flags(fl.tolist())
-        return SweepResult(flags=fl, matching="greedy", min_iou=None, frag=None, iou_q=None, frag_streams=None, iou_q_streams=None,
-                           **sweep_values(counters, iou_sums, thresholds, k, L))
+        return fl, values(*outs, thresholds, int(k[0]), L)
+
+    def _replay_greedy(self, lgp, score, thr, reached, count, mask, flags, st):
+        B, dev = self.B, self.counters.device
+        c = torch.empty(count, B, len(COUNTERS), dtype=torch.int64, device=dev)
+        q = torch.empty(count, B, dtype=torch.float64, device=dev)
+        _lib.call("rtk_score_replay", B, self.T, lgp, score.data_ptr(), thr.data_ptr(), None if reached is None else reached.data_ptr(), count,
+                  c.data_ptr(), q.data_ptr(), None if mask is None else mask.data_ptr(), st)
+        return c, q
 
     def _replay_optimal(self, lgp, prp, score, thr, reached, count, min_iou, mask, flags, st):
         B, dev = self.B, self.counters.device
@@ -737,37 +752,16 @@ class TrackScorer:
                   count, min_iou, c.data_ptr(), iq.data_ptr(), q.data_ptr(), None if mask is None else mask.data_ptr(), flags.data_ptr(), st)
         return c, iq, q
 
-    def _sweep_optimal(self, L, check, min_iou):
-        """`sweep` under the optimal matching: track means, the unfiltered optimal replay with the mask, the sort, the existing
-        threshold walk and the optimal replay at the thresholds; one download."""
-        B, dev, nc = self.B, self.counters.device, len(OPTIMAL_COUNTERS)
-        lg, pr = self._log_block(), self._pair_block()
-        lgp, prp, st = ctypes.addressof(lg), ctypes.addressof(pr), _stream()
-        score = torch.zeros(B, self.R, dtype=torch.float64, device=dev)
-        flags = self.flags.clone()
-        _lib.call("rtk_score_track_means", B, lgp, score.data_ptr(), flags.data_ptr(), st)
-        mask = torch.zeros(B, self.R, dtype=torch.uint8, device=dev)
-        minus = torch.full((1,), float("-inf"), dtype=torch.float64, device=dev)
-        c0, _, _ = self._replay_optimal(lgp, prp, score, minus, None, 1, min_iou, mask, flags, st)
-        ordered = torch.where(mask.bool(), score, minus).reshape(-1).sort(descending=True).values
-        n, gt = mask.sum(dtype=torch.int64).reshape(1), c0[0, :, OPTIMAL_COUNTERS.index("gt")].sum().reshape(1)
-        thr = torch.empty(L + 1, dtype=torch.float64, device=dev)
-        reached = torch.empty(1, dtype=torch.int32, device=dev)
-        _lib.call("rtk_score_thresholds", ordered.data_ptr(), n.data_ptr(), gt.data_ptr(), L, thr.data_ptr(), reached.data_ptr(), st)
-        c, iq, q = self._replay_optimal(lgp, prp, score, thr, reached, L + 1, min_iou, None, flags, st)
-        host = torch.cat([c.reshape(-1), iq.reshape(-1), q.reshape(-1).view(torch.int64), thr.view(torch.int64), reached.long(),
-                          flags.long()]).cpu().numpy()
-        o = (L + 1) * B * nc
-        c12 = host[:o].reshape(L + 1, B, nc).copy()
-        iou_q = host[o:o + (L + 1) * B].reshape(L + 1, B).copy()
-        o += (L + 1) * B
-        iou_sums = host[o:o + (L + 1) * B].copy().view(np.float64).reshape(L + 1, B)
-        o += (L + 1) * B
-        thresholds = host[o:o + L + 1].copy().view(np.float64)
-        k, fl = int(host[o + L + 1]), host[o + L + 2:].copy()
-        if check:
-            self._raise_on_flags(fl.tolist())
-        return SweepResult(flags=fl, matching="optimal", min_iou=min_iou, **optimal_sweep_values(c12, iou_q, iou_sums, thresholds, k, L))
+    def _threshold_scores(self, threshold, lgp, flags, st):
+        """The prologue of a call that may filter by track score.  threshold None: (None, None), no launch.  A float or a 0-dim
+        tensor: (the threshold (1) and the track scores (B,R) on the device), one launch (rtk_score_track_means)."""
+        if threshold is None:
+            return None, None
+        dev = self.counters.device
+        thr = torch.as_tensor(threshold, dtype=torch.float64).reshape(1).to(dev)
+        score = torch.zeros(self.B, self.R, dtype=torch.float64, device=dev)
+        _lib.call("rtk_score_track_means", self.B, lgp, score.data_ptr(), flags.data_ptr(), st)
+        return thr, score
 
     def clear_optimal(self, min_iou, threshold=None, check=True):
         """The one operating point under the optimal matching (module docstring): every logged detection (threshold None, one launch)
@@ -777,22 +771,16 @@ class TrackScorer:
         iou_q, iou_sum and the ratios mota, moda, recall, precision, motp (iou_sum / tp), mt_fraction, pt_fraction, ml_fraction (NaN
         without a denominator); `flags` (B); `min_iou`, `threshold`."""
         m = self._optimal_args("clear_optimal", min_iou)
-        B, dev, nc = self.B, self.counters.device, len(OPTIMAL_COUNTERS)
+        B, dev = self.B, self.counters.device
         lg, pr = self._log_block(), self._pair_block()
         lgp, prp, st = ctypes.addressof(lg), ctypes.addressof(pr), _stream()
-        score = torch.zeros(B, self.R, dtype=torch.float64, device=dev)
         flags = self.flags.clone()
-        thr = torch.full((1,), float("-inf"), dtype=torch.float64, device=dev)
-        if threshold is not None:
-            thr = torch.as_tensor(threshold, dtype=torch.float64).reshape(1).to(dev)
-            _lib.call("rtk_score_track_means", B, lgp, score.data_ptr(), flags.data_ptr(), st)
+        thr, score = self._threshold_scores(threshold, lgp, flags, st)
+        if thr is None:          # nothing is removed: the scores are not read past the comparison with -inf
+            thr = torch.full((1,), float("-inf"), dtype=torch.float64, device=dev)
+            score = torch.zeros(B, self.R, dtype=torch.float64, device=dev)
         c, iq, q = self._replay_optimal(lgp, prp, score, thr, None, 1, m, None, flags, st)
-        host = torch.cat([c.reshape(-1), iq.reshape(-1), q.reshape(-1).view(torch.int64), thr.view(torch.int64), flags.long()]).cpu().numpy()
-        counters = host[:B * nc].reshape(B, nc).copy()
-        iou_q = host[B * nc:B * nc + B].copy()
-        iou_sum = host[B * nc + B:B * nc + 2 * B].copy().view(np.float64)
-        tau = float(host[B * nc + 2 * B:B * nc + 2 * B + 1].copy().view(np.float64)[0])
-        fl = host[B * nc + 2 * B + 1:].copy()
+        (counters,), (iou_q,), (iou_sum,), (tau,), fl = _download([c, iq, q, thr, flags.long()])
         if check:
             self._raise_on_flags(fl.tolist())
         per = {k: counters[:, i] for i, k in enumerate(OPTIMAL_COUNTERS)}
@@ -801,7 +789,7 @@ class TrackScorer:
         total_iou = float(np.cumsum(iou_sum)[-1]) if B else 0.0          # cumsum: one addition after the other, in stream order
         overall = {k: int(total[i]) for i, k in enumerate(OPTIMAL_COUNTERS)}
         overall.update(iou_q=int(iou_q.sum()), iou_sum=total_iou, **{k: float(v) for k, v in optimal_values(total, total_iou).items()})
-        return dict(per_stream=per, overall=overall, flags=fl, min_iou=m, threshold=None if threshold is None else tau)
+        return dict(per_stream=per, overall=overall, flags=fl, min_iou=m, threshold=None if threshold is None else float(tau))
 
     def hota(self, alphas=19, threshold=None, check=True):
         """HOTA, DetA, AssA and LocA over the log (module docstring; definitions in include/rtk_score.h) at `alphas` levels
@@ -815,29 +803,17 @@ class TrackScorer:
         A = int(alphas)
         if not 1 <= A <= 63:
             raise ValueError("alphas=%d outside [1, 63]" % A)
-        B, dev, nc, ns = self.B, self.counters.device, len(HOTA_COUNTERS), len(HOTA_SUMS)
+        B, dev = self.B, self.counters.device
         lg = self._log_block()
         lgp, st = ctypes.addressof(lg), _stream()
         flags = self.flags.clone()
-        score = thr = None
-        if threshold is not None:
-            thr = torch.as_tensor(threshold, dtype=torch.float64).reshape(1).to(dev)
-            score = torch.zeros(B, self.R, dtype=torch.float64, device=dev)
-            _lib.call("rtk_score_track_means", B, lgp, score.data_ptr(), flags.data_ptr(), st)
-        c = torch.empty(A, B, nc, dtype=torch.int64, device=dev)
-        q = torch.empty(A, B, ns, dtype=torch.float64, device=dev)
+        thr, score = self._threshold_scores(threshold, lgp, flags, st)
+        c = torch.empty(A, B, len(HOTA_COUNTERS), dtype=torch.int64, device=dev)
+        q = torch.empty(A, B, len(HOTA_SUMS), dtype=torch.float64, device=dev)
         _lib.call("rtk_score_hota", B, self.T, lgp, None if score is None else score.data_ptr(), None if thr is None else thr.data_ptr(), A,
                   c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
-        parts = [c.reshape(-1), q.reshape(-1).view(torch.int64), flags.long()]
-        if thr is not None:
-            parts.append(thr.view(torch.int64))
-        host = torch.cat(parts).cpu().numpy()
-        o = A * B * nc
-        counters = host[:o].reshape(A, B, nc).copy()
-        sums = host[o:o + A * B * ns].copy().view(np.float64).reshape(A, B, ns)
-        o += A * B * ns
-        fl = host[o:o + B].copy()
-        tau = None if thr is None else float(host[o + B:].copy().view(np.float64)[0])
+        counters, sums, fl, *tau = _download([c, q, flags.long()] + ([] if thr is None else [thr]))
+        tau = float(tau[0][0]) if tau else None
         if check:
             self._raise_on_flags(fl.tolist())
         return HotaResult(flags=fl, threshold=tau, **hota_values(counters, sums))
@@ -856,27 +832,17 @@ class TrackScorer:
             raise ValueError("alphas=%r must be a float or a sequence of 1 to 63 floats" % (alphas,))
         if not (np.isfinite(al) & (al > 0.0) & (al <= 1.0)).all():
             raise ValueError("alphas=%r: every level must be finite and in (0, 1]" % (alphas,))
-        A, B, dev, nc = al.shape[0], self.B, self.counters.device, len(IDENTITY_COUNTERS)
+        A, B, dev = al.shape[0], self.B, self.counters.device
         lg = self._log_block()
         lgp, st = ctypes.addressof(lg), _stream()
         flags = self.flags.clone()
-        score = thr = None
-        if threshold is not None:
-            thr = torch.as_tensor(threshold, dtype=torch.float64).reshape(1).to(dev)
-            score = torch.zeros(B, self.R, dtype=torch.float64, device=dev)
-            _lib.call("rtk_score_track_means", B, lgp, score.data_ptr(), flags.data_ptr(), st)
+        thr, score = self._threshold_scores(threshold, lgp, flags, st)
         levels = torch.from_numpy(al.copy()).to(dev)
-        c = torch.empty(A, B, nc, dtype=torch.int64, device=dev)
+        c = torch.empty(A, B, len(IDENTITY_COUNTERS), dtype=torch.int64, device=dev)
         _lib.call("rtk_score_identity", B, self.T, lgp, None if score is None else score.data_ptr(), None if thr is None else thr.data_ptr(),
                   levels.data_ptr(), A, c.data_ptr(), flags.data_ptr(), st)
-        parts = [c.reshape(-1), flags.long()]
-        if thr is not None:
-            parts.append(thr.view(torch.int64))
-        host = torch.cat(parts).cpu().numpy()
-        o = A * B * nc
-        counters = host[:o].reshape(A, B, nc).copy()
-        fl = host[o:o + B].copy()
-        tau = None if thr is None else float(host[o + B:].copy().view(np.float64)[0])
+        counters, fl, *tau = _download([c, flags.long()] + ([] if thr is None else [thr]))
+        tau = float(tau[0][0]) if tau else None
         if check:
             self._raise_on_flags(fl.tolist())
         return IdentityResult(flags=fl, threshold=tau, **identity_values(counters, al))

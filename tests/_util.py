@@ -1,8 +1,13 @@
 """Shared helpers for the parity tests (golden fixtures, deterministic weights, tolerances)."""
+import collections
 import json
 import os
+import re
+import shutil
+import subprocess
 
 import numpy as np
+import pytest
 import torch
 
 from ratrack_amd import synth
@@ -109,3 +114,31 @@ def grad_report(case, grads, prefix=""):
                          norm=float(np.sqrt((full * full).sum())), ref_norm=float(n), probe=probe,
                          ref_probe=float(case[prefix + "grad_probes"][i]), gmax=gmax))
     return rows
+
+
+# ---- what a kernel file's gfx950 code object states ------------------------------------------------------------------------------
+KernelNotes = collections.namedtuple("KernelNotes", "private lds wavefront max_threads")
+
+
+def kernel_notes(src, tmp_path):
+    """Compiles `src` for the device with the flags it is built with -> ({kernel symbol: KernelNotes}, the assembly text): the
+    .private_segment_fixed_size (scratch), .group_segment_fixed_size (static LDS), .wavefront_size and .max_flat_workgroup_size of
+    every kernel in the notes of the assembly.  Skips where there is no hipcc."""
+    from ratrack_amd import build as B
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    out = str(tmp_path / (os.path.basename(src) + ".s"))
+    cmd = [hipcc] + [f for f in B.flags_for(src) if f != "-fPIC"] + ["-I", os.path.join(ROOT, "include"), "-I", B.CSRC, "-S",
+                                                                    "--cuda-device-only", "-o", out, src]
+    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
+    asm = open(out).read()
+    notes = asm[asm.index("amdhsa.kernels"):]
+    found = {}
+    for e in re.split(r"\n\s+- \.", notes):
+        m = re.search(r"\.name:\s+(\S+)", e)
+        v = [re.search(r"\.%s:\s+(\d+)" % k, e)
+             for k in ("private_segment_fixed_size", "group_segment_fixed_size", "wavefront_size", "max_flat_workgroup_size")]
+        if m and all(v):
+            found[m.group(1)] = KernelNotes(*(int(x.group(1)) for x in v))
+    return found, asm

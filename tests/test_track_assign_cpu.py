@@ -6,13 +6,12 @@ the statement differs from mutual-best, from greedy, from an fp32 gate and from 
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import _track_assign_util as U
+from _util import kernel_notes
 from ratrack_amd import _lib, abi, build as B
 from ratrack_amd import tracker as T
 
@@ -41,30 +40,8 @@ def test_header_declares_and_library_exports_the_entry_point():
         assert "asm" not in code and "atomic" not in code.split("la_solve_dense(int R")[-1], name
 
 
-def _kernel_notes(src, tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path / (os.path.basename(src) + ".s"))
-    cmd = [hipcc] + [f for f in B.flags_for(src) if f != "-fPIC"] + ["-I", os.path.join(ROOT, "include"), "-I", B.CSRC, "-S",
-                                                                    "--cuda-device-only", "-o", out, src]
-    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    notes = asm[asm.index("amdhsa.kernels"):]
-    found = {}
-    for e in re.split(r"\n\s+- \.", notes):
-        m = re.search(r"\.name:\s+(\S+)", e)
-        p = re.search(r"\.private_segment_fixed_size:\s+(\d+)", e)
-        g = re.search(r"\.group_segment_fixed_size:\s+(\d+)", e)
-        w = re.search(r"\.wavefront_size:\s+(\d+)", e)
-        t = re.search(r"\.max_flat_workgroup_size:\s+(\d+)", e)
-        if m and p and g and w and t:
-            found[m.group(1)] = (int(p.group(1)), int(g.group(1)), int(w.group(1)), int(t.group(1)))
-    return found, asm
-
-
 def test_the_kernel_builds_for_gfx950_without_scratch_and_states_its_lds(tmp_path):
-    found, asm = _kernel_notes(os.path.join(B.CSRC, "track_assign.hip"), tmp_path)
+    found, asm = kernel_notes(os.path.join(B.CSRC, "track_assign.hip"), tmp_path)
     # one kernel, one wave, no scratch, no static LDS: all of it is dynamic and rtk_associate_optimal_lds_bytes states it
     assert len(found) == 1 and "associate_optimal_kernel" in list(found)[0] and list(found.values())[0] == (0, 0, 64, 64), found
     body = re.sub(r";[^\n]*", "", asm)

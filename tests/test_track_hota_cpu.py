@@ -7,14 +7,13 @@ import ctypes
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import _track_hota_util as H
 import _track_sweep_util as W
+from _util import kernel_notes
 from ratrack_amd import _lib, abi, build as B
 from ratrack_amd import track_score as TS
 
@@ -44,22 +43,7 @@ def test_header_declares_and_library_exports_hota():
 
 
 def test_hota_kernel_builds_for_gfx950_without_scratch(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(B.CSRC, "track_hota.hip")
-    out = str(tmp_path / "track_hota.s")
-    cmd = [hipcc] + [f for f in B.flags_for(src) if f != "-fPIC"] + ["-I", os.path.join(ROOT, "include"), "-I", B.CSRC, "-S",
-                                                                    "--cuda-device-only", "-o", out, src]
-    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    notes = asm[asm.index("amdhsa.kernels"):]
-    found = {}
-    for e in re.split(r"\n\s+- \.", notes):
-        m = re.search(r"\.name:\s+(\S+)", e)
-        p = re.search(r"\.private_segment_fixed_size:\s+(\d+)", e)
-        if m and p:
-            found[m.group(1)] = int(p.group(1))
+    found = {k: v.private for k, v in kernel_notes(os.path.join(B.CSRC, "track_hota.hip"), tmp_path)[0].items()}
     assert len(found) == 1 and [v for name, v in found.items() if "hota_kernel" in name] == [0], found
 
 

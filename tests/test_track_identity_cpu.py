@@ -7,14 +7,13 @@ import ctypes
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import _track_identity_util as I
 import _track_sweep_util as W
+from _util import kernel_notes
 from ratrack_amd import _lib, abi, build as B
 from ratrack_amd import track_score as TS
 
@@ -43,33 +42,19 @@ def test_header_declares_and_library_exports_identity():
     solver = open(os.path.join(B.CSRC, "lds_assignment.h")).read()
     for word in ("The contract.", "Exact: integers only", "Bounded:", "no floating point, no scratch, no inline assembly"):
         assert word in solver, word
-    assert "asm" not in re.sub(r"//[^\n]*", "", solver) and "asm" not in re.sub(r"//[^\n]*", "", open(os.path.join(B.CSRC, "track_identity.hip")).read())
+    assert "asm" not in re.sub(r"//[^\n]*", "", solver)
+    for name in ("track_identity.hip", "score_log_walk.h"):          # the kernel's device code lives in both
+        assert "asm" not in re.sub(r"//[^\n]*", "", open(os.path.join(B.CSRC, name)).read()), name
 
 
 def test_identity_kernel_builds_for_gfx950_without_scratch_and_states_its_lds(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(B.CSRC, "track_identity.hip")
-    out = str(tmp_path / "track_identity.s")
-    cmd = [hipcc] + [f for f in B.flags_for(src) if f != "-fPIC"] + ["-I", os.path.join(ROOT, "include"), "-I", B.CSRC, "-S",
-                                                                    "--cuda-device-only", "-o", out, src]
-    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    notes = asm[asm.index("amdhsa.kernels"):]
-    found = {}
-    for e in re.split(r"\n\s+- \.", notes):
-        m = re.search(r"\.name:\s+(\S+)", e)
-        p = re.search(r"\.private_segment_fixed_size:\s+(\d+)", e)
-        g = re.search(r"\.group_segment_fixed_size:\s+(\d+)", e)
-        if m and p and g:
-            found[m.group(1)] = (int(p.group(1)), int(g.group(1)))
+    found, _ = kernel_notes(os.path.join(B.CSRC, "track_identity.hip"), tmp_path)
     # one instance per label capacity, each "identity_kernel<capacity>": no scratch, and the LDS the host function reports
-    assert len(found) == 2 and all("identity_kernel" in name and v[0] == 0 for name, v in found.items()), found
+    assert len(found) == 2 and all("identity_kernel" in name and v.private == 0 for name, v in found.items()), found
     lds = _lib._fn("rtk_score_identity_lds_bytes")
-    small = [v[1] for name, v in found.items() if "identity_kernelILi1024E" in name]
+    small = [v.lds for name, v in found.items() if "identity_kernelILi1024E" in name]
     assert small == [lds(1024)] and lds(1024) <= 65536 and lds(1) == lds(1024), (found, lds(1024))
-    large = [v[1] for name, v in found.items() if "identity_kernelILi1024E" not in name]
+    large = [v.lds for name, v in found.items() if "identity_kernelILi1024E" not in name]
     assert large == [lds(1025)] and lds(1024) < lds(1025) <= 65536
     assert lds(100000) > 65536 and lds(0) == -1
 

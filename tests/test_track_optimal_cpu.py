@@ -8,13 +8,12 @@ import ctypes
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import _track_optimal_util as O
+from _util import kernel_notes
 from ratrack_amd import _lib, abi, build as B
 from ratrack_amd import track_score as TS
 
@@ -41,38 +40,18 @@ def test_header_declares_and_library_exports_the_pair_log_and_the_optimal_replay
     for word in ("ONE ASSIGNMENT", "THE CALLER CHOOSES", "still NOT a reproduction", "(1 << 23) + min(floor(iou * 65536), 65536)",
                  "tp * 2^23 + iou_q", "seen but unmatched in its previous seen frame", "logged whole or not at\n * all"):
         assert word in text, word
-    for name in ("track_optimal.hip", "track_score_pairs.hip"):
+    for name in ("track_optimal.hip", "score_log_walk.h", "track_score_pairs.hip"):
         assert "asm" not in re.sub(r"//[^\n]*", "", open(os.path.join(B.CSRC, name)).read()), name
 
 
-def _kernel_notes(src, tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path / (os.path.basename(src) + ".s"))
-    cmd = [hipcc] + [f for f in B.flags_for(src) if f != "-fPIC"] + ["-I", os.path.join(ROOT, "include"), "-I", B.CSRC, "-S",
-                                                                    "--cuda-device-only", "-o", out, src]
-    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    notes = asm[asm.index("amdhsa.kernels"):]
-    found = {}
-    for e in re.split(r"\n\s+- \.", notes):
-        m = re.search(r"\.name:\s+(\S+)", e)
-        p = re.search(r"\.private_segment_fixed_size:\s+(\d+)", e)
-        g = re.search(r"\.group_segment_fixed_size:\s+(\d+)", e)
-        if m and p and g:
-            found[m.group(1)] = (int(p.group(1)), int(g.group(1)))
-    return found
-
-
 def test_optimal_replay_builds_for_gfx950_without_scratch_and_states_its_lds(tmp_path):
-    found = _kernel_notes(os.path.join(B.CSRC, "track_optimal.hip"), tmp_path)
+    found, _ = kernel_notes(os.path.join(B.CSRC, "track_optimal.hip"), tmp_path)
     # one instance per track-table capacity: no scratch, and the static LDS is the figure the host function reports
-    assert len(found) == 2 and all("optimal_replay_kernel" in name and v[0] == 0 for name, v in found.items()), found
+    assert len(found) == 2 and all("optimal_replay_kernel" in name and v.private == 0 for name, v in found.items()), found
     lds = _lib._fn("rtk_score_optimal_lds_bytes")
-    small = [v[1] for name, v in found.items() if "optimal_replay_kernelILi1024E" in name]
+    small = [v.lds for name, v in found.items() if "optimal_replay_kernelILi1024E" in name]
     assert small == [lds(1024)] and lds(1024) <= 65536 and lds(1) == lds(1024), (found, lds(1024))
-    large = [v[1] for name, v in found.items() if "optimal_replay_kernelILi1024E" not in name]
+    large = [v.lds for name, v in found.items() if "optimal_replay_kernelILi1024E" not in name]
     assert large == [lds(1025)] and lds(1024) < lds(1025) <= 65536
     assert lds(100000) > 65536 and lds(0) == -1
     # the figure, from its parts (ints): IoUs of the matches | edge list | solver tables at 256 x 64 x 2048 | track table 5 T | frame rows | scalars
@@ -81,9 +60,9 @@ def test_optimal_replay_builds_for_gfx950_without_scratch_and_states_its_lds(tmp
 
 
 def test_pair_logging_kernels_build_without_scratch_and_with_no_static_lds(tmp_path):
-    found = _kernel_notes(os.path.join(B.CSRC, "track_score_pairs.hip"), tmp_path)
+    found, _ = kernel_notes(os.path.join(B.CSRC, "track_score_pairs.hip"), tmp_path)
     assert sorted(n for n in found) == sorted(n for n in found if "ts_pairs" in n) and len(found) == 2, found
-    assert all(v == (0, 0) for v in found.values()), found          # dynamic LDS only: rtk_track_score_lds_bytes / _memory_lds_bytes
+    assert all((v.private, v.lds) == (0, 0) for v in found.values()), found          # dynamic LDS only: rtk_track_score_lds_bytes / _memory_lds_bytes
 
 
 def test_entry_points_refuse_before_any_launch():

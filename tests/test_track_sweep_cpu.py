@@ -5,14 +5,13 @@ the planned sequence of tests/test_track_sweep_gpu.py holds every situation it i
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import _track_score_util as S
 import _track_sweep_util as W
+from _util import kernel_notes
 from ratrack_amd import _lib, abi, build as B
 from ratrack_amd import track_score as TS
 
@@ -40,32 +39,12 @@ def test_header_declares_and_library_exports_the_sweep():
         assert word in text, word
 
 
-def _kernel_notes(src, tmp_path):
-    """{kernel symbol: .private_segment_fixed_size} from the notes of the file's gfx950 assembly; nothing else of it is read."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path / (os.path.basename(src) + ".s"))
-    cmd = [hipcc] + [f for f in B.flags_for(src) if f != "-fPIC"] + ["-I", os.path.join(ROOT, "include"), "-I", B.CSRC, "-S",
-                                                                    "--cuda-device-only", "-o", out, src]
-    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    notes = asm[asm.index("amdhsa.kernels"):]
-    found = {}
-    for e in re.split(r"\n\s+- \.", notes):
-        m = re.search(r"\.name:\s+(\S+)", e)
-        p = re.search(r"\.private_segment_fixed_size:\s+(\d+)", e)
-        if m and p:
-            found[m.group(1)] = int(p.group(1))
-    return found
-
-
 def test_sweep_kernels_and_the_logged_wrapper_build_for_gfx950_without_scratch(tmp_path):
-    found = _kernel_notes(os.path.join(B.CSRC, "track_sweep.hip"), tmp_path)
+    found = {k: v.private for k, v in kernel_notes(os.path.join(B.CSRC, "track_sweep.hip"), tmp_path)[0].items()}
     for k in ("sweep_means_kernel", "sweep_thresholds_kernel", "sweep_replay_kernel"):
         assert [v for name, v in found.items() if k in name] == [0], (k, found)
     assert len(found) == 3, found
-    found = _kernel_notes(os.path.join(B.CSRC, "track_score.hip"), tmp_path)
+    found = {k: v.private for k, v in kernel_notes(os.path.join(B.CSRC, "track_score.hip"), tmp_path)[0].items()}
     logged = [name for name in found if "ts_logged_kernel" in name]
     assert len(logged) == 1 and found[logged[0]] == 0, found
     assert "track_score_kernel" not in logged[0] and "gt_objects_kernel" not in logged[0]
