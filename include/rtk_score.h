@@ -37,9 +37,9 @@ extern "C" {
 #define RTK_SCORE_FLAG_LOG 16        /* rtk_track_score_logged: a frame did not fit the stream's log and was not logged at all */
 #define RTK_SCORE_FLAG_SWEEP 32      /* rtk_score_track_means: more track ids in one clip than RTK_SCORE_SWEEP_TRACKS (no score written) */
 #define RTK_SCORE_FLAG_TABLE 64      /* rtk_track_score_memory: a table_count outside [num_objects, Kobj] (clamped) */
-#define RTK_SCORE_FLAG_HOTA 128      /* rtk_score_hota: a clip with more labels, track ids or pairs than its tables hold (outputs unspecified) */
-#define RTK_SCORE_FLAG_IDENTITY 256  /* rtk_score_identity: the same, of its tables */
-#define RTK_SCORE_FLAG_OPTIMAL 512   /* rtk_score_replay_optimal: a frame with more candidate pairs than RTK_SCORE_PAIR_EDGES (outputs unspecified) */
+#define RTK_SCORE_FLAG_HOTA 128      /* rtk_score_hota, rtk_score_alignment: a clip with more labels, track ids or pairs than its tables hold (outputs unspecified) */
+#define RTK_SCORE_FLAG_IDENTITY 256  /* rtk_score_identity, rtk_score_identity_pairs: the same, of its tables */
+#define RTK_SCORE_FLAG_OPTIMAL 512   /* rtk_score_replay_optimal, rtk_score_hota_optimal: a frame with more candidate pairs than RTK_SCORE_PAIR_EDGES (outputs unspecified) */
 
 /* LDS bytes of one workgroup for these sizes (host functions: no device is touched). */
 RTK_EXPORT int rtk_gt_objects_lds_bytes(int K, int N);
@@ -332,7 +332,9 @@ RTK_EXPORT int rtk_score_identity(int B, int T, const rtk_score_log_t *log, cons
  * ground-truth objects that refuses pairs below an IoU threshold, and on top of it id switches, fragmentations, MT / ML and the
  * sweep over recall levels.  This section is that matching scheme on the reference's point IoU, at a threshold THE CALLER CHOOSES
  * (there is no default: the threshold of the reference's evaluation is not known).  It is still NOT a reproduction of the reference
- * README's table, whose threshold and evaluator are not distributed; HOTA and IDF1 stay under the greedy rule.
+ * README's table, whose threshold and evaluator are not distributed.  HOTA and the identity metrics have their own section on the
+ * pair log, at the end of this file: rtk_score_hota and rtk_score_identity stay under the greedy rule, rtk_score_hota_optimal and
+ * rtk_score_identity_pairs follow TrackEval's arrangement.
  *
  * The main log keeps only each detection's best object, from which no assignment can be computed afterwards; the pair log keeps
  * every overlap.  Per frame of the main log (same frame index), for every detection i and kept object j with common > 0, in
@@ -395,6 +397,106 @@ RTK_EXPORT int rtk_score_replay_optimal(int B, int T, const rtk_score_log_t *log
                                         long long *counters /* (count,B,12) */, long long *iou_q /* (count,B) */,
                                         double *iou_sum /* (count,B) */, unsigned char *tp_mask /* NULL or (B,R) */, int *flags /* (B) */,
                                         rtk_stream_t stream);
+
+/* ---- HOTA and the identity metrics under TrackEval's matching (csrc/track_hota_optimal.hip, csrc/track_identity_pairs.hip,
+ *      csrc/lds_assignment.h, TrackScorer.hota(matching="optimal"), TrackScorer.identity(pairs="all")) ---------------------------------
+ *
+ * rtk_score_hota matches each detection to its single best object, first come first served, again at every alpha, and
+ * rtk_score_identity sees only a detection's best object.  TrackEval does neither: its HOTA matches every frame ONCE, by a Hungarian
+ * assignment over similarity x global alignment score, and thresholds the matched pairs at each alpha afterwards; its Identity counts
+ * every pair above the threshold.  This section is that arrangement over the pair log.  WHAT NOW AGREES WITH TrackEval: the
+ * arrangement of HOTA (alignment pass, one matching per frame for all alpha, the association sums) and of Identity (every pair, one
+ * global assignment).  WHAT STILL DOES NOT: the similarity is the reference's POINT IoU, not a box IoU (the reference's result files
+ * hold points: its own choice), and the frame's assignment is solved on scores truncated to 28 BITS (below).  rtk_score_hota and
+ * rtk_score_identity are unchanged.
+ *
+ * HOTA under the optimal matching.  Per stream, per clip (the frames from one reset to the next), frames in log order.
+ *   removal      the sweep's: with rec_score and a threshold t a detection whose track score is < t is removed before anything else,
+ *                the alignment pass included (TrackEval filters the tracker data first).
+ *   valid pair   a logged pair (i, j, c) of a frame whose key and indices describe the frame, with c > 0, whose detection i remains,
+ *                and with den = |i| + |j| - c > 0.  Its similarity is s = (double)c / (double)den and sbar = min(s, 1.0): coincident
+ *                points count once per PAIR, so the point IoU can exceed 1 -- the sums below and the weights take sbar, the alpha test
+ *                and LocA take s unclamped, as rtk_score_hota takes rec_iou.
+ *   alignment    per clip.  Every sum is float64, starts from 0.0 and adds one term after the other, no FMA.  Per frame r_i = the sum
+ *                of sbar over detection i's valid pairs in pair-log order (j ascending) and k_j = the sum of sbar over object j's
+ *                valid pairs in pair-log order (i ascending); per valid pair q = sbar / ((r_i + k_j) - sbar) (TrackEval's sim_iou).
+ *                pmc[g,t] += q for g the label id of object j and t the track id of detection i: frames in order, then pairs in
+ *                pair-log order.  cg[g] the frames of the clip whose kept labels contain g, ct[t] the remaining detections of the
+ *                clip with track id t.  At the clip's close A[g,t] = pmc / ((double)(cg + ct) - pmc).
+ *   matching     per frame, ONE MATCHING FOR ALL ALPHA: la_solve (csrc/lds_assignment.h) with rows = detections, columns = kept
+ *                objects, one edge per valid pair of weight max(1, (int)floor(min(A[g,t] * sbar, 1.0) * 2^28)).  The matching is the
+ *                solver's documented one (rows enter in order, ties go to the smaller column).  This is the one departure from
+ *                TrackEval's arrangement: the float64 score is truncated to 28 bits so that the optimum is an integer, and the
+ *                max(1, ...) keeps a positive overlap from vanishing; the float score of the optimum found therefore lies within
+ *                min(P, G) * 2^-28 of the untruncated optimum -- that bound follows from the truncation, it is not measured.
+ *   per level    alpha_a = (double)a / (double)(A + 1) as in rtk_score_hota.  A matched pair is a true positive iff s >= alpha
+ *                (float64 >=: an IoU of 3/5 counts at 12/20).  tp += 1; loc += s, added in kept-object order within the frame,
+ *                frames in order; n_a[g,t] += 1.  gt = sum cg and pred = sum ct.
+ *   clip close   the clip's (g,t) with n_a > 0 IN ORDER OF FIRST APPEARANCE AMONG THE VALID PAIRS (frame order, then pair-log order):
+ *                ass += N / (double)(cg + ct - n), ass_re += N / (double)cg, ass_pr += N / (double)ct with N = (double)(n*n) from the
+ *                integer product, as rtk_score_hota adds them.  pairs = the number of those (g,t); frames and clips as there; clips
+ *                still open are closed at the end.
+ * Counters, sums and the host arithmetic are rtk_score_hota's (RTK_SCORE_HOTA_COUNTERS, RTK_SCORE_HOTA_SUMS, hota_values).
+ *
+ * Two launches.  rtk_score_alignment, one workgroup per stream, walks the log with a label table, a track table and the
+ * insertion-ordered list of the clip's potential (g,t) -- those with a valid pair -- and walks every clip a second time at its close.
+ * It leaves three tables, so that the second launch needs neither a label table nor a track table:
+ *   pair_a       (B,Q) float64, aligned with pair_key: A[g,t] of every logged pair (0 where the pair is not valid);
+ *   pair_index   (B,Q) int32, aligned with pair_key: the index of the pair's (g,t) in the stream's table of clip-pairs -- the clips'
+ *                potential pairs one clip after the other, each clip's in order of first appearance -- or -1: removed or not valid;
+ *   clip_cg, clip_ct   (B,Q) int32: cg and ct of every clip-pair (a clip-pair has a valid logged pair, so Q bounds their number).
+ * rtk_score_hota_optimal, grid (stream, alpha index), then solves every frame and folds the sums.  Every level re-solves the same
+ * assignment: the kernel is latency bound and the grid fills the device with it. */
+
+/* Most potential (label id, track id) pairs of one clip of one stream in rtk_score_alignment: the list with its float64 sums and its
+ * lookup take 24 bytes each, which next to a 1024-entry label table and the track table leaves room for these in RTK_SCORE_LDS_LIMIT
+ * (62 496 bytes in all).  rtk_score_hota_optimal counts per clip-pair in the same number of words. */
+#define RTK_SCORE_ALIGN_PAIRS 1024
+
+/* LDS bytes of one workgroup of rtk_score_alignment for T label ids per clip (a host function: no device is touched); -1 for a T below
+ * 1.  Built for two label capacities, 1024 and the largest that fits RTK_SCORE_LDS_LIMIT (1404); a T takes the smaller one that holds
+ * it: this is that instance's figure, or for a larger T what its tables would need. */
+RTK_EXPORT int rtk_score_alignment_lds_bytes(int T);
+
+/* One workgroup per stream.  T bounds the label ids of one clip (rtk_track_score's T; a T whose tables do not fit RTK_SCORE_LDS_LIMIT is
+ * refused), RTK_SCORE_SWEEP_TRACKS its track ids and RTK_SCORE_ALIGN_PAIRS its potential pairs.  A clip of stream b beyond one of the
+ * three raises RTK_SCORE_FLAG_HOTA in flags[b] (or-ed in; nothing else of flags is touched): that stream's outputs are then
+ * unspecified but written, the other streams are unaffected.  The logs are walked with rtk_score_replay_optimal's clamps, so a foreign
+ * buffer is never read out of bounds.  Reads the logs, rec_score and threshold; writes its four tables -- for every logged pair of
+ * every logged frame, and for every clip-pair -- and flags. */
+RTK_EXPORT int rtk_score_alignment(int B, int T, const rtk_score_log_t *log, const rtk_score_pairs_t *pairs,
+                                   const double *rec_score /* (B,R) or NULL */, const double *threshold /* device scalar, or NULL */,
+                                   double *pair_a /* (B,Q) */, int *pair_index /* (B,Q) */, int *clip_cg /* (B,Q) */, int *clip_ct /* (B,Q) */,
+                                   int *flags /* (B) */, rtk_stream_t stream);
+
+/* Grid (stream, alpha index), one wave each: counters (alphas,B,6) and sums (alphas,B,4) of level a = index + 1 of `alphas` levels
+ * (1..63), in rtk_score_hota's layouts.  rec_score and threshold must be those rtk_score_alignment was given.  A pair whose index does
+ * not belong to its clip is skipped, so foreign tables are never read out of bounds.  A frame of stream b with more valid pairs than
+ * RTK_SCORE_PAIR_EDGES raises RTK_SCORE_FLAG_OPTIMAL in flags[b] (or-ed in): that stream's outputs are then unspecified but written, the
+ * other streams are unaffected.  Static LDS: 44 068 bytes.  Reads the logs and the four tables and writes only its three outputs. */
+RTK_EXPORT int rtk_score_hota_optimal(int B, const rtk_score_log_t *log, const rtk_score_pairs_t *pairs,
+                                      const double *rec_score /* (B,R) or NULL */, const double *threshold /* device scalar, or NULL */,
+                                      int alphas, const double *pair_a, const int *pair_index, const int *clip_cg, const int *clip_ct,
+                                      long long *counters /* (alphas,B,6) */, double *sums /* (alphas,B,4) */, int *flags /* (B) */,
+                                      rtk_stream_t stream);
+
+/* Identity over every pair.  rtk_score_identity with one change, in what a frame adds: n[g,t] is the number of frames of the clip in
+ * which SOME REMAINING DETECTION with track id t has a VALID PAIR (above) with an object of label g and s >= alpha (float64 >=, s
+ * unclamped).  A frame adds at most 1 to a pair; there is no best-object restriction, so a detection that overlaps two objects above
+ * alpha counts for both, as TrackEval counts every pair above the threshold.  Everything after that is rtk_score_identity's: the
+ * per-clip maximum-weight one-to-one matching by la_solve, gt, pred, the counters (RTK_SCORE_ID_COUNTERS; pairs = the distinct (g,t)
+ * with n > 0), the limits and RTK_SCORE_FLAG_IDENTITY, and the host arithmetic (identity_values). */
+
+/* LDS bytes of one workgroup of rtk_score_identity_pairs for T label ids per clip: rtk_score_identity_lds_bytes' rules and figures (the
+ * words the pair walk adds lie where the solver's tables are larger). */
+RTK_EXPORT int rtk_score_identity_pairs_lds_bytes(int T);
+
+/* Grid (stream, level index): rtk_score_identity's arguments plus the pair log, which is walked with rtk_score_replay_optimal's
+ * clamps.  Reads the logs, rec_score, threshold and alphas and writes only counters and flags. */
+RTK_EXPORT int rtk_score_identity_pairs(int B, int T, const rtk_score_log_t *log, const rtk_score_pairs_t *pairs,
+                                        const double *rec_score /* (B,R) or NULL */, const double *threshold /* device scalar, or NULL */,
+                                        const double *alphas /* device, (count) */, int count, long long *counters /* (count,B,6) */,
+                                        int *flags /* (B) */, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -232,6 +232,11 @@ SIGNATURES = {
     "rtk_track_score_pairs": [_p, _p, _p, _p, _p, _p, _p],
     "rtk_score_optimal_lds_bytes": [_i],
     "rtk_score_replay_optimal": [_i, _i, _p, _p, _p, _p, _p, _i, _d, _p, _p, _p, _p, _p, _p],
+    "rtk_score_alignment_lds_bytes": [_i],
+    "rtk_score_alignment": [_i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "rtk_score_hota_optimal": [_i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "rtk_score_identity_pairs_lds_bytes": [_i],
+    "rtk_score_identity_pairs": [_i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p],
     # ---- include/rtk_train.h
     "rtk_bn_train_stats": [_i] * 5 + [_p] * 3 + [_p],
     "rtk_bn_relu_fwd": [_i] * 5 + [_p, _p, _i, _p, _p],

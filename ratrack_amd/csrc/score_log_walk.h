@@ -1,6 +1,6 @@
 // score_log_walk.h -- what a kernel needs to walk the scorer's per-frame log (rtk_score_log_t, include/rtk_score.h), stated once:
-// track_sweep.hip, track_hota.hip, track_identity.hip and track_optimal.hip replay the log with it, and a new replay kernel
-// includes it and restates none of it.  Everything here is inlined into its caller, and the kernels' code is what it was when each
+// track_sweep.hip, track_hota.hip, track_identity.hip, track_optimal.hip, track_hota_optimal.hip and track_identity_pairs.hip replay
+// the log with it, and a new replay kernel includes it and restates none of it.  Everything here is inlined into its caller, and the kernels' code is what it was when each
 // file carried these lines itself.
 //
 //   lw_frame / lw_pair_frame   a frame slot of the log (and of the pair log), clamped to what the stream's log can hold
@@ -8,7 +8,8 @@
 //   lw_hash, LW_EMPTY, LW_SLOTS, lw_track_slot<INSERT>   the per-clip track table: open addressing, slots claimed by CAS
 //   lw_pair_find / lw_pair_append <PSLOTS>               the (label entry, track slot) pair list with its lookup
 //   lw_stays                   whether a detection remains at a threshold
-//   lw_log_ok                  the host's check of a log argument
+//   lw_valid_pair, LW_REMOVED  a logged pair as a valid pair of its frame, with its similarity
+//   lw_log_ok / lw_pairs_ok    the host's check of a log / pair-log argument
 //
 // Three short loops stay in the kernels: a label id's entry in the label table, the first kept object with a label id, and the
 // MT / PT / ML classification of a closing clip.  As functions they were inlined with the loop's exit behind its body where the
@@ -100,7 +101,30 @@ __device__ __forceinline__ void lw_pair_append(int *ptab, int *pkey, int *pn, in
 // whether a detection of this track score remains at threshold tau: a score equal to the threshold stays
 __device__ __forceinline__ bool lw_stays(double score, double tau) { return !(score < tau); }
 
+#define LW_REMOVED (-2)      // a detection's row word where its track score is below the threshold (any other value: it remains)
+
+// a logged pair of frame `fr` as a VALID pair (include/rtk_score.h, "HOTA under the optimal matching"): its detection, its kept object
+// and its similarity (double)c / (double)(|i| + |j| - c), unclamped -- or false: the pair does not describe its frame, its detection
+// was removed (rrow[i] == LW_REMOVED), or there is no overlap (c <= 0, or a denominator that is not positive: coincident points count
+// once per PAIR, so c may exceed a size)
+__device__ __forceinline__ bool lw_valid_pair(const rtk_score_pairs_t &pr, const lw_pair_frame_t &fr, size_t rb, size_t qb, int p, const int *rrow,
+                                              int *row, int *col, double *s) {
+    const int key = pr.pair_key[qb + fr.pair + p], c = pr.pair_common[qb + fr.pair + p];
+    const int i = key >> 8, j = key & 255;
+    if (key < 0 || i >= fr.P || j >= fr.G || c <= 0 || rrow[i] == LW_REMOVED) return false;
+    const int si = pr.rec_size[rb + fr.rec + i], sj = pr.label_size[rb + fr.lab + j];
+    const long long den = (long long)si + (long long)sj - (long long)c;
+    if (den <= 0) return false;
+    *row = i; *col = j; *s = (double)c / (double)den;
+    return true;
+}
+
 // host side: a log argument with every table present
 static inline bool lw_log_ok(const rtk_score_log_t *lg) {
     return lg && lg->F >= 1 && lg->R >= 1 && lg->cursor && lg->frame && lg->label && lg->rec_track && lg->rec_best && lg->rec_conf && lg->rec_iou;
+}
+
+// host side: a pair-log argument with every table present
+static inline bool lw_pairs_ok(const rtk_score_pairs_t *pr) {
+    return pr && pr->Q >= 1 && pr->cursor && pr->frame_pair && pr->pair_key && pr->pair_common && pr->rec_size && pr->label_size;
 }

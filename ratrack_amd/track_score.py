@@ -107,8 +107,22 @@ an object matched again after a frame in which it was seen but unmatched.  tp, f
 are optimal the solver's documented choice (rows in order, ties to the smaller column) is taken.  `min_iou` has no default: the
 threshold of the reference's evaluation is not known.  THIS IS THE KITTI / AB3DMOT MATCHING SCHEME ON THE REFERENCE'S POINT IoU AT A
 THRESHOLD THE CALLER CHOOSES; it is still not a reproduction of the reference README's numbers, whose threshold and evaluator are not
-distributed.  HOTA and IDF1 stay under the greedy rule.  The greedy path is untouched: without `sweep_pairs` the scorer issues the
-launches it always issued.
+distributed.  The greedy path is untouched: without `sweep_pairs` the scorer issues the launches it always issued.
+
+HOTA and Identity under TrackEval's matching.  With the pair log,
+
+    ho  = scorer.hota(matching="optimal")           # HotaResult, .matching == "optimal"
+    idn = scorer.identity(pairs="all")              # IdentityResult, .pair_mode == "all"
+
+follow TrackEval's arrangement (definitions in include/rtk_score.h, at the end).  HOTA: per clip an alignment pass gives every (label,
+track) its global alignment score A -- a Jaccard of the pair's accumulated normalised overlap --, every frame is matched ONCE by an
+exact assignment over similarity x A (csrc/lds_assignment.h, the float64 score truncated to 28 bits so that the optimum is an
+integer), and the matched pairs are thresholded at each alpha afterwards; A is what makes HOTA prefer the track that follows an object
+through the clip over a one-frame intruder with a slightly larger IoU.  Identity: every (detection, object) pair above the level
+counts, not only a detection's best object.  `threshold=` removes detections before anything else, the alignment pass included.  WHAT
+NOW AGREES WITH TrackEval is the arrangement of both metrics; WHAT STILL DOES NOT is the similarity -- the reference's point IoU in
+place of a box IoU, because its result files hold points -- and the 28-bit weights.  The defaults (`matching="greedy"`,
+`pairs="best"`) are the calls above with their launches and bits.
 
 Nothing here synchronises with the device except `GtObjects.check()`, `TrackScorer.check()`, `TrackScorer.result()`,
 `TrackScorer.sweep()`, `TrackScorer.hota()`, `TrackScorer.identity()` and `TrackScorer.clear_optimal()`.
@@ -141,6 +155,7 @@ IDENTITY_PAIRS = 1024                  # RTK_SCORE_ID_PAIRS
 FLAG_OPTIMAL = 512                     # RTK_SCORE_FLAG_OPTIMAL
 OPTIMAL_COUNTERS = ("frames", "gt", "pred", "tp", "fp", "fn", "idsw", "frag", "tracks", "mt", "pt", "ml")
 PAIR_EDGES = 2048                      # RTK_SCORE_PAIR_EDGES
+ALIGN_PAIRS = 1024                     # RTK_SCORE_ALIGN_PAIRS
 
 
 # ---- what fits -------------------------------------------------------------------------------------------------------------
@@ -377,7 +392,7 @@ class HotaResult:
     detpr, assa, assre, asspr, loca, hota_alpha (NaN where the denominator is 0).  Scalars, each the sum over the levels of the
     non-NaN terms divided by A: hota, deta_mean, assa_mean, detre_mean, detpr_mean, assre_mean, asspr_mean, loca_mean.  `counters`
     (A,B,6) int64 in HOTA_COUNTERS order and `sums` (A,B,4) float64 in HOTA_SUMS order per stream; `flags` (B); `threshold` (None
-    or the float the detections were filtered with)."""
+    or the float the detections were filtered with); `matching` "greedy" or "optimal"."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -418,7 +433,8 @@ class IdentityResult:
     """What `TrackScorer.identity` returns (host values; definitions in include/rtk_score.h).  `alpha` (A) float64, the levels as
     given.  Per-level arrays of length A, pooled over the streams: idtp, idfn, idfp, gt, pred, pairs (integers) and idf1, idr, idp
     (NaN where the denominator is 0).  `counters` (A,B,6) int64 in IDENTITY_COUNTERS order per stream; `flags` (B); `threshold` (None
-    or the float the detections were filtered with)."""
+    or the float the detections were filtered with); `pair_mode` "best" or "all": what `identity(pairs=...)` was given (the field
+    `pairs` is the count)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -791,40 +807,69 @@ class TrackScorer:
         overall.update(iou_q=int(iou_q.sum()), iou_sum=total_iou, **{k: float(v) for k, v in optimal_values(total, total_iou).items()})
         return dict(per_stream=per, overall=overall, flags=fl, min_iou=m, threshold=None if threshold is None else float(tau))
 
-    def hota(self, alphas=19, threshold=None, check=True):
+    def _pair_log_args(self, what, keyword, value, choices):
+        """The checks `hota(matching=...)` and `identity(pairs=...)` share: the keyword's value, and the pair log for the second choice."""
+        if value not in choices:
+            raise ValueError("TrackScorer.%s: %s=%r is neither \"%s\" nor \"%s\"" % (what, keyword, value, choices[0], choices[1]))
+        if value == choices[1] and not self.pairs:
+            raise RuntimeError("TrackScorer.%s: the optimal matching needs the pair log (give sweep_pairs)" % what)
+
+    def hota(self, alphas=19, threshold=None, check=True, matching="greedy"):
         """HOTA, DetA, AssA and LocA over the log (module docstring; definitions in include/rtk_score.h) at `alphas` levels
         a / (alphas + 1).  threshold None: every logged detection counts, one launch.  A float or a 0-dim tensor (for instance
         `sweep().best["threshold"]`): the detections whose track score is below it are removed as the sweep removes them, two
         launches (track scores, then HOTA).  Then one download.  The running state and the log are only read: scoring may go on.
         check: raise (naming the stream) on any sticky flag and on a clip that overflowed HOTA's tables; check=False returns the
-        other streams' numbers (`flags` tells which to leave out).  -> HotaResult."""
+        other streams' numbers (`flags` tells which to leave out).  matching "greedy": `update`'s rule at every level, today's call.
+        "optimal": TrackEval's arrangement over the pair log (sweep_pairs) -- the alignment pass, then one exact assignment per frame
+        for all levels (module docstring) --, one launch more; a clip beyond the alignment pass's tables raises FLAG_HOTA, a frame with
+        more than PAIR_EDGES valid pairs FLAG_OPTIMAL.  -> HotaResult."""
+        self._pair_log_args("hota", "matching", matching, ("greedy", "optimal"))
         if not self.logging:
             raise RuntimeError("TrackScorer.hota: the scorer keeps no log (give sweep_frames and sweep_records)")
         A = int(alphas)
         if not 1 <= A <= 63:
             raise ValueError("alphas=%d outside [1, 63]" % A)
         B, dev = self.B, self.counters.device
+        if matching == "optimal":
+            need = _lib._fn("rtk_score_alignment_lds_bytes")(self.T)
+            if need < 0 or need > LDS_LIMIT:
+                raise ValueError("TrackScorer.hota: max_gt_tracks=%d needs %d bytes of LDS per stream for the alignment pass, the limit is %d"
+                                 % (self.T, need, LDS_LIMIT))
         lg = self._log_block()
         lgp, st = ctypes.addressof(lg), _stream()
         flags = self.flags.clone()
         thr, score = self._threshold_scores(threshold, lgp, flags, st)
         c = torch.empty(A, B, len(HOTA_COUNTERS), dtype=torch.int64, device=dev)
         q = torch.empty(A, B, len(HOTA_SUMS), dtype=torch.float64, device=dev)
-        _lib.call("rtk_score_hota", B, self.T, lgp, None if score is None else score.data_ptr(), None if thr is None else thr.data_ptr(), A,
-                  c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
+        sp, tp = None if score is None else score.data_ptr(), None if thr is None else thr.data_ptr()
+        if matching == "optimal":
+            pr = self._pair_block()
+            prp = ctypes.addressof(pr)
+            pair_a = torch.empty(B, self.Q, dtype=torch.float64, device=dev)
+            pair_index, clip_cg, clip_ct = (torch.empty(B, self.Q, dtype=torch.int32, device=dev) for _ in range(3))
+            _lib.call("rtk_score_alignment", B, self.T, lgp, prp, sp, tp, pair_a.data_ptr(), pair_index.data_ptr(), clip_cg.data_ptr(),
+                      clip_ct.data_ptr(), flags.data_ptr(), st)
+            _lib.call("rtk_score_hota_optimal", B, lgp, prp, sp, tp, A, pair_a.data_ptr(), pair_index.data_ptr(), clip_cg.data_ptr(),
+                      clip_ct.data_ptr(), c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
+        else:
+            _lib.call("rtk_score_hota", B, self.T, lgp, sp, tp, A, c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
         counters, sums, fl, *tau = _download([c, q, flags.long()] + ([] if thr is None else [thr]))
         tau = float(tau[0][0]) if tau else None
         if check:
             self._raise_on_flags(fl.tolist())
-        return HotaResult(flags=fl, threshold=tau, **hota_values(counters, sums))
+        return HotaResult(flags=fl, threshold=tau, matching=matching, **hota_values(counters, sums))
 
-    def identity(self, alphas=(0.5,), threshold=None, check=True):
+    def identity(self, alphas=(0.5,), threshold=None, check=True, pairs="best"):
         """IDF1, IDP and IDR over the log (module docstring; definitions in include/rtk_score.h).  alphas: a float or a sequence of
         1..63 floats, each finite and in (0, 1]: the IoU levels.  threshold as in `hota`: None, one launch; a float or a 0-dim
         tensor, the detections whose track score is below it are removed, two launches (track scores, then the walk).  Then one
         download.  The running state and the log are only read: scoring may go on.  check: raise (naming the stream) on any sticky
         flag and on a clip that overflowed the tables; check=False returns the other streams' numbers (`flags` tells which to leave
-        out).  -> IdentityResult."""
+        out).  pairs "best": a detection counts for its best object only, today's call.  "all": every (detection, object) pair of the
+        pair log (sweep_pairs) at or above the level counts, as TrackEval counts them (module docstring); the same number of
+        launches.  -> IdentityResult."""
+        self._pair_log_args("identity", "pairs", pairs, ("best", "all"))
         if not self.logging:
             raise RuntimeError("TrackScorer.identity: the scorer keeps no log (give sweep_frames and sweep_records)")
         al = np.atleast_1d(np.asarray(alphas, dtype=np.float64))
@@ -839,10 +884,14 @@ class TrackScorer:
         thr, score = self._threshold_scores(threshold, lgp, flags, st)
         levels = torch.from_numpy(al.copy()).to(dev)
         c = torch.empty(A, B, len(IDENTITY_COUNTERS), dtype=torch.int64, device=dev)
-        _lib.call("rtk_score_identity", B, self.T, lgp, None if score is None else score.data_ptr(), None if thr is None else thr.data_ptr(),
-                  levels.data_ptr(), A, c.data_ptr(), flags.data_ptr(), st)
+        sp, tp = None if score is None else score.data_ptr(), None if thr is None else thr.data_ptr()
+        if pairs == "all":
+            pr = self._pair_block()
+            _lib.call("rtk_score_identity_pairs", B, self.T, lgp, ctypes.addressof(pr), sp, tp, levels.data_ptr(), A, c.data_ptr(), flags.data_ptr(), st)
+        else:
+            _lib.call("rtk_score_identity", B, self.T, lgp, sp, tp, levels.data_ptr(), A, c.data_ptr(), flags.data_ptr(), st)
         counters, fl, *tau = _download([c, flags.long()] + ([] if thr is None else [thr]))
         tau = float(tau[0][0]) if tau else None
         if check:
             self._raise_on_flags(fl.tolist())
-        return IdentityResult(flags=fl, threshold=tau, **identity_values(counters, al))
+        return IdentityResult(flags=fl, threshold=tau, pair_mode=pairs, **identity_values(counters, al))
