@@ -498,6 +498,77 @@ RTK_EXPORT int rtk_score_identity_pairs(int B, int T, const rtk_score_log_t *log
                                         const double *alphas /* device, (count) */, int count, long long *counters /* (count,B,6) */,
                                         int *flags /* (B) */, rtk_stream_t stream);
 
+/* ---- TrackEval's centre-distance similarity on the pair log (csrc/track_score_centre.hip, csrc/track_replay_sim.hip,
+ *      TrackScorer(similarity="centre")) ----------------------------------------------------------------------------------------------
+ *
+ * The two sections above say that what still does not agree with TrackEval is the similarity: a point IoU where TrackEval has a box IoU.
+ * A box IoU will never be available here -- the detections are point clusters without boxes -- but TrackEval has a second similarity
+ * for detections that are positions, _calculate_euclidean_similarity: sim = max(0, 1 - |a - b| / zero_distance), zero_distance = 2.0 by
+ * default.  This section writes the pair log under that similarity and replays it with the four kernels above, unchanged in every other
+ * respect.  The point IoU is harsh on radar clusters of two to five points (one missed point halves it); this one asks whether the
+ * detection sits on its object.  DEPARTURES FROM TrackEval AFTER THIS: the 28-bit assignment weights, and the positions, which are point
+ * centroids rather than label-box centres.
+ *
+ * Per active stream b and frame, with n the clamped n_valid, P detections and G kept objects, as in rtk_track_score.
+ *   centre       of detection i: over the columns p < n with obj[b][p] == i, in ascending p, three float64 sums sx += (double)x_p, sy,
+ *                sz, each from 0.0; c_i = (sx / m, sy / m, sz / m) with m the (double) number of such columns (the row's rec_size).  A
+ *                detection with m == 0 has no pairs.  This is the rule rtk_gt_objects states for its own centres.
+ *   position     of kept object j: gt_centre[b][j][0..2], float64 -- the tensor rtk_gt_objects writes as `centre`, in the kept order of
+ *                gt_label_id: the mean of the points of the object's own box.  A merged rider does not move it.
+ *   similarity   dx = c_i.x - g_j.x, dy, dz likewise; d2 = (dx * dx + dy * dy) + dz * dz; d = sqrt(d2); s = 1.0 - d / zero_distance.  All
+ *                float64, every operation rounded on its own, no contraction.  (The device's double sqrt is the compiler's expansion;
+ *                DESIGN section 4.9 has what was measured of it.)
+ *   logging      the pair (i, j) is logged iff s > 0.0; a NaN is not logged.  The common point count does not matter: a pair with
+ *                common == 0 and d < zero_distance is logged, a pair with common points whose centres are zero_distance apart is not.
+ *   the log      pairs in (i, then j) order; pair_key = i << 8 | j as above; pair_common the pair's `common` count, which may now be 0;
+ *                pair_sim (B,Q) float64, aligned with pair_key, is s.  rec_size, label_size, frame_pair and cursor as above.  A frame is
+ *                logged whole or not at all, with the fit rule and RTK_SCORE_FLAG_LOG of rtk_track_score_pairs.
+ *   replays      a logged pair is VALID iff its key describes its frame, its detection remains, and s = pair_sim[q] > 0.0.  pair_common
+ *                and the sizes are not read.  Everything else in the replay sections above holds as written with "IoU" read as s:
+ *                candidates s >= min_iou; weight (1 << 23) + min(floor(s * 65536), 65536); HOTA's sbar = min(s, 1.0), sim_iou, the
+ *                alignment score and the 28-bit weights; Identity s >= alpha.
+ *
+ * rtk_score_pairs_t keeps its seven fields (its layout is pinned); the similarity travels beside it as one more argument, and a log has
+ * ONE similarity: a block written by rtk_track_score_pairs_centre goes to the *_sim replays with its pair_sim, a block written by
+ * rtk_track_score_pairs to the plain ones, which launch the kernels they always launched.  (Fed to the plain replays, a centre log would be
+ * read as point IoUs of its integers: the caller keeps the two apart, as TrackScorer does by building one scorer per similarity.) */
+
+/* rtk_track_score_pairs, bit for bit -- every counter, state tensor, output and tensor of the main log -- in the same single launch,
+ * with the pair log written by the rules above.  Every word has one writer (detection i's thread forms its centre in registers and
+ * writes row i's pairs behind the ordered prefix of the rows' pair counts), plain stores, no floating-point atomics: the same bits on
+ * every run.  LDS: rtk_track_score_centre_lds_bytes -- the figure of rtk_track_score_lds_bytes / rtk_track_score_memory_lds_bytes rounded
+ * up to 8 bytes, plus 24 K + 16: the kept objects' positions, zero_distance and the stream's pair_sim address are staged there at the
+ * start, so that the three arguments are not carried in scalar registers through the body (with them carried, the compiler reserved a
+ * private segment).  A column's detection index rides in the unused fourth word of its coordinates.  Refuses a NULL pair_sim, a NULL
+ * gt_centre and a zero_distance that is not finite and > 0. */
+RTK_EXPORT int rtk_track_score_centre_lds_bytes(int Kobj, int K, int N, int memory /* 0: no track memory */);
+RTK_EXPORT int rtk_track_score_pairs_centre(const rtk_track_score_in_t *in, const rtk_track_score_state_t *state, const rtk_track_score_out_t *out,
+                                            const rtk_score_log_t *log, const rtk_score_memory_t *mem /* NULL: no track memory */,
+                                            const rtk_score_pairs_t *pairs, double *pair_sim /* (B,Q) */, const double *gt_centre /* (B,K,3) */,
+                                            double zero_distance, rtk_stream_t stream);
+
+/* The four replays on a log that carries its similarity: the arguments, grids, limits, flags, outputs and static LDS figures
+ * (rtk_score_optimal_lds_bytes, rtk_score_alignment_lds_bytes, 44 068 bytes, rtk_score_identity_pairs_lds_bytes) of the entry points
+ * without _sim, plus pair_sim (B,Q), which must not be NULL.  One wave of 64 threads per workgroup, kernels with names of their own. */
+RTK_EXPORT int rtk_score_replay_optimal_sim(int B, int T, const rtk_score_log_t *log, const rtk_score_pairs_t *pairs, const double *pair_sim,
+                                            const double *rec_score, const double *thresholds, const int *reached, int count, double min_iou,
+                                            long long *counters /* (count,B,12) */, long long *iou_q /* (count,B) */,
+                                            double *iou_sum /* (count,B) */, unsigned char *tp_mask /* NULL or (B,R) */, int *flags /* (B) */,
+                                            rtk_stream_t stream);
+RTK_EXPORT int rtk_score_alignment_sim(int B, int T, const rtk_score_log_t *log, const rtk_score_pairs_t *pairs, const double *pair_sim,
+                                       const double *rec_score /* (B,R) or NULL */, const double *threshold /* device scalar, or NULL */,
+                                       double *pair_a /* (B,Q) */, int *pair_index /* (B,Q) */, int *clip_cg /* (B,Q) */, int *clip_ct /* (B,Q) */,
+                                       int *flags /* (B) */, rtk_stream_t stream);
+RTK_EXPORT int rtk_score_hota_optimal_sim(int B, const rtk_score_log_t *log, const rtk_score_pairs_t *pairs, const double *pair_sim,
+                                          const double *rec_score /* (B,R) or NULL */, const double *threshold /* device scalar, or NULL */,
+                                          int alphas, const double *pair_a, const int *pair_index, const int *clip_cg, const int *clip_ct,
+                                          long long *counters /* (alphas,B,6) */, double *sums /* (alphas,B,4) */, int *flags /* (B) */,
+                                          rtk_stream_t stream);
+RTK_EXPORT int rtk_score_identity_pairs_sim(int B, int T, const rtk_score_log_t *log, const rtk_score_pairs_t *pairs, const double *pair_sim,
+                                            const double *rec_score /* (B,R) or NULL */, const double *threshold /* device scalar, or NULL */,
+                                            const double *alphas /* device, (count) */, int count, long long *counters /* (count,B,6) */,
+                                            int *flags /* (B) */, rtk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,12 @@ SIGNATURES = {
     "rtk_score_hota_optimal": [_i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],
     "rtk_score_identity_pairs_lds_bytes": [_i],
     "rtk_score_identity_pairs": [_i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p],
+    "rtk_track_score_centre_lds_bytes": [_i, _i, _i, _i],
+    "rtk_track_score_pairs_centre": [_p, _p, _p, _p, _p, _p, _p, _p, _d, _p],
+    "rtk_score_replay_optimal_sim": [_i, _i, _p, _p, _p, _p, _p, _p, _i, _d, _p, _p, _p, _p, _p, _p],
+    "rtk_score_alignment_sim": [_i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "rtk_score_hota_optimal_sim": [_i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "rtk_score_identity_pairs_sim": [_i, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p],
     # ---- include/rtk_train.h
     "rtk_bn_train_stats": [_i] * 5 + [_p] * 3 + [_p],
     "rtk_bn_relu_fwd": [_i] * 5 + [_p, _p, _i, _p, _p],

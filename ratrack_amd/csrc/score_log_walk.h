@@ -8,7 +8,7 @@
 //   lw_hash, LW_EMPTY, LW_SLOTS, lw_track_slot<INSERT>   the per-clip track table: open addressing, slots claimed by CAS
 //   lw_pair_find / lw_pair_append <PSLOTS>               the (label entry, track slot) pair list with its lookup
 //   lw_stays                   whether a detection remains at a threshold
-//   lw_valid_pair, LW_REMOVED  a logged pair as a valid pair of its frame, with its similarity
+//   lw_valid_pair<SIM>, LW_REMOVED  a logged pair as a valid pair of its frame, with its similarity (SIM: the one the log carries)
 //   lw_log_ok / lw_pairs_ok    the host's check of a log / pair-log argument
 //
 // Three short loops stay in the kernels: a label id's entry in the label table, the first kept object with a label id, and the
@@ -106,9 +106,22 @@ __device__ __forceinline__ bool lw_stays(double score, double tau) { return !(sc
 // a logged pair of frame `fr` as a VALID pair (include/rtk_score.h, "HOTA under the optimal matching"): its detection, its kept object
 // and its similarity (double)c / (double)(|i| + |j| - c), unclamped -- or false: the pair does not describe its frame, its detection
 // was removed (rrow[i] == LW_REMOVED), or there is no overlap (c <= 0, or a denominator that is not positive: coincident points count
-// once per PAIR, so c may exceed a size)
+// once per PAIR, so c may exceed a size).
+// SIM: the log carries its pairs' similarity (pair_sim (B,Q), include/rtk_score.h, the last section) -- valid iff the key describes the
+// frame, the detection remains and s = pair_sim[q] > 0.0 (a NaN is not); pair_common and the sizes are not read.  Without SIM pair_sim
+// is not read and the function is what it was.
+template <bool SIM = false>
 __device__ __forceinline__ bool lw_valid_pair(const rtk_score_pairs_t &pr, const lw_pair_frame_t &fr, size_t rb, size_t qb, int p, const int *rrow,
-                                              int *row, int *col, double *s) {
+                                              int *row, int *col, double *s, const double *pair_sim = nullptr) {
+    if (SIM) {
+        const int key = pr.pair_key[qb + fr.pair + p];
+        const int i = key >> 8, j = key & 255;
+        if (key < 0 || i >= fr.P || j >= fr.G || rrow[i] == LW_REMOVED) return false;
+        const double v = pair_sim[qb + fr.pair + p];
+        if (!(v > 0.0)) return false;
+        *row = i; *col = j; *s = v;
+        return true;
+    }
     const int key = pr.pair_key[qb + fr.pair + p], c = pr.pair_common[qb + fr.pair + p];
     const int i = key >> 8, j = key & 255;
     if (key < 0 || i >= fr.P || j >= fr.G || c <= 0 || rrow[i] == LW_REMOVED) return false;

@@ -1,6 +1,7 @@
 // track_score_body.h -- the LDS layout, the body and the argument checks of the scoring kernels: rtk_track_score and
-// rtk_track_score_logged (track_score.hip), rtk_track_score_memory (track_score_memory.hip) and rtk_track_score_pairs
-// (track_score_pairs.hip) instantiate the one body, each kernel behind a __global__ wrapper of its own in the file of its entry point.
+// rtk_track_score_logged (track_score.hip), rtk_track_score_memory (track_score_memory.hip), rtk_track_score_pairs
+// (track_score_pairs.hip) and rtk_track_score_pairs_centre (track_score_centre.hip) instantiate the one body, each kernel behind a
+// __global__ wrapper of its own in the file of its entry point.
 #pragma once
 #include <math.h>
 
@@ -21,6 +22,14 @@ static inline size_t ts_score_lds(int Kobj, int K, int N) {
 // the memory variant also keeps the old record's track ids: old_track[Kobj] i32 after the scalars
 static inline size_t ts_score_memory_lds(int Kobj, int K, int N) { return ts_score_lds(Kobj, K, N) + (size_t)Kobj * sizeof(int); }
 
+// the centre variant keeps, 8-byte aligned behind either layout: gpos[K][3] f64, the kept objects' positions | zero_distance f64 | the
+// address of the stream's part of pair_sim (64 bits) -- read from the arguments once, at the start, so that they are not carried in
+// scalar registers through the whole body
+static inline size_t ts_score_centre_lds(int Kobj, int K, int N, bool memory) {
+    const size_t base = memory ? ts_score_memory_lds(Kobj, K, N) : ts_score_lds(Kobj, K, N);
+    return ((base + 7) & ~(size_t)7) + ((size_t)3 * K + 2) * sizeof(double);
+}
+
 // The body of the scoring kernels.  LOG: the frame is also appended to the stream's log (rtk_score_log_t) -- thread i writes
 // detection i's record where it finds its pre-greedy best object, thread j the j-th kept label id, thread 0 the frame's slot and the
 // cursors; a frame that does not fit writes nothing and raises RTK_SCORE_FLAG_LOG.  Without LOG `lg` is not read.
@@ -32,12 +41,27 @@ static inline size_t ts_score_memory_lds(int Kobj, int K, int N) { return ts_sco
 // scal[4..7], one barrier more) gives every row its place and the frame its pair count, which joins the fit test; thread i then writes
 // its row's pairs and its size, thread j the j-th kept object's size, thread 0 the frame's slot and the cursor.  Without PAIRS `pr` is
 // not read and the body is what it was.
+// CENTRE (only with PAIRS): the pair log's similarity is TrackEval's centre-distance similarity (include/rtk_score.h, the last section)
+// -- every live column keeps its detection index in pts[p].w, thread i forms detection i's centre in ascending column order in
+// registers (N broadcast reads of LDS), decides row i's pairs once (s > 0, a 64-bit mask over the kept objects) where PAIRS counts
+// common > 0, and writes key, common and s behind the same ordered prefix; the kept objects' positions are G broadcast reads of LDS,
+// where they, zero_distance and the stream's pair_sim address are put at the start (ts_score_centre_lds: 24 K + 16 bytes more).
+// Without CENTRE the three arguments are not read and the body is what it was.
 static_assert(RTK_SCORE_MAX_OBJECTS <= TS_THREADS, "PAIRS: one thread per detection row");
-template <bool LOG, bool MEM, bool PAIRS = false>
+// s = 1 - |c - g| / zero_distance in float64, every operation rounded on its own (the build has contraction off)
+__device__ __forceinline__ double ts_centre_similarity(double cx, double cy, double cz, const double *g, double zero_distance) {
+    const double dx = cx - g[0], dy = cy - g[1], dz = cz - g[2];
+    const double d2 = (dx * dx + dy * dy) + dz * dz;
+    return 1.0 - sqrt(d2) / zero_distance;
+}
+
+template <bool LOG, bool MEM, bool PAIRS = false, bool CENTRE = false>
 __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in, const rtk_track_score_state_t &st,
                                                  const rtk_track_score_out_t &out, const rtk_score_log_t &lg,
-                                                 const rtk_score_memory_t &mm, const rtk_score_pairs_t &pr = rtk_score_pairs_t{}) {
+                                                 const rtk_score_memory_t &mm, const rtk_score_pairs_t &pr = rtk_score_pairs_t{},
+                                                 double *pair_sim = nullptr, const double *gt_centre = nullptr, double zero_distance = 0.0) {
     static_assert(LOG || !PAIRS, "the pair log goes with the main log");
+    static_assert(PAIRS || !CENTRE, "the centre similarity is the pair log's");
     extern __shared__ __attribute__((aligned(16))) unsigned char ts_smem[];
     const int b = blockIdx.x, t = threadIdx.x, lane = t & (RTK_WAVE - 1), wave = t / RTK_WAVE;
     const int N = in.N, Kobj = in.Kobj, K = in.K, T = in.T, W = (N + 31) / 32;
@@ -49,6 +73,8 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
     int *gsize = prev_id + Kobj, *glabel = gsize + K, *gslot = glabel + K, *gpred = gslot + K, *entry = gpred + K;
     int *scal = entry + K;      // 0: predicted points | 1: ground-truth columns | 2..4: mt, pt, ml of a closing clip
     int *old_track = scal + 8;  // MEM only
+    double *gpos = nullptr;     // CENTRE only
+    if (CENTRE) gpos = reinterpret_cast<double *>(ts_smem + ((reinterpret_cast<unsigned char *>(MEM ? old_track + Kobj : old_track) - ts_smem + 7) & ~(size_t)7));
 
     const size_t ob = (size_t)b * Kobj, kb = (size_t)b * K, tb = (size_t)b * T;
     float *target = out.aff_target + ob * Kobj;
@@ -85,6 +111,13 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
     int log_q = 0, pair_at = 0, pair_total = 0;      // PAIRS: the pair cursor, the first pair of this thread's row, the frame's pairs
     if (PAIRS) log_q = pr.cursor[b];
 
+    if (CENTRE) {      // the three arguments end here
+        for (int e = t; e < 3 * G; e += TS_THREADS) gpos[e] = gt_centre[kb * 3 + e];
+        if (t == 0) {
+            gpos[3 * K] = zero_distance;
+            reinterpret_cast<unsigned long long *>(gpos)[3 * K + 1] = (unsigned long long)(pair_sim + (size_t)b * pr.Q);
+        }
+    }
     if (t < 8) scal[t] = 0;
     for (int i = t; i < Kobj; i += TS_THREADS) {
         psize[i] = 0;
@@ -131,6 +164,7 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
         gmask[p] = m;
         if (m) qlist[atomicAdd(&scal[1], 1)] = p;
         const int o = live ? in.obj[(size_t)b * N + p] : -1;
+        if (CENTRE) pts[p].w = __int_as_float((o >= 0 && o < P) ? o : -1);
         if (o >= 0 && o < P) {
             atomicAdd(&psize[o], 1);
             plist[atomicAdd(&scal[0], 1)] = p | (o << 16);
@@ -163,7 +197,33 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
     // ---- PAIRS: the rows' pair counts, their ordered prefix, and whether the frame's pairs fit ----
     if (PAIRS) {
         int mine = 0;
-        if (t < P) {
+        double cx = 0.0, cy = 0.0, cz = 0.0;      // CENTRE: the centre of this thread's detection
+        unsigned long long logged = 0ull;          // CENTRE: the kept objects (K <= 64) this thread's row is logged with
+        if (CENTRE) {
+            if (t < P) {
+                double sx = 0.0, sy = 0.0, sz = 0.0;
+                int m = 0;
+                // ascending column order: rtk_gt_objects' rule for its own centres.  Without a branch, so that the reads of LDS run ahead
+                // of the adds (behind a test of .w every column costs a round trip of its own): another detection's column adds +0.0,
+                // which changes no bit -- a sum that starts from +0.0 is never -0.0 (x + -x is +0.0 under round-to-nearest)
+#pragma unroll 8
+                for (int p = 0; p < n; ++p) {
+                    const float4 a = pts[p];
+                    const bool own = __float_as_int(a.w) == t;
+                    sx += own ? (double)a.x : 0.0;
+                    sy += own ? (double)a.y : 0.0;
+                    sz += own ? (double)a.z : 0.0;
+                    m += own ? 1 : 0;
+                }
+                if (m > 0) {
+                    cx = sx / (double)m; cy = sy / (double)m; cz = sz / (double)m;
+#pragma unroll 4
+                    for (int j = 0; j < G; ++j)      // the one place a pair is decided: s > 0.0, a NaN is not
+                        if (ts_centre_similarity(cx, cy, cz, gpos + 3 * j, gpos[3 * K]) > 0.0) logged |= 1ull << j;
+                }
+            }
+            mine = __popcll(logged);
+        } else if (t < P) {
             for (int j = 0; j < G; ++j) mine += common[t * K + j] > 0 ? 1 : 0;
         }
         const int upto = wave_inclusive_scan(mine, lane);
@@ -176,6 +236,18 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
         }
         pair_at += upto - mine;
         log_fits = log_fits && log_q >= 0 && log_q <= pr.Q - pair_total;
+        if (CENTRE && log_fits) {      // row t's pairs in ascending j: key, common, and s formed again by the same operations
+            double *sim = reinterpret_cast<double *>(reinterpret_cast<unsigned long long *>(gpos)[3 * K + 1]) + log_q + pair_at;
+            size_t q = (size_t)b * pr.Q + log_q + pair_at;
+            while (logged) {
+                const int j = __ffsll((long long)logged) - 1;
+                logged &= logged - 1;
+                pr.pair_key[q] = (t << 8) | j;
+                pr.pair_common[q] = common[t * K + j];
+                *sim++ = ts_centre_similarity(cx, cy, cz, gpos + 3 * j, gpos[3 * K]);
+                ++q;
+            }
+        }
     }
 
     // ---- every prediction's best object: strict > from 0, the first of equals ----
@@ -197,10 +269,12 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
             lg.rec_iou[r] = bi;
             if (PAIRS) {
                 pr.rec_size[r] = psize[i];
-                size_t q = (size_t)b * pr.Q + log_q + pair_at;
-                for (int j = 0; j < G; ++j) {
-                    const int c = common[i * K + j];
-                    if (c > 0) { pr.pair_key[q] = (i << 8) | j; pr.pair_common[q] = c; ++q; }
+                if (!CENTRE) {      // (CENTRE: written with the prefix above)
+                    size_t q = (size_t)b * pr.Q + log_q + pair_at;
+                    for (int j = 0; j < G; ++j) {
+                        const int c = common[i * K + j];
+                        if (c > 0) { pr.pair_key[q] = (i << 8) | j; pr.pair_common[q] = c; ++q; }
+                    }
                 }
             }
         }

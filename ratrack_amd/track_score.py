@@ -120,9 +120,26 @@ exact assignment over similarity x A (csrc/lds_assignment.h, the float64 score t
 integer), and the matched pairs are thresholded at each alpha afterwards; A is what makes HOTA prefer the track that follows an object
 through the clip over a one-frame intruder with a slightly larger IoU.  Identity: every (detection, object) pair above the level
 counts, not only a detection's best object.  `threshold=` removes detections before anything else, the alignment pass included.  WHAT
-NOW AGREES WITH TrackEval is the arrangement of both metrics; WHAT STILL DOES NOT is the similarity -- the reference's point IoU in
-place of a box IoU, because its result files hold points -- and the 28-bit weights.  The defaults (`matching="greedy"`,
-`pairs="best"`) are the calls above with their launches and bits.
+NOW AGREES WITH TrackEval is the arrangement of both metrics and, under `similarity="centre"` (below), the similarity as well; WHAT
+STILL DOES NOT is the 28-bit weights and, under "centre", the positions, which are point centroids rather than label-box centres.
+Under the default `similarity="iou"` the similarity is the reference's point IoU -- TrackEval's other similarity, a box IoU, will never
+be available here: the detections are point clusters without boxes.  The defaults (`matching="greedy"`, `pairs="best"`) are the calls
+above with their launches and bits.
+
+The centre-distance similarity.  `TrackScorer(..., sweep_pairs=Q, similarity="centre", zero_distance=2.0)` writes the pair log under
+TrackEval's similarity for detections that are positions (`_calculate_euclidean_similarity`): s = max(0, 1 - |c - g| / zero_distance),
+c the float64 centroid of the detection's points (column order), g the kept object's `GtObjects.centre`.  A pair is logged iff s > 0,
+whatever its common point count -- the point IoU is harsh on radar clusters of two to five points, this asks whether the detection sits
+on its object.  Everything else `update` does is bit for bit what it does under "iou" (rtk_track_score_pairs_centre), and
+
+    sw  = scorer.sweep(matching="optimal", min_iou=0.5)       # min_iou: the minimum similarity
+    op  = scorer.clear_optimal(min_iou=0.5)
+    ho  = scorer.hota(matching="optimal")
+    idn = scorer.identity(pairs="all")
+
+replay that log unchanged in every other respect, with "IoU" read as s (the *_sim entry points: the same kernels' bodies on the log's
+own similarity).  `similarity_distance(s, zero_distance)` turns motp, amotp and LocA back into metres.  The greedy calls read only the
+main log and are the same under either similarity; a log has one similarity: build two scorers for both.
 
 Nothing here synchronises with the device except `GtObjects.check()`, `TrackScorer.check()`, `TrackScorer.result()`,
 `TrackScorer.sweep()`, `TrackScorer.hota()`, `TrackScorer.identity()` and `TrackScorer.clear_optimal()`.
@@ -158,12 +175,47 @@ PAIR_EDGES = 2048                      # RTK_SCORE_PAIR_EDGES
 ALIGN_PAIRS = 1024                     # RTK_SCORE_ALIGN_PAIRS
 
 
+# ---- the similarity of the pair log ----------------------------------------------------------------------------------------
+
+SIMILARITIES = ("iou", "centre")
+ZERO_DISTANCE = 2.0                    # TrackEval's default zero_distance
+
+
+def check_similarity(similarity="iou", zero_distance=None, sweep_pairs=None):
+    """The checks of `TrackScorer(similarity=..., zero_distance=..., sweep_pairs=...)`, host only and before anything is allocated
+    -> (similarity, zero_distance as a float, or None under "iou").  "iou": the point IoU of the logged integers, today's scorer; a
+    zero_distance given with it is an error.  "centre": TrackEval's centre-distance similarity, which lives in the pair log and so
+    needs sweep_pairs; zero_distance None means 2.0, any other value must be a finite number > 0."""
+    if similarity not in SIMILARITIES:
+        raise ValueError("TrackScorer: similarity=%r is neither \"iou\" nor \"centre\"" % (similarity,))
+    if similarity == "iou":
+        if zero_distance is not None:
+            raise ValueError("TrackScorer: zero_distance=%r goes with similarity=\"centre\"; the point IoU has no distance scale" % (zero_distance,))
+        return "iou", None
+    if sweep_pairs is None:
+        raise ValueError("TrackScorer: similarity=\"centre\" lives in the pair log (give sweep_pairs, with sweep_frames and sweep_records)")
+    if zero_distance is None:
+        return "centre", ZERO_DISTANCE
+    try:
+        z = float(zero_distance)
+    except (TypeError, ValueError):
+        raise ValueError("TrackScorer: zero_distance=%r is not a number" % (zero_distance,))
+    if not (np.isfinite(z) and z > 0.0):
+        raise ValueError("TrackScorer: zero_distance=%r must be finite and above 0" % (zero_distance,))
+    return "centre", z
+
+
+def similarity_distance(s, zero_distance):
+    """The distance a centre-distance similarity stands for, (1 - s) * zero_distance in float64: motp, amotp and LocA in metres."""
+    return (1.0 - np.asarray(s, dtype=np.float64)) * float(zero_distance)
+
+
 # ---- what fits -------------------------------------------------------------------------------------------------------------
 
-def check_fit(max_boxes, points, max_objects=None, track_memory=False):
+def check_fit(max_boxes, points, max_objects=None, track_memory=False, centre=False):
     """Raises ValueError, stating the limit, for sizes whose per-stream tables do not fit one workgroup's LDS: those of `gt_objects`
     (max_boxes, points) and, with max_objects, those of `TrackScorer.update` as well (track_memory: of its memory variant, which
-    keeps max_objects more words).  Host only."""
+    keeps max_objects more words; centre: of the centre-similarity variant, which keeps the kept objects' positions).  Host only."""
     K, N = int(max_boxes), int(points)
     if not 1 <= K <= MAX_BOXES:
         raise ValueError("max_boxes=%d outside [1, %d] (a point's ground-truth objects are one 64-bit mask)" % (K, MAX_BOXES))
@@ -177,7 +229,10 @@ def check_fit(max_boxes, points, max_objects=None, track_memory=False):
     Kobj = int(max_objects)
     if not 1 <= Kobj <= MAX_OBJECTS:
         raise ValueError("max_objects=%d outside [1, %d]" % (Kobj, MAX_OBJECTS))
-    need = _lib._fn("rtk_track_score_memory_lds_bytes" if track_memory else "rtk_track_score_lds_bytes")(Kobj, K, N)
+    if centre:
+        need = _lib._fn("rtk_track_score_centre_lds_bytes")(Kobj, K, N, 1 if track_memory else 0)
+    else:
+        need = _lib._fn("rtk_track_score_memory_lds_bytes" if track_memory else "rtk_track_score_lds_bytes")(Kobj, K, N)
     if need < 0 or need > LDS_LIMIT:
         raise ValueError("TrackScorer: max_objects=%d, max_boxes=%d and N=%d need %d bytes of LDS per stream, the limit is %d"
                          % (Kobj, K, N, need, LDS_LIMIT))
@@ -299,7 +354,8 @@ class SweepResult:
     smota (NaN at index 0), motp, moda, recall, precision.  amota, samota, amotp.  `best`: dict of the level of the largest MOTA
     (level, threshold, mota, moda, recall, precision, mt_fraction, pt_fraction, ml_fraction and the raw counts), None when no level
     was reached.  `unfiltered`: the pooled index-0 counts and iou_sum.  `counters` (L+1,B,11) int64 and `iou_sums` (L+1,B) float64 per
-    stream; `flags` (B).  `matching` "greedy" or "optimal" and `min_iou` (None for greedy).  Under the optimal matching also `frag`
+    stream; `flags` (B).  `matching` "greedy" or "optimal" and `min_iou` (None for greedy); `similarity` and `zero_distance` of the
+    scorer's pair log ("iou" and None, or "centre" and its distance scale: the IoU sums are then sums of s).  Under the optimal matching also `frag`
     (L+1) int64, the pooled fragmentations per level, and `iou_q` (L+1) int64, the pooled sums of the matches' IoUs quantised to
     1/65536 (both 0 past `reached`), with `frag_streams` and `iou_q_streams` (L+1,B) per stream; under the greedy rule they are
     None.  MOTP is iou_sum / tp under either."""
@@ -392,7 +448,8 @@ class HotaResult:
     detpr, assa, assre, asspr, loca, hota_alpha (NaN where the denominator is 0).  Scalars, each the sum over the levels of the
     non-NaN terms divided by A: hota, deta_mean, assa_mean, detre_mean, detpr_mean, assre_mean, asspr_mean, loca_mean.  `counters`
     (A,B,6) int64 in HOTA_COUNTERS order and `sums` (A,B,4) float64 in HOTA_SUMS order per stream; `flags` (B); `threshold` (None
-    or the float the detections were filtered with); `matching` "greedy" or "optimal"."""
+    or the float the detections were filtered with); `matching` "greedy" or "optimal"; `similarity` and `zero_distance` of the scorer's
+    pair log ("iou" and None, or "centre" and its distance scale)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -434,7 +491,7 @@ class IdentityResult:
     given.  Per-level arrays of length A, pooled over the streams: idtp, idfn, idfp, gt, pred, pairs (integers) and idf1, idr, idp
     (NaN where the denominator is 0).  `counters` (A,B,6) int64 in IDENTITY_COUNTERS order per stream; `flags` (B); `threshold` (None
     or the float the detections were filtered with); `pair_mode` "best" or "all": what `identity(pairs=...)` was given (the field
-    `pairs` is the count)."""
+    `pairs` is the count); `similarity` and `zero_distance` of the scorer's pair log ("iou" and None, or "centre" and its distance scale)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -497,10 +554,18 @@ class TrackScorer:
     with and without track_memory), for `sweep(matching="optimal")` and `clear_optimal`.  A frame whose pairs do not fit is logged in
     neither log (FLAG_LOG).  The pair log (device tensors): pair_cursor (B) int32; pair_frame (B,F,2) int32 first pair | pair count;
     pair_key (B,Q) int32 detection index << 8 | kept-object index; pair_common (B,Q) int32; log_size, log_label_size (B,R) int32, the
-    point counts of the logged detections and kept objects."""
+    point counts of the logged detections and kept objects.
+
+    similarity: "iou" (today's object, launches and bits) or "centre", which needs sweep_pairs: the pair log then holds every pair
+    with centre-distance similarity s = 1 - |c - g| / zero_distance > 0 (module docstring; rtk_track_score_pairs_centre), pair_common
+    may be 0, and pair_sim (B,Q) float64 holds s.  zero_distance: None (2.0 under "centre") or a finite number > 0; only with
+    "centre".  `update` / `update_raw` then read `gobj.centre`; `sweep(matching="optimal")`, `clear_optimal`, `hota(matching="optimal")`
+    and `identity(pairs="all")` replay the log on s (min_iou: the minimum similarity)."""
 
     def __init__(self, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, device="cuda", sweep_frames=None, sweep_records=None,
-                 track_memory=False, sweep_pairs=None):
+                 track_memory=False, sweep_pairs=None, similarity="iou", zero_distance=None):
+        self.similarity, self.zero_distance = check_similarity(similarity, zero_distance, sweep_pairs)
+        self.centre = self.similarity == "centre"
         self.B, self.Kobj, self.K, self.T = int(streams), int(max_objects), int(max_boxes), int(max_gt_tracks)
         if self.T < 1:
             raise ValueError("max_gt_tracks=%d must be at least 1" % self.T)
@@ -520,7 +585,7 @@ class TrackScorer:
             if self.Q < 1 or self.B * self.Q >= 2 ** 31:
                 raise ValueError("TrackScorer: sweep_pairs=%d must be at least 1 (and the pair log below 2^31 entries)" % self.Q)
         self.track_memory = bool(track_memory)
-        check_fit(self.K, 1, self.Kobj, self.track_memory)
+        check_fit(self.K, 1, self.Kobj, self.track_memory, self.centre)
         B, z = self.B, lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
         self.counters = torch.zeros(B, len(COUNTERS), dtype=torch.int64, device=device)
         self.iou_sum = torch.zeros(B, dtype=torch.float64, device=device)
@@ -540,6 +605,8 @@ class TrackScorer:
             self.pair_cursor, self.pair_frame = z(B), z(B, self.F, 2)
             self.pair_key, self.pair_common = z(B, self.Q), z(B, self.Q)
             self.log_size, self.log_label_size = z(B, self.R), z(B, self.R)
+        if self.centre:
+            self.pair_sim = torch.zeros(B, self.Q, dtype=torch.float64, device=device)
 
     def _log_block(self, object_conf=None):
         return ScoreLog(self.F, self.R, object_conf, self.log_cursor.data_ptr(), self.log_frame.data_ptr(), self.log_label.data_ptr(),
@@ -579,8 +646,15 @@ class TrackScorer:
         if gobj.max_boxes != self.K or gobj.points != N or gobj.count.numel() != B:
             raise ValueError("TrackScorer(max_boxes=%d): ground-truth objects of %d slots over %d points against %d points"
                              % (self.K, gobj.max_boxes, gobj.points, N))
-        check_fit(self.K, N, self.Kobj, self.track_memory)
+        check_fit(self.K, N, self.Kobj, self.track_memory, self.centre)
         dev = pc1.device
+        gt_centre = None
+        if self.centre:
+            gt_centre = getattr(gobj, "centre", None)
+            if gt_centre is None or tuple(gt_centre.shape) != (B, self.K, 3) or gt_centre.dtype != torch.float64:
+                raise ValueError("TrackScorer(similarity=\"centre\"): gobj.centre must be (%d,%d,3) float64, got %s"
+                                 % (B, self.K, None if gt_centre is None else (tuple(gt_centre.shape), gt_centre.dtype)))
+            gt_centre = gt_centre.to(dev).contiguous()
         if self.track_memory and (table_ids is None or table_count is None or tuple(table_ids.shape) != (B, self.Kobj) or table_count.numel() != B):
             raise ValueError("TrackScorer(track_memory=True): update_raw needs the tracker's table, table_ids (%d,%d) and table_count (%d), got %s and %s"
                              % (B, self.Kobj, B, None if table_ids is None else tuple(table_ids.shape),
@@ -612,7 +686,12 @@ class TrackScorer:
         if self.track_memory:
             table_ids, table_count = as32(table_ids), as32(table_count)
             mm = ScoreMemory(table_ids.data_ptr(), table_count.data_ptr(), self.row_track.data_ptr(), self.labelled_coasted.data_ptr())
-        if self.pairs:
+        if self.centre:
+            lg, pr = self._log_block(object_conf.data_ptr()), self._pair_block()
+            _lib.call("rtk_track_score_pairs_centre", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), ctypes.addressof(lg),
+                      None if mm is None else ctypes.addressof(mm), ctypes.addressof(pr), self.pair_sim.data_ptr(), gt_centre.data_ptr(),
+                      self.zero_distance, _stream())
+        elif self.pairs:
             lg, pr = self._log_block(object_conf.data_ptr()), self._pair_block()
             _lib.call("rtk_track_score_pairs", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), ctypes.addressof(lg),
                       None if mm is None else ctypes.addressof(mm), ctypes.addressof(pr), _stream())
@@ -704,7 +783,8 @@ class TrackScorer:
         positives' scores, the threshold walk and the replay at every threshold on the device -- five launches of this library plus
         torch's sort -- then one download.  The running state and the log are only read: scoring may go on.  check: raise (naming the
         stream) on any sticky flag, a frame that did not fit the log among them.  matching "greedy": `update`'s rule, today's call.
-        "optimal": both replays match every frame by an exact assignment over the logged pairs with IoU >= min_iou (module docstring);
+        "optimal": both replays match every frame by an exact assignment over the logged pairs with IoU >= min_iou (module docstring;
+        under similarity="centre" min_iou is the minimum similarity s);
         it needs the pair log (sweep_pairs) and an explicit min_iou in (0, 1] -- there is no default.  -> SweepResult."""
         if matching not in ("greedy", "optimal"):
             raise ValueError("TrackScorer.sweep: matching=%r is neither \"greedy\" nor \"optimal\"" % (matching,))
@@ -720,11 +800,12 @@ class TrackScorer:
             replay = lambda lgp, score, thr, reached, count, mask, flags, st: self._replay_optimal(lgp, prp, score, thr, reached, count, m, mask,
                                                                                                   flags, st)
             fl, val = self._sweep(L, check, replay, OPTIMAL_COUNTERS, optimal_sweep_values)
-            return SweepResult(flags=fl, matching="optimal", min_iou=m, **val)
+            return SweepResult(flags=fl, matching="optimal", min_iou=m, similarity=self.similarity, zero_distance=self.zero_distance, **val)
         if min_iou is not None:
             raise ValueError("TrackScorer.sweep: min_iou=%r goes with matching=\"optimal\"; the greedy rule has no threshold" % (min_iou,))
         fl, val = self._sweep(L, check, self._replay_greedy, COUNTERS, sweep_values)
-        return SweepResult(flags=fl, matching="greedy", min_iou=None, frag=None, iou_q=None, frag_streams=None, iou_q_streams=None, **val)
+        return SweepResult(flags=fl, matching="greedy", min_iou=None, frag=None, iou_q=None, frag_streams=None, iou_q_streams=None,
+                           similarity=self.similarity, zero_distance=self.zero_distance, **val)
 
     def _sweep(self, L, check, replay, names, values):
         """The sweep under either matching: track means, the unfiltered replay with the mask, the sort, the threshold walk and the
@@ -764,8 +845,12 @@ class TrackScorer:
         c = torch.empty(count, B, len(OPTIMAL_COUNTERS), dtype=torch.int64, device=dev)
         iq = torch.empty(count, B, dtype=torch.int64, device=dev)
         q = torch.empty(count, B, dtype=torch.float64, device=dev)
-        _lib.call("rtk_score_replay_optimal", B, self.T, lgp, prp, score.data_ptr(), thr.data_ptr(), None if reached is None else reached.data_ptr(),
-                  count, min_iou, c.data_ptr(), iq.data_ptr(), q.data_ptr(), None if mask is None else mask.data_ptr(), flags.data_ptr(), st)
+        tail = (score.data_ptr(), thr.data_ptr(), None if reached is None else reached.data_ptr(), count, min_iou, c.data_ptr(), iq.data_ptr(),
+                q.data_ptr(), None if mask is None else mask.data_ptr(), flags.data_ptr(), st)
+        if self.centre:
+            _lib.call("rtk_score_replay_optimal_sim", B, self.T, lgp, prp, self.pair_sim.data_ptr(), *tail)
+        else:
+            _lib.call("rtk_score_replay_optimal", B, self.T, lgp, prp, *tail)
         return c, iq, q
 
     def _threshold_scores(self, threshold, lgp, flags, st):
@@ -805,7 +890,8 @@ class TrackScorer:
         total_iou = float(np.cumsum(iou_sum)[-1]) if B else 0.0          # cumsum: one addition after the other, in stream order
         overall = {k: int(total[i]) for i, k in enumerate(OPTIMAL_COUNTERS)}
         overall.update(iou_q=int(iou_q.sum()), iou_sum=total_iou, **{k: float(v) for k, v in optimal_values(total, total_iou).items()})
-        return dict(per_stream=per, overall=overall, flags=fl, min_iou=m, threshold=None if threshold is None else float(tau))
+        return dict(per_stream=per, overall=overall, flags=fl, min_iou=m, threshold=None if threshold is None else float(tau),
+                    similarity=self.similarity, zero_distance=self.zero_distance)
 
     def _pair_log_args(self, what, keyword, value, choices):
         """The checks `hota(matching=...)` and `identity(pairs=...)` share: the keyword's value, and the pair log for the second choice."""
@@ -848,17 +934,22 @@ class TrackScorer:
             prp = ctypes.addressof(pr)
             pair_a = torch.empty(B, self.Q, dtype=torch.float64, device=dev)
             pair_index, clip_cg, clip_ct = (torch.empty(B, self.Q, dtype=torch.int32, device=dev) for _ in range(3))
-            _lib.call("rtk_score_alignment", B, self.T, lgp, prp, sp, tp, pair_a.data_ptr(), pair_index.data_ptr(), clip_cg.data_ptr(),
-                      clip_ct.data_ptr(), flags.data_ptr(), st)
-            _lib.call("rtk_score_hota_optimal", B, lgp, prp, sp, tp, A, pair_a.data_ptr(), pair_index.data_ptr(), clip_cg.data_ptr(),
-                      clip_ct.data_ptr(), c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
+            tables = (pair_a.data_ptr(), pair_index.data_ptr(), clip_cg.data_ptr(), clip_ct.data_ptr())
+            if self.centre:
+                sim = self.pair_sim.data_ptr()
+                _lib.call("rtk_score_alignment_sim", B, self.T, lgp, prp, sim, sp, tp, *tables, flags.data_ptr(), st)
+                _lib.call("rtk_score_hota_optimal_sim", B, lgp, prp, sim, sp, tp, A, *tables, c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
+            else:
+                _lib.call("rtk_score_alignment", B, self.T, lgp, prp, sp, tp, *tables, flags.data_ptr(), st)
+                _lib.call("rtk_score_hota_optimal", B, lgp, prp, sp, tp, A, *tables, c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
         else:
             _lib.call("rtk_score_hota", B, self.T, lgp, sp, tp, A, c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
         counters, sums, fl, *tau = _download([c, q, flags.long()] + ([] if thr is None else [thr]))
         tau = float(tau[0][0]) if tau else None
         if check:
             self._raise_on_flags(fl.tolist())
-        return HotaResult(flags=fl, threshold=tau, matching=matching, **hota_values(counters, sums))
+        return HotaResult(flags=fl, threshold=tau, matching=matching, similarity=self.similarity, zero_distance=self.zero_distance,
+                          **hota_values(counters, sums))
 
     def identity(self, alphas=(0.5,), threshold=None, check=True, pairs="best"):
         """IDF1, IDP and IDR over the log (module docstring; definitions in include/rtk_score.h).  alphas: a float or a sequence of
@@ -887,11 +978,16 @@ class TrackScorer:
         sp, tp = None if score is None else score.data_ptr(), None if thr is None else thr.data_ptr()
         if pairs == "all":
             pr = self._pair_block()
-            _lib.call("rtk_score_identity_pairs", B, self.T, lgp, ctypes.addressof(pr), sp, tp, levels.data_ptr(), A, c.data_ptr(), flags.data_ptr(), st)
+            if self.centre:
+                _lib.call("rtk_score_identity_pairs_sim", B, self.T, lgp, ctypes.addressof(pr), self.pair_sim.data_ptr(), sp, tp, levels.data_ptr(), A,
+                          c.data_ptr(), flags.data_ptr(), st)
+            else:
+                _lib.call("rtk_score_identity_pairs", B, self.T, lgp, ctypes.addressof(pr), sp, tp, levels.data_ptr(), A, c.data_ptr(), flags.data_ptr(), st)
         else:
             _lib.call("rtk_score_identity", B, self.T, lgp, sp, tp, levels.data_ptr(), A, c.data_ptr(), flags.data_ptr(), st)
         counters, fl, *tau = _download([c, flags.long()] + ([] if thr is None else [thr]))
         tau = float(tau[0][0]) if tau else None
         if check:
             self._raise_on_flags(fl.tolist())
-        return IdentityResult(flags=fl, threshold=tau, pair_mode=pairs, **identity_values(counters, al))
+        return IdentityResult(flags=fl, threshold=tau, pair_mode=pairs, similarity=self.similarity, zero_distance=self.zero_distance,
+                              **identity_values(counters, al))
