@@ -217,6 +217,26 @@ RTK_EXPORT int rtk_cost_volume_split_term(int samples, int n1, int n2, const flo
                                           const float *wd_packed, const void *split_images, const float *image_scales,
                                           const float *bias2, const float *bias3, const rtk_layer_t *wn, float *out, int out_pitch,
                                           int workgroups, rtk_stream_t stream);
+/* The forward cost volume on a 16-position tile (one query point per wave, eight waves per workgroup, two per SIMD;
+ * v_mfma_f32_16x16x32_f16): the same operator on the same arithmetic pieces as rtk_cost_volume_split_shared / _term -- the same split
+ * pieces under the same per-position scales, fp32 accumulation; the bits differ because a matrix instruction sums 32 products instead
+ * of 16, and the WeightNet's output layer its 8 in another order.  Same arguments and limits, but the two layers come in the
+ * fragment order of the 16-position tile:
+ * rtk_pack_split_layer16: as rtk_pack_split_layer (same scale, same pieces), image of cin/32 * cout/16 * 2 fragments of 1 KiB,
+ * fragment (up, v, p) = piece p of 2^k W, rows 16 v .. +15 against the 32 input channels of k-step up; lane 16 g + i holds
+ * W[16 v + i][32 up + 16 (t / 4) + 4 g + t % 4], t = 0..7 (ratrack_amd.fused.pack_layer_split16 is its host restatement). */
+RTK_EXPORT int rtk_pack_split_layer16(int cout, int cin, const float *w, int transposed, void *image, float *inv_scale,
+                                      rtk_stream_t stream);
+RTK_EXPORT int rtk_cost_volume_split16_shared(int samples, int n1, int n2, const float *xyz1, const float *xyz2,
+                                              const int64_t *knn_idx, const float *p1, const float *p2, const float *wd_packed,
+                                              const void *split_images16, const float *image_scales, const float *bias2,
+                                              const float *bias3, const rtk_layer_t *wn, float *out, int out_pitch, int workgroups,
+                                              rtk_stream_t stream);
+RTK_EXPORT int rtk_cost_volume_split16_term(int samples, int n1, int n2, const float *xyz1, const float *xyz2,
+                                            const int64_t *knn_idx, const float *p1, const float *p2, const float *sample_term,
+                                            const float *wd_packed, const void *split_images16, const float *image_scales,
+                                            const float *bias2, const float *bias3, const rtk_layer_t *wn, float *out, int out_pitch,
+                                            int workgroups, rtk_stream_t stream);
 /* rtk_sa_scale for the scales whose MLP is offset layer (c1 = 32 or 64 channels) + ONE layer c1 -> 64, nsample 16 or 32 (sa2 scale 1,
  * sa3 scales 0 and 1 of the PNHead): same arguments, the layer as its split image + inverse scale (rtk_pack_split_layer(64, c1, ...)) + fp32 bias.
  * (A sample whose q rows span 2^32 bytes or more, n * q_pitch * 4, is computed by the serial loop: same bits.) */

@@ -184,6 +184,9 @@ SIGNATURES = {
     "rtk_cost_volume_split_shared": [_i] * 3 + [_p] * 10 + [P(Layer), _p, _i, _i, _p],
     "rtk_cost_volume_split_gconst": [_i] * 3 + [_p] * 10 + [P(Layer), _p, _i, _i, _p],
     "rtk_cost_volume_split_term": [_i] * 3 + [_p] * 11 + [P(Layer), _p, _i, _i, _p],
+    "rtk_pack_split_layer16": [_i, _i, _p, _i, _p, _p, _p],
+    "rtk_cost_volume_split16_shared": [_i] * 3 + [_p] * 10 + [P(Layer), _p, _i, _i, _p],
+    "rtk_cost_volume_split16_term": [_i] * 3 + [_p] * 11 + [P(Layer), _p, _i, _i, _p],
     "rtk_sa_scale_split": [_i] * 4 + [_p] * 4 + [_i, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p],
     "rtk_sa_scale_split_serial": [_i] * 4 + [_p] * 4 + [_i, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p],
     "rtk_split_mlp2": [_i, _p, _p, _p, _p, _p, _p, _p],

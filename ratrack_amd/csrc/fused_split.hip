@@ -18,6 +18,9 @@ constexpr int CV_F = 32;
 
 // ---- packing: (cout x cin) row-major fp32 weights -> split image + the inverse of its power-of-two scale (split_mfma.h) ---------
 // Every workgroup scans the whole matrix for max|w| itself (at most 256 KiB, L2-resident: one launch, no atomics, no scratch).
+// TILE16: the fragment order of the 16-position tile (fused_common.h) -- 16-row blocks, k-steps of 32:
+// frag[up][v][p][lane = 16 g + i][t] = piece_p(2^k W[16 v + i][32 up + 16 (t / 4) + 4 g + t % 4]); the same scale, the same pieces.
+template <bool TILE16>
 __global__ __launch_bounds__(256) void pack_split_kernel(int cout, int cin, const float *__restrict__ w, int transposed, u4v *__restrict__ out,
                                                          float *__restrict__ inv_scale) {
     __shared__ unsigned s_m[4];
@@ -36,17 +39,19 @@ __global__ __launch_bounds__(256) void pack_split_kernel(int cout, int cin, cons
     mb = max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3]));
     const LaneScale sc = lane_scale_of(mb);
     if (blockIdx.x == 0 && threadIdx.x == 0) *inv_scale = sc.inv;
-    const int VB = cout / 32, slot = blockIdx.x * 256 + threadIdx.x;      // slot = (s, v, lane)
-    if (slot >= (cin / 16) * VB * 64) return;
+    const int VB = cout / (TILE16 ? 16 : 32), slot = blockIdx.x * 256 + threadIdx.x;      // slot = (s, v, lane)
+    if (slot >= (cin / (TILE16 ? 32 : 16)) * VB * 64) return;
     const int lane = slot & 63, v = (slot >> 6) % VB, s = (slot >> 6) / VB, hh = lane >> 5, i = lane & 31;
-    const int o = 32 * v + i, c0 = 32 * (s >> 1) + 16 * (s & 1) + 4 * hh;      // this slot: W[o][c0 .. c0 + 3], W[o][c0 + 8 .. c0 + 11]
+    // this slot: W[o][c0 .. c0 + 3], W[o][c0 + C1 .. c0 + C1 + 3]
+    constexpr int C1 = TILE16 ? 16 : 8;
+    const int o = TILE16 ? 16 * v + (lane & 15) : 32 * v + i, c0 = TILE16 ? 32 * s + 4 * (lane >> 4) : 32 * (s >> 1) + 16 * (s & 1) + 4 * hh;
     f4 x0, x1;
     if (transposed) {                                                          // W = w^T, w (cin, cout) row-major
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { x0[r] = w[(size_t)(c0 + r) * cout + o]; x1[r] = w[(size_t)(c0 + 8 + r) * cout + o]; }
+        for (int r = 0; r < 4; ++r) { x0[r] = w[(size_t)(c0 + r) * cout + o]; x1[r] = w[(size_t)(c0 + C1 + r) * cout + o]; }
     } else {
         const float *row = w + (size_t)o * cin + c0;
-        x0 = *reinterpret_cast<const f4 *>(row); x1 = *reinterpret_cast<const f4 *>(row + 8);
+        x0 = *reinterpret_cast<const f4 *>(row); x1 = *reinterpret_cast<const f4 *>(row + C1);
     }
     u4v b[2];
     split2(x0, x1, sc.s, b);
@@ -569,6 +574,284 @@ void cost_volume_split_kernel(const CvSplitParams P) {
         for (int v = 2; v < SPLIT_VB; ++v) out_block(v);
         pt = ptn; valid = validn; i = in_; nb = nbn; q0 = q0n; q1 = q1n;
         if (P.st) { q0 = add4_rn(q0n, s0n); q1 = add4_rn(q1n, s1n); }
+        dx = __fsub_rn(cn[0], cn[3]); dy = __fsub_rn(cn[1], cn[4]); dz = __fsub_rn(cn[2], cn[5]);
+    }
+    ws.finish();
+}
+
+// ---- the forward on the 16-position tile: two waves per SIMD ---------------------------------------------------------------------
+// The same operator on the same arithmetic pieces (layer 1 and the WeightNet's output layer on the fp32-input MFMA, layers 2 and 3 as
+// three fp16 products of two pieces under the position's power-of-two scale, fp32 accumulation), on the tile of fused_common.h: a
+// wave owns ONE query point x its 16 neighbours, lane = 16 g + j holds channels 16 u + 4 g + r of position j, the layers run on
+// v_mfma_f32_16x16x32_f16 over the image order of rtk_pack_split_layer16.  64 registers of activations and 64 accumulators instead of
+// 128 + 128: a wave fits in half a SIMD's register file, the workgroup has eight waves (eight points per iteration, as the 32-position
+// kernel) on one weight stream, and what one wave does outside the matrix pipe -- layer 1, the epilogues, the neighbour sum -- can run
+// under the other wave's MFMAs.  The price: every streamed fragment is read from LDS by eight waves for 16 positions each instead of
+// four waves for 32 (twice the fragment reads per MFMA).
+constexpr int CV16_NW = 8;
+constexpr int CV16_V = 16;                     // 16-channel blocks of 256 channels
+constexpr int CV16_KS = 8;                     // k-steps (32 input channels) of a 256-channel contraction
+constexpr int CV16_NF = CV16_KS * CV16_V * 2;  // fragments (KiB) of one 256 x 256 layer
+constexpr int CV16_ROWS_F4 = 16 * 32;          // f4 per wave: 16 positions x 32 slots of 16 bytes (half a gathered row per round)
+// Slot s of position p's 512 bytes holds source chunk s ^ p (CvRowsRequest); lane (g, j) reads chunk 4 u + g of position j.  The lanes a
+// ds_read_b128 serves together ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32) are 16 different positions at two values of g.
+constexpr int cv16_rows_slot(int pos, int chunk) { return pos * 32 + (chunk ^ pos); }
+constexpr bool cv16_rows_conflict_free() {
+    constexpr int served[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27}, {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
+    for (int u = 0; u < 8; ++u)
+        for (int half = 0; half < 2; ++half)
+            for (int grp = 0; grp < 2; ++grp) {
+                unsigned seen = 0u;
+                for (int k = 0; k < 16; ++k) {
+                    const int lane = 32 * half + served[grp][k], g = lane >> 4, j = lane & 15;
+                    const unsigned bankgroup = 1u << (cv16_rows_slot(j, 4 * u + g) & 15);
+                    if (seen & bankgroup) return false;
+                    seen |= bankgroup;
+                }
+            }
+    return true;
+}
+static_assert(cv16_rows_conflict_free(), "a ds_read_b128 of the staged rows must touch 16 different bank groups per lane group");
+static_assert(cv16_rows_slot(15, 31) < CV16_ROWS_F4, "a position's chunks stay inside its own 512 bytes");
+
+// The constants in the tile's layout: a lane's read is one ds_read at an immediate offset from lane * 4 (the A operands) or 16 g (the biases).
+struct CvConsts16 {
+    float wd[CV16_V * 64];            // A[i][k = g] of block v of [Wd | 0]: the packed offset image as it is
+    float wc[CV16_V * 2 * 64];        // ... of block v's two k-steps of Wc: k-slot g of step s is hidden channel 2 g + s (the eight live ones)
+    float bc[256], bias2[256], bias3[256];
+    float hid[128];                   // as CvConsts::hid
+};
+static_assert(sizeof(CvConsts16) == 15 * 1024 + 512, "4 + 8 + 3 KiB + the hidden layers");
+__device__ __forceinline__ void cv16_consts_fill(CvConsts16 &C, const float *wd, const WnSplit &W, const float *bias2, const float *bias3, int t) {
+    if (t < 256) *reinterpret_cast<f4 *>(C.wd + 4 * t) = ldc4(wd + 4 * t);
+    else if (t < 256 + 192) {
+        const int which = (t - 256) >> 6, l = t & 63;
+        *reinterpret_cast<f4 *>((which == 0 ? C.bc : which == 1 ? C.bias2 : C.bias3) + 4 * l) = ldc4((which == 0 ? W.bc : which == 1 ? bias2 : bias3) + 4 * l);
+    }
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const int e = 512 * n + t, v = e >> 7, s = (e >> 6) & 1, l = e & 63, k = 2 * (l >> 4) + s;
+        C.wc[e] = ldc(W.wc + ((v * 64 + 16 * (k >> 2) + (l & 15)) * 4 + (k & 3)));
+    }
+    if (t < 104) {
+        const int u = t < 32 ? 0 : t - 32, o = u >> 3, c = u & 7;
+        C.hid[t] = ldc(t < 32 ? W.wa + 16 * (t >> 3) + (t & 7) : t < 96 ? W.wb + (16 * (c >> 2) + o) * 4 + (c & 3) : W.bb + (t - 96));
+    }
+}
+
+// wn_hidden_lds in pieces: the same operations on the same values, but no more than 40 of the image's 104 words in registers at a time
+// (left to itself hipcc reads them all first -- next to the tile's 64 activations that is past the wave's half of the register file)
+__device__ __forceinline__ void cv16_wn_hidden(const CvConsts16 &C, float dx, float dy, float dz, float (&t2)[8]) {
+    float t1[8];
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+        float a = __fmaf_rn(C.hid[o], dx, 0.f);
+        a = __fmaf_rn(C.hid[8 + o], dy, a);
+        a = __fmaf_rn(C.hid[16 + o], dz, a);
+        t1[o] = fmaxf(__fadd_rn(a, C.hid[24 + o]), 0.f);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+        float a = C.hid[96 + o];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) a = __fmaf_rn(C.hid[32 + 8 * o + c], t1[c], a);
+        t2[o] = fmaxf(a, 0.f);
+        asm volatile("" : "+v"(t2[o]));      // computed HERE: sunk to its use in the output epilogue, the 64 weights would live across the layers
+        if (o % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// one round of the wave's 16 gathered rows: eight requests of two half rows each (CvRowsRequest: lanes 0..31 position 2 T, 32..63 position 2 T + 1)
+template <int HALF>
+__device__ __forceinline__ void cv16_rows_request(const float *p2, int nbrow, f4 *rows, int lane) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the previous round's reads have returned before their slots are overwritten
+    CvRowsRequest(p2, rows, nbrow, HALF, lane).all(std::make_integer_sequence<int, 8>{});
+}
+// this lane's eight slots of the round: channels 128 HALF + 16 u + 4 g .. + 3, u = 0..7
+template <int HALF>
+__device__ __forceinline__ void cv16_rows_read(const f4 *rows, int j, int g, f4 (&h)[CV16_V]) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) h[8 * HALF + u] = rows[j * 32 + ((4 * u + g) ^ j)];
+}
+// layer 1 of blocks U0 .. U0 + 7: leaky((q of block u + the gathered row) + Wd.d)
+template <int U0>
+__device__ __forceinline__ void cv16_layer1_blocks(const CvConsts16 &C, const f4 q, float bop, int lane, float kinf, f4 (&h)[CV16_V]) {
+    auto block = [&](auto uc) {
+        constexpr int u = decltype(uc)::value;
+        h[u] = leaky_med4(mfma4(C.wd[u * 64 + lane], bop, add_row_bcast<u>(q, h[u])), kinf);
+    };
+    block(std::integral_constant<int, U0>{}); block(std::integral_constant<int, U0 + 1>{});
+    block(std::integral_constant<int, U0 + 2>{}); block(std::integral_constant<int, U0 + 3>{});
+    block(std::integral_constant<int, U0 + 4>{}); block(std::integral_constant<int, U0 + 5>{});
+    block(std::integral_constant<int, U0 + 6>{}); block(std::integral_constant<int, U0 + 7>{});
+}
+
+// One group step of a layer on the 16-position tile: the four fragments (h and l piece) of two 16-row output blocks against the two B
+// pieces of the k-step, six MFMAs, the two blocks interleaved, small terms first (LayerStepS::mm, fused_common.h); the reads of the next
+// group and the splitting of the next k-step's activations sit between them (SplitStep, split_mfma.h).
+template <int FBASE, int GI, class WS, int F, bool ZERO>
+struct Split16Step {
+    static constexpr int GV = CV16_V / 2, NG = CV16_KS * GV;
+    template <int GJ, int PART>
+    static __device__ __forceinline__ void load_part(WS &ws, f4 (&dst)[SPLIT_GF]) {
+        constexpr int f0 = FBASE + GJ * SPLIT_GF;
+        if constexpr (PART == 0) {
+            if constexpr (f0 % F == 0 && f0 != 0) ws.sync();
+            if constexpr ((f0 % F) / SPLIT_GF < split_issue_groups(F)) ws.template issue_part<(f0 % F) / SPLIT_GF, split_issue_groups(F)>();
+        }
+        dst[2 * PART] = ws.template frag_async<(f0 + 2 * PART) % F>();
+        dst[2 * PART + 1] = ws.template frag_async<(f0 + 2 * PART + 1) % F>();
+    }
+    static __device__ __forceinline__ void run(WS &ws, const f4 (&h)[CV16_V], float scale, f4 (&acc)[CV16_V], f4 (&a)[2][SPLIT_GF], u4v (&b)[2][2]) {
+        constexpr int up = GI / GV, v0 = (GI % GV) * 2;
+        static_assert(F % SPLIT_GF == 0, "a group step reads four consecutive fragments of one chunk");
+        lds_wait<0>(a[GI & 1]);
+        const f4(&c)[SPLIT_GF] = a[GI & 1];
+        const u4v(&B)[2] = b[up & 1];
+        f4 z0, z1;
+        if constexpr (ZERO && up == 0) z0 = z1 = f4_zero();
+        else { z0 = acc[v0]; z1 = acc[v0 + 1]; }
+        acc[v0] = mfma16_h(__builtin_bit_cast(u4v, c[1]), B[0], z0);                    // l . h
+        acc[v0 + 1] = mfma16_h(__builtin_bit_cast(u4v, c[3]), B[0], z1);
+        if constexpr (GI + 1 < NG) load_part<GI + 1, 0>(ws, a[(GI + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+        acc[v0] = mfma16_h(__builtin_bit_cast(u4v, c[0]), B[1], acc[v0]);               // h . l
+        acc[v0 + 1] = mfma16_h(__builtin_bit_cast(u4v, c[2]), B[1], acc[v0 + 1]);
+        if constexpr (GI + 1 < NG) load_part<GI + 1, 1>(ws, a[(GI + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (up + 1 < CV16_KS && GI % GV < 4) split2_word_of<GI % GV>(h[2 * (up + 1)], h[2 * (up + 1) + 1], scale, b[(up + 1) & 1]);
+        acc[v0] = mfma16_h(__builtin_bit_cast(u4v, c[0]), B[0], acc[v0]);               // h . h
+        acc[v0 + 1] = mfma16_h(__builtin_bit_cast(u4v, c[2]), B[0], acc[v0 + 1]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+};
+template <int FBASE, class WS, int F, bool ZERO, int... GI>
+__device__ __forceinline__ void split16_layer_impl(WS &ws, const f4 (&h)[CV16_V], float scale, f4 (&acc)[CV16_V], std::integer_sequence<int, GI...>) {
+    f4 a[2][SPLIT_GF];
+    u4v b[2][2];
+    Split16Step<FBASE, 0, WS, F, ZERO>::template load_part<0, 0>(ws, a[0]);
+    Split16Step<FBASE, 0, WS, F, ZERO>::template load_part<0, 1>(ws, a[0]);
+    split2(h[0], h[1], scale, b[0]);
+    __builtin_amdgcn_sched_barrier(0);
+    (Split16Step<FBASE, GI, WS, F, ZERO>::run(ws, h, scale, acc, a, b), ...);
+}
+// acc = 2^(kw + kx) W . h for a 256 x 256 layer whose 16-position image starts at fragment FBASE of the stream; scale = this lane's 2^kx
+// (lane_scale16).  All waves of the workgroup call this together (the stream has barriers).
+template <int FBASE, int NW, int F, int NF>
+__device__ __forceinline__ void split16_layer(WStreamA<NW, F, NF> &ws, const f4 (&h)[CV16_V], float scale, f4 (&acc)[CV16_V]) {
+    split16_layer_impl<FBASE, WStreamA<NW, F, NF>, F, true>(ws, h, scale, acc, std::make_integer_sequence<int, CV16_KS * (CV16_V / 2)>{});
+}
+
+__global__ __launch_bounds__(64 * CV16_NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void cost_volume_split_kernel16(const CvSplitParams P) {
+    const float kinf = rtk_hidden_inf();
+    __shared__ __attribute__((aligned(16))) f4 s_w[2 * CV_F * 64];
+    __shared__ __attribute__((aligned(16))) f4 s_rows[CV16_NW * CV16_ROWS_F4];
+    __shared__ __attribute__((aligned(16))) CvConsts16 s_c;      // 64 + 64 + 15.5 KiB
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), g = lane >> 4, j = lane & 15;
+    f4 *rows = s_rows + wave * CV16_ROWS_F4;
+    constexpr int PPW = CV16_NW;                                    // points per workgroup iteration
+    const int groups = (P.n1 + PPW - 1) / PPW;
+    // tiles = (sample, group of eight points), dealt as in cost_volume_split_kernel: flat (P.gx > 0) or one sample per grid row
+    const bool flat = P.gx > 0;
+    const int xcd = blockIdx.x & 7, t0 = flat ? (int)(blockIdx.x >> 3) : (int)blockIdx.x, tstep = flat ? P.gx >> 3 : (int)gridDim.x;
+    const int ntiles = flat ? (P.samples >> 3) * groups : groups;
+    auto locate = [&](int t, int &b_, int &G_) {
+        if (flat) { const int sk = t / groups; b_ = sk * 8 + xcd; G_ = t - sk * groups; }
+        else { b_ = blockIdx.y; G_ = t; }
+    };
+    int b, bx;
+    locate(t0 < ntiles ? t0 : 0, b, bx);
+    cv16_consts_fill(s_c, P.wd, P.wn, P.bias2, P.bias3, (int)threadIdx.x);
+    WStreamA<CV16_NW, CV_F, 2 * CV16_NF> ws;
+    ws.start_parts(P.blob, s_w, wave, lane);                        // (its barrier publishes the constants too)
+    const float wi2 = ldc(P.wsc), wi3 = ldc(P.wsc + 1);
+    // Software-pipelined by one tile as the 32-position kernel: the next tile's neighbour index is requested at the top of the current
+    // tile, the first half of its gathered rows after layer 1, its direction and its p1 slot in the output epilogue.
+    bool valid = bx * PPW + wave < P.n1;
+    long i = (long)b * P.n1 + (valid ? bx * PPW + wave : P.n1 - 1);
+    long nb = 0;
+    float dx = 0.f, dy = 0.f, dz = 0.f;
+    f4 q = {0.f, 0.f, 0.f, 0.f};                                    // p1 slot j of this wave's point: channels 16 j + 4 g .. + 3
+    if (t0 < ntiles) {
+        nb = (long)b * P.n2 + (long)P.knn[i * 16 + j];
+        cv16_rows_request<0>(P.p2, (int)nb, rows, lane);
+        q = ldc4(P.p1 + i * 256 + 16 * j + 4 * g);
+        if (P.st) q = add4_rn(q, ldc4(P.st + b * 256 + 16 * j + 4 * g));
+        dx = __fsub_rn(P.xyz2[nb * 3], P.xyz1[i * 3]); dy = __fsub_rn(P.xyz2[nb * 3 + 1], P.xyz1[i * 3 + 1]);
+        dz = __fsub_rn(P.xyz2[nb * 3 + 2], P.xyz1[i * 3 + 2]);
+    }
+    for (int t = t0; t < ntiles; t += tstep) {
+        asm volatile("" ::: "memory");
+        // (the swizzled LDS addresses of the rows -- 16 reads, 16 request offsets -- are functions of the lane alone: computed from a
+        // copy the optimiser cannot see through, one v_xor each per tile, they are not kept in 32 registers across the loop)
+        int lv = lane;
+        asm volatile("" : "+v"(lv));
+        const int jv = lv & 15, gv = lv >> 4;
+        const bool more = t + tstep < ntiles;                       // (wave-uniform)
+        int bn, Gn;
+        locate(more ? t + tstep : t, bn, Gn);
+        const bool validn = Gn * PPW + wave < P.n1;
+        const long in_ = (long)bn * P.n1 + (validn ? Gn * PPW + wave : P.n1 - 1);
+        long knn_next = 0;
+        if (more) knn_next = (long)P.knn[in_ * 16 + j];
+        // layer 1: leaky(p1[i] + p2[nb] + Wd.d)     (bias folded into p1, or into the per-sample term)
+        f4 h[CV16_V];
+        float t2[8];
+        {
+            const float bop = g == 0 ? dx : g == 1 ? dy : g == 2 ? dz : 0.f;      // B[k = g][j]; k = 3 is the image's zero column
+            cv16_rows_read<0>(rows, jv, gv, h);
+            cv16_rows_request<1>(P.p2, (int)nb, rows, lv);
+            cv16_layer1_blocks<0>(s_c, q, bop, lane, kinf, h);
+            cv16_wn_hidden(s_c, dx, dy, dz, t2);      // the WeightNet's hidden layers while round 1 of the rows arrives
+            __builtin_amdgcn_sched_barrier(0);
+            cv16_rows_read<1>(rows, jv, gv, h);
+            cv16_layer1_blocks<8>(s_c, q, bop, lane, kinf, h);
+        }
+        const long nbn = (long)bn * P.n2 + knn_next;
+        if (more) cv16_rows_request<0>(P.p2, (int)nbn, rows, lv);      // lands under layers 2 and 3
+        f4 acc[CV16_V];
+        LaneScale sc = lane_scale16(h);
+        split16_layer<0>(ws, h, sc.s, acc);
+        float c = sc.inv * wi2;
+#pragma unroll
+        for (int v = 0; v < CV16_V; ++v) h[v] = leaky_med4(scale_bias4(acc[v], c, *reinterpret_cast<const f4 *>(s_c.bias2 + 16 * v + 4 * g)), kinf);
+        sc = lane_scale16(h);
+        split16_layer<CV16_NF>(ws, h, sc.s, acc);
+        ws.sync();                                                   // wrap the stream to chunk 0
+        c = sc.inv * wi3;
+#pragma unroll
+        for (int v = 0; v < CV16_V; ++v) h[v] = leaky_med4(scale_bias4(acc[v], c, *reinterpret_cast<const f4 *>(s_c.bias3 + 16 * v + 4 * g)), kinf);
+        // ---- next tile: its direction and its p1 slot, under the output epilogue ------------------------------------------------
+        float cn[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        f4 qn = q, sn = q;
+        if (more) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { cn[k] = ldc(P.xyz2 + nbn * 3 + k); cn[3 + k] = ldc(P.xyz1 + in_ * 3 + k); }
+            qn = ldc4(P.p1 + in_ * 256 + 16 * j + 4 * g);
+        }
+        if (more && P.st) sn = ldc4(P.st + bn * 256 + 16 * j + 4 * g);
+        // out[i] = sum over the 16 neighbours of relu(Wc.t2 + bc) * a3: K = 8 as two k-steps of the fp32-input MFMA (k-slot g of step s
+        // = hidden channel 2 g + s), four 16-channel blocks per transposing reduction (lane j ends with block 4 m + 2 (bit 3) + (bit 2))
+        const float tb0 = g == 0 ? t2[0] : g == 1 ? t2[2] : g == 2 ? t2[4] : t2[6], tb1 = g == 0 ? t2[1] : g == 1 ? t2[3] : g == 2 ? t2[5] : t2[7];
+        float *o = P.out + i * P.out_pitch + 4 * g + 16 * (2 * ((j >> 3) & 1) + ((j >> 2) & 1));
+#pragma unroll
+        for (int m = 0; m < CV16_V / 4; ++m) {
+            f4 r[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int v = 4 * m + e;
+                f4 w = *reinterpret_cast<const f4 *>(s_c.bc + 16 * v + 4 * g);
+                w = mfma4(s_c.wc[(2 * v) * 64 + lane], tb0, w);
+                w = mfma4(s_c.wc[(2 * v + 1) * 64 + lane], tb1, w);
+                r[e] = relu_med4(w, kinf) * h[v];
+            }
+            const f4 s = row_sum16_transpose4(r[0], r[1], r[2], r[3]);
+            if (valid && (j & 3) == 0) *reinterpret_cast<f4 *>(o + 64 * m) = s;
+        }
+        valid = validn; i = in_; nb = nbn; q = qn;
+        if (P.st) q = add4_rn(qn, sn);
         dx = __fsub_rn(cn[0], cn[3]); dy = __fsub_rn(cn[1], cn[4]); dz = __fsub_rn(cn[2], cn[5]);
     }
     ws.finish();
@@ -1205,8 +1488,17 @@ extern "C" int rtk_pack_split_layer(int cout, int cin, const float *w, int trans
     RTK_REQUIRE(cout > 0 && cin > 0 && cout % 32 == 0 && cin % 32 == 0 && w && image && inv_scale, "pack_split_layer: bad arguments");
     RTK_REQUIRE((long)cout * cin <= (1L << 22), "pack_split_layer: more than 2^22 weights (every workgroup scans the matrix for its scale)");
     const int slots = (cin / 16) * (cout / 32) * 64;
-    pack_split_kernel<<<(slots + 255) / 256, 256, 0, (hipStream_t)stream>>>(cout, cin, w, transposed, (u4v *)image, inv_scale);
+    pack_split_kernel<false><<<(slots + 255) / 256, 256, 0, (hipStream_t)stream>>>(cout, cin, w, transposed, (u4v *)image, inv_scale);
     RTK_CHECK_LAUNCH("pack_split_layer");
+    return RTK_OK;
+}
+
+extern "C" int rtk_pack_split_layer16(int cout, int cin, const float *w, int transposed, void *image, float *inv_scale, rtk_stream_t stream) {
+    RTK_REQUIRE(cout > 0 && cin > 0 && cout % 32 == 0 && cin % 32 == 0 && w && image && inv_scale, "pack_split_layer16: bad arguments");
+    RTK_REQUIRE((long)cout * cin <= (1L << 22), "pack_split_layer16: more than 2^22 weights (every workgroup scans the matrix for its scale)");
+    const int slots = (cin / 32) * (cout / 16) * 64;
+    pack_split_kernel<true><<<(slots + 255) / 256, 256, 0, (hipStream_t)stream>>>(cout, cin, w, transposed, (u4v *)image, inv_scale);
+    RTK_CHECK_LAUNCH("pack_split_layer16");
     return RTK_OK;
 }
 
@@ -1253,7 +1545,7 @@ static int cv_split_forward(const char *who, int samples, int n1, int n2, const 
                             const float *p1, const float *p2, const float *wd_packed, const void *split_images, const float *image_scales,
                             const float *bias2, const float *bias3, const rtk_layer_t *wn, float *out, int out_pitch, float *a1, float *a2,
                             float *a3, void *mask1, void *mask2, float *amax, int workgroups, rtk_stream_t stream,
-                            const float *sample_term = nullptr, bool global_consts = false) {
+                            const float *sample_term = nullptr, bool global_consts = false, bool tile16 = false) {
     CvSplitParams P;
     dim3 grid;
     if (cv_split_fill(who, P, samples, n1, n2, xyz1, xyz2, knn_idx, split_images, image_scales, wn, grid) != RTK_OK) return RTK_ERR_INVALID;
@@ -1273,7 +1565,9 @@ static int cv_split_forward(const char *who, int samples, int n1, int n2, const 
         P.gx = 8 * per_xcd;
         grid = dim3(P.gx);
     }
-    if (save) cost_volume_split_kernel<true><<<grid, 64 * SP_NW, 0, (hipStream_t)stream>>>(P);
+    static_assert(2 * SP_NW == CV16_NW, "both tiles take eight points per workgroup iteration: one grid rule");
+    if (tile16) cost_volume_split_kernel16<<<grid, 64 * CV16_NW, 0, (hipStream_t)stream>>>(P);
+    else if (save) cost_volume_split_kernel<true><<<grid, 64 * SP_NW, 0, (hipStream_t)stream>>>(P);
     else if (global_consts) cost_volume_split_kernel<false, false><<<grid, 64 * SP_NW, 0, (hipStream_t)stream>>>(P);
     else cost_volume_split_kernel<false><<<grid, 64 * SP_NW, 0, (hipStream_t)stream>>>(P);
     RTK_CHECK_LAUNCH(who);
@@ -1313,6 +1607,26 @@ extern "C" int rtk_cost_volume_split_term(int samples, int n1, int n2, const flo
     RTK_REQUIRE(workgroups >= 0 && sample_term, "cost_volume_split_term: workgroups = %d, sample_term = %p", workgroups, (const void *)sample_term);
     return cv_split_forward("cost_volume_split_term", samples, n1, n2, xyz1, xyz2, knn_idx, p1, p2, wd_packed, split_images, image_scales,
                             bias2, bias3, wn, out, out_pitch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workgroups, stream, sample_term);
+}
+
+extern "C" int rtk_cost_volume_split16_shared(int samples, int n1, int n2, const float *xyz1, const float *xyz2, const int64_t *knn_idx,
+                                              const float *p1, const float *p2, const float *wd_packed, const void *split_images16,
+                                              const float *image_scales, const float *bias2, const float *bias3, const rtk_layer_t *wn,
+                                              float *out, int out_pitch, int workgroups, rtk_stream_t stream) {
+    RTK_REQUIRE(workgroups >= 0, "cost_volume_split16_shared: workgroups = %d", workgroups);
+    return cv_split_forward("cost_volume_split16_shared", samples, n1, n2, xyz1, xyz2, knn_idx, p1, p2, wd_packed, split_images16, image_scales,
+                            bias2, bias3, wn, out, out_pitch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workgroups, stream, nullptr, false,
+                            true);
+}
+
+extern "C" int rtk_cost_volume_split16_term(int samples, int n1, int n2, const float *xyz1, const float *xyz2, const int64_t *knn_idx,
+                                            const float *p1, const float *p2, const float *sample_term, const float *wd_packed,
+                                            const void *split_images16, const float *image_scales, const float *bias2, const float *bias3,
+                                            const rtk_layer_t *wn, float *out, int out_pitch, int workgroups, rtk_stream_t stream) {
+    RTK_REQUIRE(workgroups >= 0 && sample_term, "cost_volume_split16_term: workgroups = %d, sample_term = %p", workgroups, (const void *)sample_term);
+    return cv_split_forward("cost_volume_split16_term", samples, n1, n2, xyz1, xyz2, knn_idx, p1, p2, wd_packed, split_images16, image_scales,
+                            bias2, bias3, wn, out, out_pitch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workgroups, stream, sample_term,
+                            false, true);
 }
 
 extern "C" int rtk_cost_volume_split_train(int samples, int n1, int n2, const float *xyz1, const float *xyz2, const int64_t *knn_idx,

@@ -670,6 +670,11 @@ class Geometry:
 
 
 CV_SPLIT_MAX_ROWS = 1 << 22      # rtk_cost_volume_split*: rows of p2 per launch (csrc/fused_split.hip)
+# The inference forward's cost-volume kernel: False = the 32-position tile, one wave per SIMD (rtk_cost_volume_split_shared / _term);
+# True = the 16-position tile, two waves per SIMD (rtk_cost_volume_split16_shared / _term).  Same operator, same arithmetic pieces.
+# On by default: faster at every measured configuration (profiles/cv_tile16_ab_same_box.txt).  RTK_CV_TILE16=0 in the environment
+# selects the 32-position kernel for a whole process (the suite, bench.py) without touching either.
+CV_TILE16 = os.environ.get("RTK_CV_TILE16", "1") == "1"
 
 
 def cv_shared_workgroups(samples, n1, dev):
@@ -813,6 +818,12 @@ class FusedBackbone:
         for l, w in enumerate(w23):
             _lib.call("rtk_pack_split_layer", 256, 256, w.data_ptr(), 0, self.cv_images[l * SPLIT_IMAGE_256:].data_ptr(),
                       self.cv_scales[l:].data_ptr(), _stream())
+        # ... and in the fragment order of the 16-position tile (CV_TILE16): the same pieces, the same scales
+        self.cv_images16 = torch.empty(2 * SPLIT_IMAGE_256, dtype=torch.int16, device=dev)
+        scales16 = torch.empty(2, dtype=torch.float32, device=dev)
+        for l, w in enumerate(w23):
+            _lib.call("rtk_pack_split_layer16", 256, 256, w.data_ptr(), 0, self.cv_images16[l * SPLIT_IMAGE_256:].data_ptr(),
+                      scales16[l:].data_ptr(), _stream())
         torch.cuda.current_stream().synchronize()      # w23 may go
         self.wn1 = _WeightNet(sd, "fc_layer.weightnet1", dev)
         self.wn2 = _WeightNet(sd, "fc_layer.weightnet2", dev)
@@ -957,14 +968,16 @@ class FusedBackbone:
                 nb = min(step, B - b0)
                 wgs = cv_shared_workgroups(nb, N, x1.device) if self.cv_shared else 0
                 r0 = b0 * N
+                images = self.cv_images16 if CV_TILE16 else self.cv_images
                 if sample_term is not None:
-                    _lib.call("rtk_cost_volume_split_term", nb, N, N, x1[b0:].data_ptr(), x2[b0:].data_ptr(), knn1[b0:].data_ptr(),
+                    _lib.call("rtk_cost_volume_split16_term" if CV_TILE16 else "rtk_cost_volume_split_term", nb, N, N, x1[b0:].data_ptr(), x2[b0:].data_ptr(), knn1[b0:].data_ptr(),
                               p1[r0:].data_ptr(), p2[r0:].data_ptr(), sample_term[b0:].data_ptr(), self.cv_wd.data_ptr(),
-                              self.cv_images.data_ptr(), self.cv_scales.data_ptr(), self.cv_bias23[0].data_ptr(), self.cv_bias23[1].data_ptr(),
+                              images.data_ptr(), self.cv_scales.data_ptr(), self.cv_bias23[0].data_ptr(), self.cv_bias23[1].data_ptr(),
                               self.wn1.arr, cor1[r0:].data_ptr(), 256, wgs, _stream())
                     continue
-                _lib.call("rtk_cost_volume_split_shared", nb, N, N, x1[b0:].data_ptr(), x2[b0:].data_ptr(), knn1[b0:].data_ptr(), p1[r0:].data_ptr(),
-                          p2[r0:].data_ptr(), self.cv_wd.data_ptr(), self.cv_images.data_ptr(), self.cv_scales.data_ptr(),
+                _lib.call("rtk_cost_volume_split16_shared" if CV_TILE16 else "rtk_cost_volume_split_shared", nb, N, N, x1[b0:].data_ptr(),
+                          x2[b0:].data_ptr(), knn1[b0:].data_ptr(), p1[r0:].data_ptr(),
+                          p2[r0:].data_ptr(), self.cv_wd.data_ptr(), images.data_ptr(), self.cv_scales.data_ptr(),
                           self.cv_bias23[0].data_ptr(), self.cv_bias23[1].data_ptr(), self.wn1.arr, cor1[r0:].data_ptr(), 256, wgs, _stream())
             return
         _lib.call("rtk_cost_volume", B, N, N, x1.data_ptr(), x2.data_ptr(), knn1.data_ptr(), p1.data_ptr(), p2.data_ptr(),
