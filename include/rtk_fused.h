@@ -556,6 +556,63 @@ RTK_EXPORT int rtk_track_memory_motion(int B, int K, int max_age, float beta, co
 /* The largest K (max_objects) the batched association accepts: its per-stream table must fit one workgroup's LDS. */
 RTK_EXPORT int rtk_track_max_objects(void);
 
+/* ---- The result log (csrc/track_results.hip, ratrack_amd/result_log.py): a tracked step's result file kept on the device ---------
+ * A result file holds, per object of a frame in association order, its confidence, its track id and the xyz of its points in column
+ * order (BatchedTracker.write_results).  The log keeps exactly that per stream, packed, with per-frame offsets and cursors that live on
+ * the device, so that a step appends without a host round trip (a captured append replays correctly) and everything is downloaded once.
+ * F frames, R records and P points per stream bound the memory.  Zero-initialised by the caller; only rtk_result_log_append writes it. */
+#define RTK_RESULT_MAX_OBJECTS 256   /* object slots of a frame: RTK_SCORE_MAX_OBJECTS, the frame word's 16-bit count and the scan's width */
+#define RTK_RESULT_FLAG_OBJECTS 1    /* a num_objects outside [0, K]: the frame was not logged */
+#define RTK_RESULT_FLAG_STEP 2       /* the step's flags word had bit 0 or bit 1 set (object overflow, bad n_valid): not logged */
+#define RTK_RESULT_FLAG_FULL 4       /* the frame needed more than what is left of F, R or P: not logged at all */
+#define RTK_RESULT_FLAG_TRACKS 8     /* rtk_result_log_select: more track ids in one clip than the track table holds (2048) */
+
+typedef struct {
+    int F, R, P;
+    int *cursor;                  /* (B,4) frames | records | points logged so far | unused (never written) */
+    int *frame;                   /* (B,F,4) first record | first point | P_f + 65536 * (the frame began a clip) | 0: rtk_score_log_t's word */
+    int *tag;                     /* (B,F,4) seq | index | points of the frame | the step's flags word */
+    int *rec_track;               /* (B,R) per object, in order: its track id */
+    float *rec_conf;              /* (B,R) its object_conf */
+    int *rec_hits;                /* (B,R) its object_hits, 0 when the step has none */
+    int *rec_size;                /* (B,R) its point count */
+    float *points;                /* (B,P,3) xyz, object after object, inside an object in increasing column */
+    int *flags;                   /* (B) sticky: RTK_RESULT_FLAG_OBJECTS | _STEP | _FULL */
+} rtk_result_log_t;
+
+/* rtk_result_log_append: one workgroup per stream.  pc1 (B,3,N) read in place, obj (B,N), num_objects (B), object_ids / object_conf
+ * (B,K); object_hits (B,K), step_flags (B), reset (B), active (B) may be NULL (hits 0 / flags 0 / no clip mark / every stream active);
+ * seq, index (B) int32 DEVICE words read at launch time.  Per active stream b with P_f = num_objects[b]:
+ *   refusals   P_f outside [0, K]: RTK_RESULT_FLAG_OBJECTS; step_flags[b] & 3: RTK_RESULT_FLAG_STEP (both where both hold); else a
+ *              frame that needs a frame slot, P_f records or its points beyond F / R / P: RTK_RESULT_FLAG_FULL.  A refused frame
+ *              writes nothing but the flag and moves no cursor.
+ *   records    record j < P_f = (object_ids[j], object_conf[j], object_hits[j] or 0, size_j), size_j the columns p with obj[b][p] == j.
+ *   points     the xyz of those columns, object after object in j order, inside an object in increasing p (a STABLE grouping; columns
+ *              with obj outside [0, P_f) belong to nothing; an object may be empty).
+ *   frame      (first record, first point, P_f + 65536 * (reset[b] != 0), 0), tag (seq[b], index[b], points, step_flags[b] or 0);
+ *              the three cursors advance.  An inactive stream changes no word.
+ * Every word has one writer and plain stores: the same bits on every run; nothing at or beyond the new cursors is touched.  Static LDS:
+ * a counter per (wave, object slot), 4 KiB.  K <= RTK_RESULT_MAX_OBJECTS; B * N, B * 4 F, B * R and B * 3 P below 2^31. */
+RTK_EXPORT int rtk_result_log_append(int B, int N, int K, const rtk_bcn_view_t *pc1, const int *obj, const int *num_objects,
+                                     const int *object_ids, const float *object_conf, const int *object_hits, const int *step_flags,
+                                     const int *seq, const int *index, const unsigned char *reset, const unsigned char *active,
+                                     const rtk_result_log_t *log, rtk_stream_t stream);
+
+/* rtk_result_log_select: which records a result file keeps.  One workgroup per stream; reads the log, writes its four outputs.
+ *   clip       a maximal run of the stream's logged frames in which only the first may carry the clip mark.
+ *   track      a (stream, clip, track id); n_t its records in the clip; its score the float64 sum of their fp32 rec_conf in log order
+ *              divided by (double)n_t: rtk_score_track_means' score (rtk_score.h, "the confidence sweep"), the same bits.
+ *   keep       1 iff !(score < tau) && (min_hits <= 1 || rec_hits >= min_hits) && n_t >= min_track_frames; tau = *threshold when
+ *              threshold (a DEVICE scalar) is not NULL, else threshold_value (-infinity keeps every score).  min_hits = 1 asks nothing,
+ *              as in BatchedTracker.write_results: a frame logged without hit counts holds rec_hits = 0 and is not emptied by it.
+ * keep (B,R) uint8, track_score (B,R) float64, track_frames (B,R) int32 are written for the records below the stream's cursor only.
+ * flags (B) is WRITTEN: 0, or RTK_RESULT_FLAG_TRACKS for a stream with a clip of more track ids than the table holds (2048, a clip
+ * within a wave's width of that may be refused too); the outputs of that clip and of the stream's later clips are then not written.
+ * The log is walked with the scorer's clamps (csrc/score_log_walk.h), so a foreign buffer is never read out of bounds. */
+RTK_EXPORT int rtk_result_log_select(int B, const rtk_result_log_t *log, const double *threshold, double threshold_value, int min_hits,
+                                     int min_track_frames, unsigned char *keep, double *track_score, int *track_frames, int *flags,
+                                     rtk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,11 @@ class TrackFrame(ctypes.Structure):
                 ("active", _p)]
 
 
+class ResultLog(ctypes.Structure):
+    _fields_ = [("F", _i), ("R", _i), ("P", _i)] + [(n, _p) for n in ("cursor", "frame", "tag", "rec_track", "rec_conf", "rec_hits", "rec_size",
+                                                                      "points", "flags")]
+
+
 # ---- include/rtk_gt.h -----------------------------------------------------------------------------------------------------------
 
 class GtBoxes(ctypes.Structure):
@@ -142,6 +147,7 @@ class PwWgradJob(ctypes.Structure):
 STRUCTS = {
     "rtk_src_t": Src, "rtk_layer_t": Layer, "rtk_interp_t": Interp, "rtk_gterm_job_t": GtermJob, "rtk_copy_job_t": CopyJob,
     "rtk_layout_job_t": LayoutJob, "rtk_bcn_view_t": View, "rtk_track_frame_t": TrackFrame,
+    "rtk_result_log_t": ResultLog,
     "rtk_gt_boxes_t": GtBoxes, "rtk_gt_in_t": GtIn, "rtk_gt_out_t": GtOut, "rtk_eval_in_t": EvalIn,
     "rtk_gt_objects_in_t": GtObjectsIn, "rtk_gt_objects_out_t": GtObjectsOut, "rtk_track_score_in_t": ScoreIn,
     "rtk_track_score_state_t": ScoreState, "rtk_track_score_out_t": ScoreOut, "rtk_score_log_t": ScoreLog,
@@ -151,7 +157,7 @@ STRUCTS = {
 }
 
 # name -> argtypes.  A struct pointer that callers pass as ctypes.addressof() is _p; one they pass as an array or byref() is typed.
-# The argument blocks of rtk_gt.h and rtk_score.h (GtIn, GtOut, EvalIn, GtObjectsIn, ..., ScoreOut, ScoreLog, ScoreMemory, ScorePairs) and rtk_track_frame_t go by
+# The argument blocks of rtk_gt.h and rtk_score.h (GtIn, GtOut, EvalIn, GtObjectsIn, ..., ScoreOut, ScoreLog, ScoreMemory, ScorePairs), rtk_track_frame_t and rtk_result_log_t go by
 # address; the *_lds_bytes are host functions that return a byte count.
 SIGNATURES = {
     # ---- include/rtk_pointnet2.h
@@ -215,6 +221,8 @@ SIGNATURES = {
     "rtk_track_memory": [_i] * 3 + [_p] * 21 + [_p],
     "rtk_track_memory_motion": [_i] * 3 + [_f] + [_p] * 24 + [_p],
     "rtk_track_max_objects": [],
+    "rtk_result_log_append": [_i] * 3 + [_p] * 12 + [_p],
+    "rtk_result_log_select": [_i, _p, _p, _d, _i, _i, _p, _p, _p, _p, _p],
     # ---- include/rtk_gt.h
     "rtk_gt_labels": [_p, _p, _p],
     "rtk_eval_frame": [_p, _p, _p, _p],
