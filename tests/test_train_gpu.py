@@ -528,7 +528,8 @@ def test_captured_collective_survives_twenty_replays():
 def test_fused_sa_chain_matches_unfused_operators(chans, ns, U, n_src, groups):
     """The fused set-abstraction chain (first-layer kernel, conv+BN kernels, MFMA weight gradient, two-pass backward) against
     the same chain built from bn_relu + framework convolutions, on odd sizes (positions not a multiple of 64, dead rows,
-    two statistics groups): output, gradients of the projection input and of every parameter, running statistics."""
+    two statistics groups): output, gradients of the projection input and of every parameter, running statistics.
+    (Where the chain meets float64, at the project's rule: tests/test_sa_chain_f64_gpu.py.)"""
     import copy
     import types
     from ratrack_amd import train_path as TP
