@@ -613,6 +613,59 @@ RTK_EXPORT int rtk_result_log_select(int B, const rtk_result_log_t *log, const d
                                      int min_track_frames, unsigned char *keep, double *track_score, int *track_frames, int *flags,
                                      rtk_stream_t stream);
 
+/* ---- Oriented boxes (csrc/track_boxes.hip, csrc/box_fit.h, ratrack_amd/boxes.py): position, size and heading of a tracked object -----
+ * The box of an object is the minimum-area rectangle around its points in the bird's-eye view (x, y), with the points' z range for
+ * its height.  THE FITTING RULE.  An object is its n points in the order the result log keeps them (increasing column); coordinates
+ * are the fp32 values widened to float64, all arithmetic is float64, and every product, sum, quotient and square root is rounded on
+ * its own (no FMA).
+ *   extremes    min and max pick one of the values; an extreme that is a zero of either sign is taken as +0 (x + 0.0), so that no
+ *               order of comparisons shows in a bit.
+ *   empty       n == 0: the eight box words are 0, valid = 0, cand = -1.  Any coordinate (x, y or z) that is not finite: the eight
+ *               words are 0, valid = -1, cand = -1.
+ *   height      cz = (zmin + zmax) / 2, h = max(zmax - zmin, min_extent).
+ *   candidates  directions d = (d_x, d_y).  Candidate 0 is (1, 0).  Candidate c = 1 + rank(i, j) belongs to the pair i < j, the pairs
+ *               in lexicographic order (rank(i, j) = i (2 n - i - 1) / 2 + j - i - 1), with d = (x_j - x_i, y_j - y_i).  A pair with
+ *               q = d_x d_x + d_y d_y == 0 is skipped and keeps its index.  The pairs are a superset of the hull's edges, so the
+ *               smallest area among them is that of the minimum-area enclosing rectangle.
+ *   area        s_k = d_x x_k + d_y y_k, t_k = d_x y_k - d_y x_k; S = max s - min s, T = max t - min t; area = (S T) / q.  Nothing
+ *               is normalised before the comparison: for small-integer inputs every term is exact.
+ *   winner      the smallest area; among equal areas the smallest c.  A function of the points alone, not of how the work is split.
+ *   box         r = sqrt(q), len_s = S / r, len_t = T / r; ms = (smin + smax) / 2, mt = (tmin + tmax) / 2;
+ *               cx = (ms d_x - mt d_y) / q, cy = (ms d_y + mt d_x) / q; yaw = atan2(d_y, d_x).  If len_t > len_s the two lengths are
+ *               swapped and yaw = yaw + PI / 2 (the box has no front).  Then while yaw >= PI / 2: yaw = yaw - PI, and while
+ *               yaw < -PI / 2: yaw = yaw + PI (PI the float64 nearest pi): yaw lies in [-pi/2, pi/2).
+ *               l = max(the longer, min_extent), w = max(the shorter, min_extent).
+ *   output      box = (cx, cy, cz, l, w, h, yaw, area), eight float64 words, area the winner's before any padding; cand (int32) the
+ *               winner; valid (int32) n, 0 for an empty object, -1 for one with a coordinate that is not finite.
+ *   cap         an object of more than RTK_BOX_MAX_POINTS points is fitted with candidate 0 alone -- the axis-aligned box, cand = 0
+ *               -- and RTK_BOX_FLAG_AXIS is set in its stream's flags word.  A record costs at most 8 128 candidates x 128 points.
+ * min_extent is a finite number >= 0 (else the call is refused).  Except for yaw (atan2 is not correctly rounded) every word is a
+ * correctly rounded function of the points. */
+#define RTK_BOX_MAX_POINTS 128       /* points of an object the candidate search takes: 2 KiB of (x, y) per wave */
+#define RTK_BOX_FLAG_AXIS 1          /* an object above RTK_BOX_MAX_POINTS was fitted axis-aligned */
+#define RTK_BOX_FLAG_OBJECTS 2       /* rtk_object_boxes: a num_objects outside [0, K]: nothing of the stream was fitted */
+
+/* rtk_result_log_boxes: the box of every record below each stream's cursors.  One workgroup of four waves per stream; a wave takes
+ * frames in turn and, inside a frame, record after record.  keep: NULL, or (B,R) uint8 (rtk_result_log_select's): only the records it
+ * marks are fitted, the others are written as empty (eight zeros, cand = -1, valid = 0).  box (B,R,8) float64, cand (B,R) int32,
+ * valid (B,R) int32 are written for the records below the stream's cursor only; nothing at or beyond it is touched.  flags (B) is
+ * WRITTEN: 0 or RTK_BOX_FLAG_AXIS -- one record above the cap raises it for its stream.  The log is walked with the scorer's clamps
+ * (csrc/score_log_walk.h) and every size is clamped to the points logged, so a foreign buffer is never read out of bounds.  No
+ * allocation, no synchronisation; every word has one writer and plain stores: the same bits on every run.  Static LDS: 8 KiB. */
+RTK_EXPORT int rtk_result_log_boxes(int B, const rtk_result_log_t *log, const unsigned char *keep, double min_extent, double *box,
+                                    int *cand, int *valid, int *flags, rtk_stream_t stream);
+
+/* rtk_object_boxes: the same for a live step.  pc1 (B,3,N) read in place, obj (B,N), num_objects (B); object j < num_objects[b] is
+ * the columns p with obj[b][p] == j in increasing p (rtk_result_log_append's grouping: what the log would hold for the step, so the
+ * two entry points give a step's objects the same bits).  box (B,K,8), cand (B,K), valid (B,K): all K rows of every stream are
+ * written, rows j >= num_objects[b] and every row of an inactive stream (active (B) uint8, may be NULL) as empty.  A num_objects
+ * outside [0, K] is refused as rtk_result_log_append refuses it: RTK_BOX_FLAG_OBJECTS and K empty rows.  flags (B) is WRITTEN.
+ * K <= RTK_RESULT_MAX_OBJECTS, B * N below 2^31.  One workgroup of four waves per stream; a wave takes objects in turn and scans the
+ * stream's N columns for each.  No allocation, no synchronisation, one writer per word. */
+RTK_EXPORT int rtk_object_boxes(int B, int N, int K, const rtk_bcn_view_t *pc1, const int *obj, const int *num_objects,
+                                const unsigned char *active, double min_extent, double *box, int *cand, int *valid, int *flags,
+                                rtk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

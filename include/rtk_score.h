@@ -502,8 +502,8 @@ RTK_EXPORT int rtk_score_identity_pairs(int B, int T, const rtk_score_log_t *log
  *      TrackScorer(similarity="centre")) ----------------------------------------------------------------------------------------------
  *
  * The two sections above say that what still does not agree with TrackEval is the similarity: a point IoU where TrackEval has a box IoU.
- * A box IoU will never be available here -- the detections are point clusters without boxes -- but TrackEval has a second similarity
- * for detections that are positions, _calculate_euclidean_similarity: sim = max(0, 1 - |a - b| / zero_distance), zero_distance = 2.0 by
+ * A box IoU is not built here -- the detections have boxes (rtk_fused.h, "Oriented boxes"), the pair log carries none -- but TrackEval
+ * has a second similarity for detections that are positions, _calculate_euclidean_similarity: sim = max(0, 1 - |a - b| / zero_distance), zero_distance = 2.0 by
  * default.  This section writes the pair log under that similarity and replays it with the four kernels above, unchanged in every other
  * respect.  The point IoU is harsh on radar clusters of two to five points (one missed point halves it); this one asks whether the
  * detection sits on its object.  DEPARTURES FROM TrackEval AFTER THIS: the 28-bit assignment weights, and the positions, which are point

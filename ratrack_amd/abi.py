@@ -223,6 +223,8 @@ SIGNATURES = {
     "rtk_track_max_objects": [],
     "rtk_result_log_append": [_i] * 3 + [_p] * 12 + [_p],
     "rtk_result_log_select": [_i, _p, _p, _d, _i, _i, _p, _p, _p, _p, _p],
+    "rtk_result_log_boxes": [_i, _p, _p, _d] + [_p] * 4 + [_p],
+    "rtk_object_boxes": [_i] * 3 + [_p] * 4 + [_d] + [_p] * 4 + [_p],
     # ---- include/rtk_gt.h
     "rtk_gt_labels": [_p, _p, _p],
     "rtk_eval_frame": [_p, _p, _p, _p],

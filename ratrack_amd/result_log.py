@@ -20,7 +20,10 @@ score `TrackScorer.sweep` reports its operating point in, the same bits -- and t
 `!(score < threshold)`, `rec_hits >= min_hits` (from 2 on; 1 asks nothing, as in `write_results`) and
 `length >= min_track_frames`: files at the sweep's operating point, and short tracks dropped whole, their first frames included.
 
-Only `write`, `frames`, `check`, `download` and `select(check=True)` synchronise.  `seq` / `index` given as host values cost one small
+`boxes` (rtk_result_log_boxes, ratrack_amd/boxes.py) fits every record's oriented box in one launch, and `write_kitti` writes them, for
+the records a selection keeps, as KITTI tracking result files, one per sequence: the format the evaluators of the field read.
+
+Only `write`, `write_kitti`, `frames`, `check`, `download` and `select(check=True)` synchronise.  `seq` / `index` given as host values cost one small
 host-to-device copy per append; given as (B,) int32 device tensors they are read at launch time and cost nothing.
 
 With a `TrackerPipeline` use one ResultLog per group and append under `torch.cuda.stream(pipe.streams[g])` before group g's next
@@ -187,6 +190,46 @@ def host_frames(host, b, keep=None):
     return out
 
 
+def check_transforms(host, transforms, streams=None):
+    """Every logged frame of `host` has its entry in `transforms` ((seq, index) -> vod_gt.FrameTransforms; None asks nothing);
+    raises ValueError naming the first that has not."""
+    if transforms is None:
+        return
+    for b, f, seq, index in logged_frames(host, streams):
+        if (seq, index) not in transforms:
+            raise ValueError("ResultLog: frame %d of stream %d is (seq=%d, index=%d), and transforms has no entry for it" % (f, b, seq, index))
+
+
+def kitti_rows(host, keep=None, transforms=None, obj_type="Car", streams=None):
+    """{seq: [(frame index, track id, obj_type, vod_io.KittiFields, score), ...]}: the lines of every sequence's KITTI tracking result
+    file, in (index, record) order -- one per kept record that has a box (host["box_valid"] > 0), its score the record's confidence.
+    host: `download(boxes=...)`'s dict.  transforms: None (radar-frame values, ry = yaw) or (seq, index) -> FrameTransforms.  Raises
+    ValueError before anything is rendered for two logged frames with one (seq, index) or a frame that `transforms` misses."""
+    from . import vod_io
+    seen = {}
+    for b, f, seq, index in logged_frames(host, streams):
+        if (seq, index) in seen:
+            raise ValueError("ResultLog: frame %d of stream %d and frame %d of stream %d are both (seq=%d, index=%d): one frame number for "
+                             "two frames" % (seen[(seq, index)][1], seen[(seq, index)][0], f, b, seq, index))
+        seen[(seq, index)] = (b, f)
+    check_transforms(host, transforms, streams)
+    rows = {}
+    for (seq, index), (b, f) in sorted(seen.items(), key=lambda kv: (kv[0][0], kv[0][1])):
+        out = rows.setdefault(seq, [])
+        rec, count = int(host["frame"][b, f, 0]), int(host["frame"][b, f, 2]) & 0xffff
+        tf = None if transforms is None else transforms[(seq, index)]
+        for r in range(rec, rec + count):
+            if (keep is not None and not keep[b, r]) or host["box_valid"][b, r] <= 0:
+                continue
+            fields = vod_io.box_label_fields(host["box"][b, r, :7], tf)
+            out.append((index, int(host["rec_track"][b, r]), obj_type, fields, float(host["rec_conf"][b, r])))
+    return rows
+
+
+def kitti_path(root, names, seq):
+    return os.path.join(root, str(names[seq]) + ".txt")
+
+
 # ---- the device half ------------------------------------------------------------------------------------------------------------
 
 class Selection:
@@ -307,11 +350,13 @@ class ResultLog:
         return sel
 
     # ---- the way out ----------------------------------------------------------------------------------------------------------------
-    def download(self, selection=None):
+    def download(self, selection=None, boxes=None):
         """-> (host, keep, flags): the live prefix of the log as a dict of numpy arrays (`write_frames`' argument), the selection's keep
         (B,records) uint8 or None, and the sticky flags or-ed with the selection's.  Two transfers whatever the frame count: the
-        cursors and flags, then everything below the largest cursors in one concatenation."""
-        head = [self.cursor.reshape(-1), self.flags] + ([] if selection is None else [selection.flags])
+        cursors and flags, then everything below the largest cursors in one concatenation.  boxes (`boxes()`'s result): its rows
+        travel in the same two transfers and join host as box (B,records,8) float64, box_cand, box_valid (B,records) int32 and
+        box_flags (B) int32 (kept apart from `flags`: a box flag refuses no frame)."""
+        head = [self.cursor.reshape(-1), self.flags] + ([] if selection is None else [selection.flags]) + ([] if boxes is None else [boxes.flags])
         head = torch.cat(head).cpu().numpy()
         B = self.B
         cursor, flags = head[:4 * B].reshape(B, 4).copy(), head[4 * B:5 * B].copy()
@@ -323,6 +368,8 @@ class ResultLog:
                  ("points", self.points[:, :p].reshape(B, -1).view(torch.int32))]
         if selection is not None:
             parts.append(("keep", selection.keep[:, :r].to(torch.int32)))
+        if boxes is not None:
+            parts += [("box", boxes.box[:, :r].reshape(B, -1).view(torch.int32)), ("box_cand", boxes.cand[:, :r]), ("box_valid", boxes.valid[:, :r])]
         flat = torch.cat([t.reshape(-1) for _, t in parts]).cpu().numpy()
         host, o = dict(cursor=cursor), 0
         for name, t in parts:
@@ -331,6 +378,9 @@ class ResultLog:
         host["rec_conf"] = host["rec_conf"].view(np.float32)
         host["points"] = host["points"].view(np.float32).reshape(B, p, 3)
         keep = host.pop("keep").astype(np.uint8) if selection is not None else None
+        if boxes is not None:
+            host["box"] = host["box"].view(np.float64).reshape(B, r, 8)
+            host["box_flags"] = head[-B:].copy() if B else head[:0].copy()
         return host, keep, flags
 
     def _selected(self, threshold, min_hits, min_track_frames):
@@ -346,6 +396,56 @@ class ResultLog:
         if check:
             raise_on_flags(flags.tolist(), self.K)
         return write_frames(root, names, host, keep, [b for b in range(self.B) if not flags[b]])
+
+    # ---- boxes ------------------------------------------------------------------------------------------------------------------
+    def boxes(self, keep=None, min_extent=0.0, into=None):
+        """The oriented box of every logged record (ratrack_amd/boxes.py; rtk_result_log_boxes): one launch, no synchronisation,
+        -> boxes.ObjectBoxes with one row per record slot, written below each stream's records cursor only (zero elsewhere).  keep:
+        None, a `Selection` or its (B,R) uint8 `keep`: the records it does not mark get no box (valid = 0).  into: an ObjectBoxes of
+        (B,R) rows to write into instead of new buffers (nothing is allocated: the call can be captured)."""
+        from . import boxes as _boxes
+        min_extent = _boxes.check_min_extent(min_extent)
+        keep = getattr(keep, "keep", keep)
+        dev = self.cursor.device
+        if keep is not None:
+            if not torch.is_tensor(keep) or tuple(keep.shape) != (self.B, self.R) or keep.dtype not in (torch.uint8, torch.bool):
+                raise ValueError("ResultLog.boxes: keep must be a (%d,%d) uint8 tensor (Selection.keep)" % (self.B, self.R))
+            keep = keep.to(device=dev).contiguous()
+            keep = keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+        if into is not None:
+            out = _boxes.check_into(into, self.B, self.R, dev)
+        else:
+            out = _boxes.ObjectBoxes(torch.zeros(self.B, self.R, 8, dtype=torch.float64, device=dev),
+                                     torch.zeros(self.B, self.R, dtype=torch.int32, device=dev),
+                                     torch.zeros(self.B, self.R, dtype=torch.int32, device=dev), torch.zeros(self.B, dtype=torch.int32, device=dev))
+        lg = self._block()
+        _lib.call("rtk_result_log_boxes", self.B, ctypes.addressof(lg), None if keep is None else keep.data_ptr(), min_extent,
+                  out.box.data_ptr(), out.cand.data_ptr(), out.valid.data_ptr(), out.flags.data_ptr(), _stream())
+        return out
+
+    def write_kitti(self, root, names, transforms=None, obj_type="Car", threshold=None, min_hits=1, min_track_frames=1, min_extent=0.0,
+                    check=True):
+        """KITTI tracking result files (vod_io.format_kitti_track_line), one per sequence: <root>/<names[seq]>.txt with one line per
+        kept record that has a box, in (index, record) order; the frame number is the frame's index, the score the record's confidence.
+        `select` runs with the given filters (when one is given), `boxes` on what it keeps, then everything is downloaded once.
+        transforms: None -- the radar-frame values as they are, ry = yaw -- or a mapping (seq, index) -> vod_gt.FrameTransforms: the
+        label fields of the camera frame (vod_io.box_label_fields); a logged frame without an entry raises ValueError before any file
+        is written.  check=True raises RuntimeError naming the stream for any flag of the log or of the selection before anything is
+        written; check=False writes the streams without one.  A stream with an object above boxes.MAX_POINTS points is written, its
+        box axis-aligned, with a warning.  Returns the paths."""
+        import warnings
+        from . import boxes as _boxes, vod_io
+        _boxes.check_min_extent(min_extent)
+        sel = self._selected(threshold, min_hits, min_track_frames)
+        host, keep, flags = self.download(sel, boxes=self.boxes(sel, min_extent))
+        if check:
+            raise_on_flags(flags.tolist(), self.K)
+        streams = [b for b in range(self.B) if not flags[b]]
+        rows = kitti_rows(host, keep, transforms, obj_type, streams)
+        for b in streams:
+            if host["box_flags"][b]:
+                warnings.warn(_boxes.flag_message(b, int(host["box_flags"][b]), self.R))
+        return [vod_io.write_kitti_tracks(kitti_path(root, names, seq), rows[seq]) for seq in sorted(rows)]
 
     def frames(self, b, threshold=None, min_hits=1, min_track_frames=1):
         """[(seq, index, [(track id, conf, points (n,3) float64), ...]), ...] of stream b: per logged frame what

@@ -122,8 +122,9 @@ through the clip over a one-frame intruder with a slightly larger IoU.  Identity
 counts, not only a detection's best object.  `threshold=` removes detections before anything else, the alignment pass included.  WHAT
 NOW AGREES WITH TrackEval is the arrangement of both metrics and, under `similarity="centre"` (below), the similarity as well; WHAT
 STILL DOES NOT is the 28-bit weights and, under "centre", the positions, which are point centroids rather than label-box centres.
-Under the default `similarity="iou"` the similarity is the reference's point IoU -- TrackEval's other similarity, a box IoU, will never
-be available here: the detections are point clusters without boxes.  The defaults (`matching="greedy"`, `pairs="best"`) are the calls
+Under the default `similarity="iou"` the similarity is the reference's point IoU.  TrackEval's other similarity is a box IoU: the
+detections now have boxes (ratrack_amd/boxes.py fits one per object on the device), but a box-IoU similarity on the pair log is not
+built yet -- `pair_sim` and the `*_sim` replays take any similarity.  The defaults (`matching="greedy"`, `pairs="best"`) are the calls
 above with their launches and bits.
 
 The centre-distance similarity.  `TrackScorer(..., sweep_pairs=Q, similarity="centre", zero_distance=2.0)` writes the pair log under

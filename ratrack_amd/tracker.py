@@ -125,7 +125,12 @@ class StepResult:
     own buffer, overwritten when `table_ids` is.
     With `BatchedTracker(assign="optimal")` (else None): assign_total (B,) int64: the weight of the stream's matching, the sum of
     (int)(aff * 2^28) over its matched pairs; 0 where nothing was associated (no previous or no current objects); an inactive stream
-    keeps the value of its last active frame (0 before the first) -- the tracker's own buffer, overwritten by the next step."""
+    keeps the value of its last active frame (0 before the first) -- the tracker's own buffer, overwritten by the next step.
+    With `BatchedTracker(boxes=True)` (else None): object_boxes (B,K,8) float64: the oriented box of object j, (cx, cy, cz, l, w, h,
+    yaw, area) in the sensor frame (ratrack_amd/boxes.py; zeros past num_objects and on an inactive stream); object_box_valid (B,K)
+    int32: the object's point count (0: no object, -1: a coordinate that is not finite); object_box_cand (B,K) int32: the winning
+    candidate of the search (-1: no box); object_box_flags (B) int32: boxes.FLAG_AXIS where an object above boxes.MAX_POINTS points was
+    fitted axis-aligned."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -235,7 +240,7 @@ class BatchedTracker:
 
     def __init__(self, net, streams, max_objects=128, iters=500, alpha=0.9, eps=1.5, threshold=0.5, train_mode=False,
                  static_state=False, graph=False, graph_warmup=2, engine=None, max_age=None, motion=None, motion_beta=1.0,
-                 assign="sinkhorn", min_affinity=0.01):
+                 assign="sinkhorn", min_affinity=0.01, boxes=False, box_min_extent=0.0):
         """train_mode: accept a train-mode net -- for a caller that runs the backbone itself and uses `associate` and the state only
         (track_train.SequenceTrainer); `step()` stays the eval-mode path.
         static_state: this frame's objects are always written to slot 0 of `desc` / `ids` / `count` and the previous objects read
@@ -269,7 +274,16 @@ class BatchedTracker:
         have; `iters` and `alpha` are ignored.  The same number of launches, the same outputs: graph, static_state, max_age, motion,
         TrackerPipeline and write_results work unchanged.  `StepResult.assign_total` (B,) int64 is that sum per stream.
         min_affinity in [0.01, 1] (needs assign="optimal"): the gate below which a pair is never matched; the default 0.01 is the
-        reference's confidence threshold.  Both are launch constants, like max_age."""
+        reference's confidence threshold.  Both are launch constants, like max_age.
+        boxes: False (default): the tracker as it is without the keyword, the same launches and outputs; `StepResult.object_boxes`,
+        `object_box_valid`, `object_box_cand` and `object_box_flags` are None.  True: one more launch after the association
+        (rtk_object_boxes, ratrack_amd/boxes.py; inside the captured graph under `graph=True`) fits every object's oriented box:
+        `StepResult.object_boxes` (B,K,8) float64, `boxes.object_boxes(out)`'s.  box_min_extent: the least length, width and height
+        of a box, a finite number >= 0 (needs boxes=True to be anything but 0).  A launch constant, like max_age."""
+        from .boxes import check_min_extent
+        self.boxes, self.box_min_extent = bool(boxes), check_min_extent(box_min_extent)
+        if not self.boxes and self.box_min_extent != 0.0:
+            raise ValueError("box_min_extent=%r without boxes=True: there is no box to pad" % (box_min_extent,))
         if max_age is not None and (isinstance(max_age, bool) or not isinstance(max_age, int) or max_age < 0):
             raise ValueError("max_age=%r: None (no track memory) or an integer >= 0 (frames a lost track is kept)" % (max_age,))
         check_motion(motion, motion_beta, max_age, "max_age")
@@ -451,12 +465,17 @@ class BatchedTracker:
                       self.age[cur].data_ptr(), self.hits[cur].data_ptr(), self.n_det[cur].data_ptr(), self.count[cur].data_ptr(),
                       desc.data_ptr(), flags.data_ptr(), memory["object_hits"].data_ptr(), memory["object_gap"].data_ptr(),
                       memory["num_coasted"].data_ptr(), st)
+        fitted = dict(object_boxes=None, object_box_valid=None, object_box_cand=None, object_box_flags=None)
+        if self.boxes:
+            from .boxes import object_boxes_raw
+            bx = object_boxes_raw(pc1, obj, num, K, active=active, min_extent=self.box_min_extent)
+            fitted.update(object_boxes=bx.box, object_box_valid=bx.valid, object_box_cand=bx.cand, object_box_flags=bx.flags)
         if not self.static_state:
             self.cur = prev                # this frame's objects are the next frame's previous objects: a swap, not a copy
         out = StepResult(flow=flow, cls=cls, h=self.h, point_track_id=point_track_id, num_objects=num, object_ids=object_ids,
                          object_conf=object_conf, _indices1=indices1, aff=aff, num_prev=num_prev, flags=flags, labels=labels, obj=obj,
                          descriptors=desc, desc_prev=desc_prev, active=active, pc1=pc1, feature1=feature1, prop=prop, max_objects=K, _cache=None,
-                         assign_total=assign_total, **memory)
+                         assign_total=assign_total, **memory, **fitted)
         self.last = out
         return out
 

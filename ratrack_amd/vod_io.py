@@ -10,10 +10,18 @@
   authors' AB3DMOT-style evaluation.  Numbers are written with Python's repr of the float32 value promoted to float, as the
   reference's str(float(t)) does, so files compare byte for byte.
 
+* boxes: KITTI tracking result files, one per sequence, one line per tracked object and frame,
+      <frame> <track id> <type> -1 -1 -10 -1 -1 -1 -1 <h> <w> <l> <x> <y> <z> <ry> <score>
+  (truncation, occlusion, alpha and the image box are not estimated), the format the KITTI tracking devkit, AB3DMOT, TrackEval's KITTI
+  loaders and the VoD devkit read.  `box_label_fields` takes a box fitted in the radar frame (ratrack_amd/boxes.py) to the label
+  fields of the camera frame: the inverse of `vod_gt.box_in_radar_frame`.
+
 Host-side code (numpy / file I/O); not part of the GPU path.  GT generation (tracking labels, oriented boxes, GT flow and object
 mappings from the VoD label / calibration / pose files) is ratrack_amd/vod_gt.py.
 """
+import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -81,4 +89,65 @@ def read_track_results(path):
             assert tok[:4] == ["NA", "1", "-1", "-1"], "not a RaTrack result line: %r" % line[:40]
             pts = np.array([float(v) for v in tok[6:]], dtype=np.float64).reshape(-1, 3)
             out.append((int(tok[5]), float(tok[4]), pts))
+    return out
+
+
+# ---- boxes: KITTI tracking result files ----------------------------------------------------------------------------------------
+
+KittiFields = namedtuple("KittiFields", "h w l x y z ry")
+
+
+def box_label_fields(box7, tf=None):
+    """box7 = (cx, cy, cz, l, w, h, yaw) in the radar frame (float64) -> KittiFields, the inverse of `vod_gt.box_in_radar_frame`:
+    (x, y, z) = t_camera_radar . (cx, cy, cz, 1); with A = tf.t_radar_lidar[:3,:3],
+    phi = atan2(sin yaw A00 - cos yaw A10, cos yaw A11 - sin yaw A01) and ry = -phi - pi/2 wrapped into [-pi, pi) -- so that the box
+    `box_in_radar_frame` builds from the fields, R = A . Rz(phi), has its first axis along `yaw` in the bird's-eye view (modulo pi: a
+    fitted box has no front), exactly, whatever tilt the extrinsics carry; h, w, l pass through.  tf None: the radar-frame values as
+    they are, ry = yaw."""
+    cx, cy, cz, l, w, h, yaw = (float(v) for v in box7)
+    if tf is None:
+        return KittiFields(h, w, l, cx, cy, cz, yaw)
+    x, y, z = (np.asarray(tf.t_camera_radar, dtype=np.float64) @ np.array([cx, cy, cz, 1.0]))[:3]
+    A = np.asarray(tf.t_radar_lidar, dtype=np.float64)
+    s, c = math.sin(yaw), math.cos(yaw)
+    phi = math.atan2(s * A[0, 0] - c * A[1, 0], c * A[1, 1] - s * A[0, 1])
+    ry = -phi - math.pi / 2
+    while ry >= math.pi:
+        ry -= 2 * math.pi
+    while ry < -math.pi:
+        ry += 2 * math.pi
+    return KittiFields(h, w, l, float(x), float(y), float(z), ry)
+
+
+def format_kitti_track_line(frame, track_id, obj_type, fields, score):
+    """One line of a KITTI tracking result file; every real number is written with repr(float), the shortest text that reads back
+    as the same float64."""
+    if not obj_type or len(str(obj_type).split()) != 1:
+        raise ValueError("obj_type=%r: one word" % (obj_type,))
+    parts = [str(int(frame)), str(int(track_id)), str(obj_type), "-1", "-1", "-10", "-1", "-1", "-1", "-1"]
+    parts += [repr(float(v)) for v in fields] + [repr(float(score))]
+    return " ".join(parts) + "\n"
+
+
+def write_kitti_tracks(path, rows):
+    """rows: [(frame, track id, type, KittiFields, score), ...] in the file's order -> `path` (its directory is made).  Returns path."""
+    text = "".join(format_kitti_track_line(*row) for row in rows)
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "w+") as f:
+        f.write(text)
+    return path
+
+
+def read_kitti_tracks(path):
+    """-> [(frame, track id, type, KittiFields, score), ...] -- the inverse of write_kitti_tracks, every float with its bits."""
+    out = []
+    with open(path) as f:
+        for line in f:
+            tok = line.split()
+            if not tok:
+                continue
+            assert len(tok) == 18 and tok[3:10] == ["-1", "-1", "-10", "-1", "-1", "-1", "-1"], "not a box result line: %r" % line[:60]
+            out.append((int(tok[0]), int(tok[1]), tok[2], KittiFields(*(float(v) for v in tok[10:17])), float(tok[17])))
     return out
