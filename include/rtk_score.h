@@ -502,8 +502,8 @@ RTK_EXPORT int rtk_score_identity_pairs(int B, int T, const rtk_score_log_t *log
  *      TrackScorer(similarity="centre")) ----------------------------------------------------------------------------------------------
  *
  * The two sections above say that what still does not agree with TrackEval is the similarity: a point IoU where TrackEval has a box IoU.
- * A box IoU is not built here -- the detections have boxes (rtk_fused.h, "Oriented boxes"), the pair log carries none -- but TrackEval
- * has a second similarity for detections that are positions, _calculate_euclidean_similarity: sim = max(0, 1 - |a - b| / zero_distance), zero_distance = 2.0 by
+ * The box IoU is the next section's (the detections have boxes: rtk_fused.h, "Oriented boxes"); this one is the similarity TrackEval
+ * has for detections that are positions, _calculate_euclidean_similarity: sim = max(0, 1 - |a - b| / zero_distance), zero_distance = 2.0 by
  * default.  This section writes the pair log under that similarity and replays it with the four kernels above, unchanged in every other
  * respect.  The point IoU is harsh on radar clusters of two to five points (one missed point halves it); this one asks whether the
  * detection sits on its object.  DEPARTURES FROM TrackEval AFTER THIS: the 28-bit assignment weights, and the positions, which are point
@@ -568,6 +568,75 @@ RTK_EXPORT int rtk_score_identity_pairs_sim(int B, int T, const rtk_score_log_t 
                                             const double *rec_score /* (B,R) or NULL */, const double *threshold /* device scalar, or NULL */,
                                             const double *alphas /* device, (count) */, int count, long long *counters /* (count,B,6) */,
                                             int *flags /* (B) */, rtk_stream_t stream);
+
+/* ---- The oriented-box IoU on the pair log, in three dimensions and in the bird's-eye view (csrc/track_score_box.hip,
+ *      TrackScorer(similarity="box") / TrackScorer(similarity="box_bev")) --------------------------------------------------------------
+ *
+ * The evaluators the result files are written for (the KITTI devkit, AB3DMOT, TrackEval's loaders, the VoD devkit) match detections to
+ * label boxes by a box overlap.  This section writes the pair log under that overlap -- between the box rtk_object_boxes fits to each
+ * detection and the label box of each kept object -- and replays it with the four *_sim kernels above, unchanged.  DEPARTURES FROM
+ * TrackEval AFTER THIS: the 28-bit assignment weights; THE UPRIGHT READING of the label box (below); and the detections' boxes, which
+ * are fitted from their points (a minimum-area rectangle, not a regressed box).
+ *
+ * All arithmetic is float64, every operation rounded on its own, no contraction.  Per active stream b and frame, with P detections
+ * and G kept objects as in rtk_track_score:
+ *   detection    box i < P is row i of rtk_object_boxes' output for the same step: det_box (B,Kobj,8) float64 = cx, cy, cz, l, w, h, yaw,
+ *                area; det_valid (B,Kobj) int32.  The detection HAS A BOX iff det_valid > 0, its first seven words are finite, l > 0 and
+ *                w > 0, and under RTK_SCORE_BOX_3D also h > 0.  A detection without a box has no pairs: a cluster of two points, or of
+ *                collinear points, fitted with min_extent = 0 has w = 0 and therefore none (fit with a positive min_extent).  L = 0.5 * l,
+ *                W = 0.5 * w; the footprint is the l x w rectangle about (cx, cy) with its length along (c, s) = (cos yaw, sin yaw); its
+ *                z range is [cz - 0.5 * h, cz + 0.5 * h].  (The device's sincos and sqrt are the compiler's expansions: not correctly
+ *                rounded, which is why pair_sim is compared within a bound -- DESIGN section 4.9.)
+ *   object       box j < G is entry gt_slot[b][j] of gt_boxes (B,K,16) float64, the frame-1 table of rtk_gt_boxes_t (centre | R | half-
+ *                extent): the box whose membership test defined the object; a merged rider does not change it.  It is read UPRIGHT IN
+ *                THE RADAR FRAME: u = (R[0][0], R[1][0]), n = sqrt(u.x * u.x + u.y * u.y), heading (hx, hy) = (u.x / n, u.y / n);
+ *                footprint 2 h0 x 2 h1 about (c.x, c.y), a = h0 along the heading and b = h1 across; z range [c.z - h2, c.z + h2].  A
+ *                slot outside [0, K), n == 0 or not finite, a half-extent that is not > 0, or one of the eight words read that is not
+ *                finite: the object has no pairs.  THE DEPARTURE: the label box carries the radar-lidar calibration's small tilt
+ *                (arccos(R[2][2]), about half a degree on the VoD calibration); the upright reading drops it, and the centre's z is
+ *                whatever the table holds -- one reason the bird's-eye-view variant exists.
+ *   prefilter    (part of the definition) dx = cx - c.x, dy = cy - c.y; ri = sqrt(L * L + W * W), rj = sqrt(a * a + b * b),
+ *                rr = ri + rj; a pair with (dx * dx + dy * dy) > rr * rr has s = 0.
+ *   z overlap    (RTK_SCORE_BOX_3D only) zo = min(top_i, top_j) - max(bottom_i, bottom_j); zo <= 0: s = 0.
+ *   frame        coordinates relative to the object's centre, in the object's own frame: D = (dx * hx + dy * hy, dy * hx - dx * hy),
+ *                E = (ex, ey) = (c * hx + s * hy, s * hx - c * hy), E' = (-ey, ex).  The detection's corners, counter-clockwise:
+ *                D + LE + WE', D - LE + WE', D - LE - WE', D + LE - WE' with LE = (L * ex, L * ey) and WE' = (-(W * ey), W * ex), each
+ *                coordinate (D + LE) then WE', in that order of additions.  The object's rectangle there is |x| <= a, |y| <= b.
+ *   cut          Sutherland-Hodgman: the detection's outline is cut by the four half-planes x <= a, x >= -a, y <= b, y >= -b in this
+ *                order.  The outline is kept as directed edges in eight slots: the four edges corner k -> corner k + 1 in slots 0..3,
+ *                and slot 4 + k for the edge cut k adds.  Cut k, with sigma(P) = a - P.x, P.x + a, b - P.y, P.y + b, looks at every
+ *                edge P0 -> P1 present, in slot order: both ends have sigma >= 0: it stays; both have sigma < 0: it goes; otherwise
+ *                t = sigma(P0) / (sigma(P0) - sigma(P1)) and the crossing point X has its cut coordinate SET TO THE BOUND ITSELF (a,
+ *                -a, b, -b) and the other one P0 + t * (P1 - P0) (that coordinate's); an edge that leaves (sigma(P0) >= 0) ends at X,
+ *                an edge that comes back starts at X.  If an edge left and an edge came back, slot 4 + k is the edge from the point
+ *                where the outline left to the point where it came back (of several, the last in slot order).  Every crossing point is
+ *                formed once and serves both edges that meet in it, so edges that nearly coincide with a bound cost rounding, not
+ *                area; boxes touching along an edge or at a corner have I2 = 0 exactly when they are parallel to the axes.
+ *   I2           Green's theorem: acc = the sum, from 0.0 in slot order, over the edges present of (P0.x * P1.y - P1.x * P0.y);
+ *                I2 = 0.5 * acc.  With yaw = 0, R = identity and dyadic coordinates and extents every operation up to here is exact.
+ *   value        A_i = l * w, A_j = (2a) * (2b).  BEV: s = I2 / ((A_i + A_j) - I2).  3D: I3 = I2 * zo, V_i = A_i * h,
+ *                V_j = A_j * (top_j - bottom_j), s = I3 / ((V_i + V_j) - I3).  Then s = min(s, 1.0): unlike the point IoU, a box IoU
+ *                above 1 is only rounding.
+ *   logging      the pair (i, j) is logged iff s > 0.0; a NaN is not logged.  Order, pair_key, pair_common (which may be 0), rec_size,
+ *                label_size, frame_pair, the cursor, the whole-frame fit rule and RTK_SCORE_FLAG_LOG are those of
+ *                rtk_track_score_pairs_centre, and the replays' validity rule is the centre section's: a log written here goes to the
+ *                *_sim replays with its pair_sim.  */
+#define RTK_SCORE_BOX_3D 0
+#define RTK_SCORE_BOX_BEV 1
+
+/* rtk_track_score_pairs, bit for bit -- every counter, state tensor, output and tensor of the main log -- in the same single launch,
+ * with the pair log written by the rules above.  Thread j stages kept object j's upright box in LDS; the P G decisions s > 0 are spread
+ * over the workgroup's 256 threads, each raising a bit of its row's 64-bit mask in LDS (an integer OR); thread i then writes row i's
+ * pairs behind the ordered prefix of the rows' pair counts, forming each s again by the same operations: one writer per word of the
+ * log, plain stores, no floating-point atomics, the same bits on every run.  LDS: rtk_track_score_box_lds_bytes -- the figure of rtk_track_score_lds_bytes /
+ * rtk_track_score_memory_lds_bytes rounded up to 8 bytes, plus 64 K + 16 (eight float64 per kept object, the mode and the stream's
+ * pair_sim address).  Refuses a NULL pair_sim, det_box, det_valid or gt_boxes and a mode that is neither of the two. */
+RTK_EXPORT int rtk_track_score_box_lds_bytes(int Kobj, int K, int N, int memory /* 0: no track memory */);
+RTK_EXPORT int rtk_track_score_pairs_box(const rtk_track_score_in_t *in, const rtk_track_score_state_t *state, const rtk_track_score_out_t *out,
+                                         const rtk_score_log_t *log, const rtk_score_memory_t *mem /* NULL: no track memory */,
+                                         const rtk_score_pairs_t *pairs, double *pair_sim /* (B,Q) */, const double *det_box /* (B,Kobj,8) */,
+                                         const int *det_valid /* (B,Kobj) */, const double *gt_boxes /* (B,K,16) */, int mode,
+                                         rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -252,6 +252,8 @@ SIGNATURES = {
     "rtk_score_identity_pairs": [_i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p],
     "rtk_track_score_centre_lds_bytes": [_i, _i, _i, _i],
     "rtk_track_score_pairs_centre": [_p, _p, _p, _p, _p, _p, _p, _p, _d, _p],
+    "rtk_track_score_box_lds_bytes": [_i, _i, _i, _i],
+    "rtk_track_score_pairs_box": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p],
     "rtk_score_replay_optimal_sim": [_i, _i, _p, _p, _p, _p, _p, _p, _i, _d, _p, _p, _p, _p, _p, _p],
     "rtk_score_alignment_sim": [_i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "rtk_score_hota_optimal_sim": [_i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],

@@ -1,7 +1,7 @@
 // track_score_body.h -- the LDS layout, the body and the argument checks of the scoring kernels: rtk_track_score and
 // rtk_track_score_logged (track_score.hip), rtk_track_score_memory (track_score_memory.hip), rtk_track_score_pairs
-// (track_score_pairs.hip) and rtk_track_score_pairs_centre (track_score_centre.hip) instantiate the one body, each kernel behind a
-// __global__ wrapper of its own in the file of its entry point.
+// (track_score_pairs.hip), rtk_track_score_pairs_centre (track_score_centre.hip) and rtk_track_score_pairs_box (track_score_box.hip)
+// instantiate the one body, each kernel behind a __global__ wrapper of its own in the file of its entry point.
 #pragma once
 #include <math.h>
 
@@ -30,6 +30,13 @@ static inline size_t ts_score_centre_lds(int Kobj, int K, int N, bool memory) {
     return ((base + 7) & ~(size_t)7) + ((size_t)3 * K + 2) * sizeof(double);
 }
 
+// the box variant keeps, 8-byte aligned behind either layout: gbox[K][8] f64, the kept objects' upright boxes (centre x, y | heading x, y |
+// half length, half width (half length 0: no box) | bottom, top) | the mode (64 bits) | the address of the stream's part of pair_sim
+static inline size_t ts_score_box_lds(int Kobj, int K, int N, bool memory) {
+    const size_t base = memory ? ts_score_memory_lds(Kobj, K, N) : ts_score_lds(Kobj, K, N);
+    return ((base + 7) & ~(size_t)7) + ((size_t)8 * K + 2) * sizeof(double);
+}
+
 // The body of the scoring kernels.  LOG: the frame is also appended to the stream's log (rtk_score_log_t) -- thread i writes
 // detection i's record where it finds its pre-greedy best object, thread j the j-th kept label id, thread 0 the frame's slot and the
 // cursors; a frame that does not fit writes nothing and raises RTK_SCORE_FLAG_LOG.  Without LOG `lg` is not read.
@@ -41,12 +48,18 @@ static inline size_t ts_score_centre_lds(int Kobj, int K, int N, bool memory) {
 // scal[4..7], one barrier more) gives every row its place and the frame its pair count, which joins the fit test; thread i then writes
 // its row's pairs and its size, thread j the j-th kept object's size, thread 0 the frame's slot and the cursor.  Without PAIRS `pr` is
 // not read and the body is what it was.
-// CENTRE (only with PAIRS): the pair log's similarity is TrackEval's centre-distance similarity (include/rtk_score.h, the last section)
+// CENTRE (only with PAIRS): the pair log's similarity is TrackEval's centre-distance similarity (include/rtk_score.h, its section)
 // -- every live column keeps its detection index in pts[p].w, thread i forms detection i's centre in ascending column order in
 // registers (N broadcast reads of LDS), decides row i's pairs once (s > 0, a 64-bit mask over the kept objects) where PAIRS counts
 // common > 0, and writes key, common and s behind the same ordered prefix; the kept objects' positions are G broadcast reads of LDS,
 // where they, zero_distance and the stream's pair_sim address are put at the start (ts_score_centre_lds: 24 K + 16 bytes more).
 // Without CENTRE the three arguments are not read and the body is what it was.
+// BOX (only with PAIRS, never with CENTRE): the pair log's similarity is the oriented-box IoU (include/rtk_score.h, the last section) in
+// CENTRE's arrangement -- thread j stages kept object j's upright box in LDS at the start (ts_score_box_lds: 64 K + 16 bytes more, the
+// mode and the stream's pair_sim address among them); the P G decisions (s > 0) are spread over the 256 threads, each reading its
+// detection's box from global memory and raising a bit of its row's 64-bit mask in LDS (where best_iou lies later; one barrier more);
+// thread i then takes row i's mask and writes key, common and s, formed again by the same operations, behind the ordered prefix.
+// Without BOX the four arguments are not read and the body is what it was.
 static_assert(RTK_SCORE_MAX_OBJECTS <= TS_THREADS, "PAIRS: one thread per detection row");
 // s = 1 - |c - g| / zero_distance in float64, every operation rounded on its own (the build has contraction off)
 __device__ __forceinline__ double ts_centre_similarity(double cx, double cy, double cz, const double *g, double zero_distance) {
@@ -55,13 +68,108 @@ __device__ __forceinline__ double ts_centre_similarity(double cx, double cy, dou
     return 1.0 - sqrt(d2) / zero_distance;
 }
 
-template <bool LOG, bool MEM, bool PAIRS = false, bool CENTRE = false>
+// ---- the oriented-box IoU (include/rtk_score.h, the last section): every operation float64 and rounded on its own ----
+// The area of the detection's footprint -- centre D, half axes (lx, ly) = L E and (-wx, wy) = W E' in the kept object's own frame -- cut
+// by the object's rectangle |x| <= a, |y| <= b: Sutherland-Hodgman by the four half-planes, kept as a set of directed edges in eight
+// fixed slots (the footprint's four, then the one edge a cut adds along its bound, from where the outline leaves to where it comes
+// back), so that no index into them is computed at run time, and Green's theorem over the slots in order.  A crossing point is formed
+// once, with its cut coordinate set to the bound itself, and serves the edge it shortens and the edge the cut adds.
+__device__ __forceinline__ double ts_box_cut_area(double Dx, double Dy, double lx, double ly, double wx, double wy, double a, double b) {
+    double x0[8], y0[8], x1[8], y1[8];
+    unsigned valid = 0xfu;
+    // the corners, counter-clockwise: D + LE + WE', D - LE + WE', D - LE - WE', D + LE - WE'
+    x0[0] = (Dx + lx) - wx; y0[0] = (Dy + ly) + wy;
+    x0[1] = (Dx - lx) - wx; y0[1] = (Dy - ly) + wy;
+    x0[2] = (Dx - lx) + wx; y0[2] = (Dy - ly) - wy;
+    x0[3] = (Dx + lx) + wx; y0[3] = (Dy + ly) - wy;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { x1[e] = x0[(e + 1) & 3]; y1[e] = y0[(e + 1) & 3]; }
+#pragma unroll
+    for (int e = 4; e < 8; ++e) { x0[e] = 0.0; y0[e] = 0.0; x1[e] = 0.0; y1[e] = 0.0; }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {      // x <= a, x >= -a, y <= b, y >= -b
+        const double lim = k < 2 ? a : b, bound = (k & 1) ? -lim : lim;
+        bool left = false, came = false;
+        double ox = 0.0, oy = 0.0, ix = 0.0, iy = 0.0;      // where the outline leaves, where it comes back
+#pragma unroll
+        for (int e = 0; e < 4 + k; ++e) {
+            if (!((valid >> e) & 1u)) continue;
+            const double v0 = k < 2 ? x0[e] : y0[e], v1 = k < 2 ? x1[e] : y1[e];
+            const double s0 = (k & 1) ? v0 + lim : lim - v0, s1 = (k & 1) ? v1 + lim : lim - v1;
+            const bool in0 = s0 >= 0.0, in1 = s1 >= 0.0;
+            if (in0 && in1) continue;
+            if (!in0 && !in1) { valid &= ~(1u << e); continue; }
+            const double t = s0 / (s0 - s1);
+            const double cx = k < 2 ? bound : x0[e] + t * (x1[e] - x0[e]), cy = k < 2 ? y0[e] + t * (y1[e] - y0[e]) : bound;
+            if (in0) { x1[e] = cx; y1[e] = cy; ox = cx; oy = cy; left = true; }
+            else { x0[e] = cx; y0[e] = cy; ix = cx; iy = cy; came = true; }
+        }
+        if (left && came) { x0[4 + k] = ox; y0[4 + k] = oy; x1[4 + k] = ix; y1[4 + k] = iy; valid |= 1u << (4 + k); }
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+        if ((valid >> e) & 1u) acc += x0[e] * y1[e] - x1[e] * y0[e];
+    return 0.5 * acc;
+}
+
+// Row d (8 words, rtk_object_boxes') and its valid word -> whether the detection has a box, and the box's terms: centre, half length and
+// width, heading (c, s), z range and height.
+__device__ __forceinline__ bool ts_box_detection(const double *d, int valid, bool bev, double &cx, double &cy, double &L, double &W, double &c,
+                                                 double &s, double &bot, double &top, double &h) {
+    const double x = d[0], y = d[1], z = d[2], l = d[3], w = d[4], hh = d[5], yaw = d[6];
+    if (!(valid > 0 && isfinite(x) && isfinite(y) && isfinite(z) && isfinite(l) && isfinite(w) && isfinite(hh) && isfinite(yaw) && l > 0.0 &&
+          w > 0.0 && (bev || hh > 0.0)))
+        return false;
+    cx = x; cy = y; h = hh;
+    L = 0.5 * l; W = 0.5 * w; bot = z - 0.5 * hh; top = z + 0.5 * hh;
+    sincos(yaw, &s, &c);
+    return true;
+}
+
+// s of a detection (centre dcx, dcy, half length L and width W, heading (c, s), z range [dbot, dtop], height h) and the staged upright
+// box g (ts_score_box_lds) of a kept object; bev: the bird's-eye-view IoU.  A box without extent (g[4] == 0) gives 0.0.
+__device__ __forceinline__ double ts_box_similarity(double dcx, double dcy, double L, double W, double hc, double hs, double dbot, double dtop,
+                                                    double h, const double *g, bool bev) {
+    const double a = g[4], b = g[5];
+    if (!(a > 0.0)) return 0.0;
+    const double dx = dcx - g[0], dy = dcy - g[1];
+    const double ri = sqrt(L * L + W * W), rj = sqrt(a * a + b * b), rr = ri + rj;
+    if ((dx * dx + dy * dy) > rr * rr) return 0.0;      // the prefilter: part of the definition
+    double zo = 1.0;
+    if (!bev) {
+        const double top = dtop < g[7] ? dtop : g[7], bottom = dbot > g[6] ? dbot : g[6];
+        zo = top - bottom;
+        if (!(zo > 0.0)) return 0.0;
+    }
+    // the ground-truth box's own frame: the detection's centre D and axis E there
+    const double hx = g[2], hy = g[3];
+    const double Dx = dx * hx + dy * hy, Dy = dy * hx - dx * hy;
+    const double ex = hc * hx + hs * hy, ey = hs * hx - hc * hy;
+    const double I2 = ts_box_cut_area(Dx, Dy, L * ex, L * ey, W * ey, W * ex, a, b);
+    const double l = 2.0 * L, w = 2.0 * W, a2 = 2.0 * a, b2 = 2.0 * b;
+    const double Ai = l * w, Aj = a2 * b2;
+    double s;
+    if (bev) {
+        s = I2 / ((Ai + Aj) - I2);
+    } else {
+        const double I3 = I2 * zo;
+        s = I3 / ((Ai * h + Aj * (g[7] - g[6])) - I3);
+    }
+    return s < 1.0 ? s : (s >= 1.0 ? 1.0 : s);      // min(s, 1.0); a NaN stays one
+}
+
+template <bool LOG, bool MEM, bool PAIRS = false, bool CENTRE = false, bool BOX = false>
 __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in, const rtk_track_score_state_t &st,
                                                  const rtk_track_score_out_t &out, const rtk_score_log_t &lg,
                                                  const rtk_score_memory_t &mm, const rtk_score_pairs_t &pr = rtk_score_pairs_t{},
-                                                 double *pair_sim = nullptr, const double *gt_centre = nullptr, double zero_distance = 0.0) {
+                                                 double *pair_sim = nullptr, const double *gt_centre = nullptr, double zero_distance = 0.0,
+                                                 const double *det_box = nullptr, const int *det_valid = nullptr,
+                                                 const double *gt_boxes = nullptr, int mode = 0) {
     static_assert(LOG || !PAIRS, "the pair log goes with the main log");
     static_assert(PAIRS || !CENTRE, "the centre similarity is the pair log's");
+    static_assert((PAIRS && !CENTRE) || !BOX, "the box similarity is the pair log's, and a log has one similarity");
+    constexpr int SIMW = BOX ? 8 : 3;      // the float64 words staged per kept object
     extern __shared__ __attribute__((aligned(16))) unsigned char ts_smem[];
     const int b = blockIdx.x, t = threadIdx.x, lane = t & (RTK_WAVE - 1), wave = t / RTK_WAVE;
     const int N = in.N, Kobj = in.Kobj, K = in.K, T = in.T, W = (N + 31) / 32;
@@ -73,8 +181,8 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
     int *gsize = prev_id + Kobj, *glabel = gsize + K, *gslot = glabel + K, *gpred = gslot + K, *entry = gpred + K;
     int *scal = entry + K;      // 0: predicted points | 1: ground-truth columns | 2..4: mt, pt, ml of a closing clip
     int *old_track = scal + 8;  // MEM only
-    double *gpos = nullptr;     // CENTRE only
-    if (CENTRE) gpos = reinterpret_cast<double *>(ts_smem + ((reinterpret_cast<unsigned char *>(MEM ? old_track + Kobj : old_track) - ts_smem + 7) & ~(size_t)7));
+    double *gpos = nullptr;     // CENTRE: the kept objects' positions; BOX: their upright boxes
+    if (CENTRE || BOX) gpos = reinterpret_cast<double *>(ts_smem + ((reinterpret_cast<unsigned char *>(MEM ? old_track + Kobj : old_track) - ts_smem + 7) & ~(size_t)7));
 
     const size_t ob = (size_t)b * Kobj, kb = (size_t)b * K, tb = (size_t)b * T;
     float *target = out.aff_target + ob * Kobj;
@@ -116,6 +224,28 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
         if (t == 0) {
             gpos[3 * K] = zero_distance;
             reinterpret_cast<unsigned long long *>(gpos)[3 * K + 1] = (unsigned long long)(pair_sim + (size_t)b * pr.Q);
+        }
+    }
+    if (BOX) {      // the four arguments end here
+        for (int j = t; j < G; j += TS_THREADS) {
+            const int slot = in.gt_slot[kb + j];
+            double gx = 0.0, gy = 0.0, gz = 0.0, ux = 0.0, uy = 0.0, h0 = 0.0, h1 = 0.0, h2 = 0.0;
+            bool ok = slot >= 0 && slot < K;
+            if (ok) {      // centre | R row-major | half-extent: the heading is R's first column
+                const double *bx = gt_boxes + (kb + slot) * RTK_GT_BOX_WORDS;
+                gx = bx[0]; gy = bx[1]; gz = bx[2]; ux = bx[3]; uy = bx[6]; h0 = bx[12]; h1 = bx[13]; h2 = bx[14];
+            }
+            const double nn = sqrt(ux * ux + uy * uy);
+            ok = ok && isfinite(gx) && isfinite(gy) && isfinite(gz) && isfinite(ux) && isfinite(uy) && isfinite(h0) && isfinite(h1) &&
+                 isfinite(h2) && isfinite(nn) && nn != 0.0 && h0 > 0.0 && h1 > 0.0 && h2 > 0.0;
+            double *g = gpos + 8 * j;
+            g[0] = gx; g[1] = gy; g[2] = ux / nn; g[3] = uy / nn;
+            g[4] = ok ? h0 : 0.0; g[5] = h1; g[6] = gz - h2; g[7] = gz + h2;
+        }
+        for (int i = t; i < Kobj; i += TS_THREADS) reinterpret_cast<unsigned long long *>(best_iou)[i] = 0ull;      // the rows' pair masks
+        if (t == 0) {
+            reinterpret_cast<unsigned long long *>(gpos)[8 * K] = (unsigned long long)mode;
+            reinterpret_cast<unsigned long long *>(gpos)[8 * K + 1] = (unsigned long long)(pair_sim + (size_t)b * pr.Q);
         }
     }
     if (t < 8) scal[t] = 0;
@@ -198,8 +328,28 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
     if (PAIRS) {
         int mine = 0;
         double cx = 0.0, cy = 0.0, cz = 0.0;      // CENTRE: the centre of this thread's detection
-        unsigned long long logged = 0ull;          // CENTRE: the kept objects (K <= 64) this thread's row is logged with
-        if (CENTRE) {
+        unsigned long long logged = 0ull;          // CENTRE, BOX: the kept objects (K <= 64) this thread's row is logged with
+        double bl = 0.0, bw = 0.0, bc = 0.0, bs = 0.0, bbot = 0.0, btop = 0.0, bh = 0.0;      // BOX: this thread's detection (cx, cy: its centre)
+        bool bev = false;
+        if (BOX) {
+            // the (i, j) decisions spread over the workgroup: pair e = i G + j to thread e mod 256, which forms detection i's terms for
+            // itself and raises bit j of row i's mask in LDS (an integer OR: any order, the same word).  The masks lie where best_iou
+            // will: zeroed at the start, read back by the row's own thread, which is also the one that writes best_iou[i] below.
+            unsigned long long *rowmask = reinterpret_cast<unsigned long long *>(best_iou);
+            bev = reinterpret_cast<unsigned long long *>(gpos)[8 * K] == (unsigned long long)RTK_SCORE_BOX_BEV;
+            for (int e = t; e < P * G; e += TS_THREADS) {
+                const int i = e / G, j = e - i * G;
+                if (ts_box_detection(det_box + (ob + i) * 8, det_valid[ob + i], bev, cx, cy, bl, bw, bc, bs, bbot, btop, bh) &&
+                    ts_box_similarity(cx, cy, bl, bw, bc, bs, bbot, btop, bh, gpos + 8 * j, bev) > 0.0)      // the one place a pair is decided: s > 0.0, a NaN is not
+                    atomicOr(&rowmask[i], 1ull << j);
+            }
+            __syncthreads();
+            if (t < P) {
+                logged = rowmask[t];
+                if (logged) ts_box_detection(det_box + (ob + t) * 8, det_valid[ob + t], bev, cx, cy, bl, bw, bc, bs, bbot, btop, bh);
+            }
+            mine = __popcll(logged);
+        } else if (CENTRE) {
             if (t < P) {
                 double sx = 0.0, sy = 0.0, sz = 0.0;
                 int m = 0;
@@ -236,15 +386,16 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
         }
         pair_at += upto - mine;
         log_fits = log_fits && log_q >= 0 && log_q <= pr.Q - pair_total;
-        if (CENTRE && log_fits) {      // row t's pairs in ascending j: key, common, and s formed again by the same operations
-            double *sim = reinterpret_cast<double *>(reinterpret_cast<unsigned long long *>(gpos)[3 * K + 1]) + log_q + pair_at;
+        if ((CENTRE || BOX) && log_fits) {      // row t's pairs in ascending j: key, common, and s formed again by the same operations
+            double *sim = reinterpret_cast<double *>(reinterpret_cast<unsigned long long *>(gpos)[SIMW * K + 1]) + log_q + pair_at;
             size_t q = (size_t)b * pr.Q + log_q + pair_at;
             while (logged) {
                 const int j = __ffsll((long long)logged) - 1;
                 logged &= logged - 1;
                 pr.pair_key[q] = (t << 8) | j;
                 pr.pair_common[q] = common[t * K + j];
-                *sim++ = ts_centre_similarity(cx, cy, cz, gpos + 3 * j, gpos[3 * K]);
+                if (BOX) *sim++ = ts_box_similarity(cx, cy, bl, bw, bc, bs, bbot, btop, bh, gpos + 8 * j, bev);
+                else *sim++ = ts_centre_similarity(cx, cy, cz, gpos + 3 * j, gpos[3 * K]);
                 ++q;
             }
         }
@@ -269,7 +420,7 @@ __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in,
             lg.rec_iou[r] = bi;
             if (PAIRS) {
                 pr.rec_size[r] = psize[i];
-                if (!CENTRE) {      // (CENTRE: written with the prefix above)
+                if (!CENTRE && !BOX) {      // (CENTRE, BOX: written with the prefix above)
                     size_t q = (size_t)b * pr.Q + log_q + pair_at;
                     for (int j = 0; j < G; ++j) {
                         const int c = common[i * K + j];

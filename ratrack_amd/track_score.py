@@ -122,10 +122,10 @@ through the clip over a one-frame intruder with a slightly larger IoU.  Identity
 counts, not only a detection's best object.  `threshold=` removes detections before anything else, the alignment pass included.  WHAT
 NOW AGREES WITH TrackEval is the arrangement of both metrics and, under `similarity="centre"` (below), the similarity as well; WHAT
 STILL DOES NOT is the 28-bit weights and, under "centre", the positions, which are point centroids rather than label-box centres.
-Under the default `similarity="iou"` the similarity is the reference's point IoU.  TrackEval's other similarity is a box IoU: the
-detections now have boxes (ratrack_amd/boxes.py fits one per object on the device), but a box-IoU similarity on the pair log is not
-built yet -- `pair_sim` and the `*_sim` replays take any similarity.  The defaults (`matching="greedy"`, `pairs="best"`) are the calls
-above with their launches and bits.
+Under the default `similarity="iou"` the similarity is the reference's point IoU.  TrackEval's other similarity is a box IoU:
+`similarity="box"` / `"box_bev"` (below) write the pair log under the oriented-box IoU of the detections' fitted boxes
+(ratrack_amd/boxes.py) and the label boxes.  The defaults (`matching="greedy"`, `pairs="best"`) are the calls above with their
+launches and bits.
 
 The centre-distance similarity.  `TrackScorer(..., sweep_pairs=Q, similarity="centre", zero_distance=2.0)` writes the pair log under
 TrackEval's similarity for detections that are positions (`_calculate_euclidean_similarity`): s = max(0, 1 - |c - g| / zero_distance),
@@ -141,6 +141,18 @@ on its object.  Everything else `update` does is bit for bit what it does under 
 replay that log unchanged in every other respect, with "IoU" read as s (the *_sim entry points: the same kernels' bodies on the log's
 own similarity).  `similarity_distance(s, zero_distance)` turns motp, amotp and LocA back into metres.  The greedy calls read only the
 main log and are the same under either similarity; a log has one similarity: build two scorers for both.
+
+The box IoU.  `TrackScorer(..., sweep_pairs=Q, similarity="box")` writes the pair log under the three-dimensional IoU of each
+detection's fitted box (`BatchedTracker(boxes=True, box_min_extent=...)`, or `boxes.object_boxes_raw`) and each kept object's label
+box -- entry `GtObjects.slot` of `GtObjects.boxes`, the frame-1 table `pack_boxes` makes --, `similarity="box_bev"` under the IoU of
+their footprints in the bird's-eye view: what the KITTI devkit, AB3DMOT, TrackEval's loaders and the VoD devkit match by.  A pair is
+logged iff its IoU is > 0, whatever its common point count; everything else `update` does is bit for bit what it does under "iou"
+(rtk_track_score_pairs_box, the same single launch), and the four calls above replay the log unchanged with "IoU" read as the box IoU.
+Definitions in include/rtk_score.h, the last section.  WHAT STILL DEPARTS FROM TrackEval: the 28-bit assignment weights; the label box
+is read UPRIGHT in the radar frame (heading from its first axis, footprint and z range from its centre and half-extents), which drops
+the radar-lidar calibration's tilt of about half a degree, and its centre's z is whatever `vod_gt.box_in_radar_frame` takes it to be --
+one reason "box_bev" exists; and the detections' boxes are fitted from their points.  A detection without a box has no pairs: a cluster
+of two points, or of collinear points, fitted with min_extent = 0 has width 0 -- give `box_min_extent` a positive value.
 
 Nothing here synchronises with the device except `GtObjects.check()`, `TrackScorer.check()`, `TrackScorer.result()`,
 `TrackScorer.sweep()`, `TrackScorer.hota()`, `TrackScorer.identity()` and `TrackScorer.clear_optimal()`.
@@ -178,16 +190,18 @@ ALIGN_PAIRS = 1024                     # RTK_SCORE_ALIGN_PAIRS
 
 # ---- the similarity of the pair log ----------------------------------------------------------------------------------------
 
-SIMILARITIES = ("iou", "centre")
+SIMILARITIES = ("iou", "centre", "box", "box_bev")
 ZERO_DISTANCE = 2.0                    # TrackEval's default zero_distance
+BOX_MODES = {"box": 0, "box_bev": 1}   # RTK_SCORE_BOX_3D, RTK_SCORE_BOX_BEV
 
 
 def check_similarity(similarity="iou", zero_distance=None, sweep_pairs=None):
-    """The checks of `TrackScorer(similarity=..., zero_distance=..., sweep_pairs=...)`, host only and before anything is allocated
-    -> (similarity, zero_distance as a float, or None under "iou").  "iou": the point IoU of the logged integers, today's scorer; a
-    zero_distance given with it is an error.  "centre": TrackEval's centre-distance similarity, which lives in the pair log and so
-    needs sweep_pairs; zero_distance None means 2.0, any other value must be a finite number > 0."""
-    if similarity not in SIMILARITIES:
+    """The checks of the two similarities that need no boxes, host only -> (similarity, zero_distance as a float, or None under
+    "iou").  "iou": the point IoU of the logged integers, today's scorer; a zero_distance given with it is an error.  "centre":
+    TrackEval's centre-distance similarity, which lives in the pair log and so needs sweep_pairs; zero_distance None means 2.0, any
+    other value must be a finite number > 0.  Anything else is refused here, the box similarities included: this function is what it
+    was before they came (tests/test_track_centre_cpu.py holds it to that); `check_pair_similarity` takes all four."""
+    if similarity not in ("iou", "centre"):
         raise ValueError("TrackScorer: similarity=%r is neither \"iou\" nor \"centre\"" % (similarity,))
     if similarity == "iou":
         if zero_distance is not None:
@@ -206,6 +220,22 @@ def check_similarity(similarity="iou", zero_distance=None, sweep_pairs=None):
     return "centre", z
 
 
+def check_pair_similarity(similarity="iou", zero_distance=None, sweep_pairs=None):
+    """The checks of `TrackScorer(similarity=..., zero_distance=..., sweep_pairs=...)`, host only and before anything is allocated
+    -> (similarity, zero_distance as a float or None).  "iou" and "centre": `check_similarity`'s.  "box" / "box_bev": the oriented-box
+    IoU in three dimensions / in the bird's-eye view, which lives in the pair log and so needs sweep_pairs; it has no distance scale,
+    so a zero_distance given with it is an error.  Any other value is a ValueError that names the four."""
+    if not isinstance(similarity, str) or similarity not in SIMILARITIES:
+        raise ValueError("TrackScorer: similarity=%r is none of \"iou\", \"centre\", \"box\", \"box_bev\"" % (similarity,))
+    if similarity not in BOX_MODES:
+        return check_similarity(similarity, zero_distance, sweep_pairs)
+    if zero_distance is not None:
+        raise ValueError("TrackScorer: zero_distance=%r goes with similarity=\"centre\"; a box IoU has no distance scale" % (zero_distance,))
+    if sweep_pairs is None:
+        raise ValueError("TrackScorer: similarity=\"%s\" lives in the pair log (give sweep_pairs, with sweep_frames and sweep_records)" % similarity)
+    return similarity, None
+
+
 def similarity_distance(s, zero_distance):
     """The distance a centre-distance similarity stands for, (1 - s) * zero_distance in float64: motp, amotp and LocA in metres."""
     return (1.0 - np.asarray(s, dtype=np.float64)) * float(zero_distance)
@@ -213,10 +243,11 @@ def similarity_distance(s, zero_distance):
 
 # ---- what fits -------------------------------------------------------------------------------------------------------------
 
-def check_fit(max_boxes, points, max_objects=None, track_memory=False, centre=False):
+def check_fit(max_boxes, points, max_objects=None, track_memory=False, centre=False, box=False):
     """Raises ValueError, stating the limit, for sizes whose per-stream tables do not fit one workgroup's LDS: those of `gt_objects`
     (max_boxes, points) and, with max_objects, those of `TrackScorer.update` as well (track_memory: of its memory variant, which
-    keeps max_objects more words; centre: of the centre-similarity variant, which keeps the kept objects' positions).  Host only."""
+    keeps max_objects more words; centre: of the centre-similarity variant, which keeps the kept objects' positions; box: of the
+    box-IoU variant, which keeps their upright boxes).  Host only."""
     K, N = int(max_boxes), int(points)
     if not 1 <= K <= MAX_BOXES:
         raise ValueError("max_boxes=%d outside [1, %d] (a point's ground-truth objects are one 64-bit mask)" % (K, MAX_BOXES))
@@ -230,7 +261,9 @@ def check_fit(max_boxes, points, max_objects=None, track_memory=False, centre=Fa
     Kobj = int(max_objects)
     if not 1 <= Kobj <= MAX_OBJECTS:
         raise ValueError("max_objects=%d outside [1, %d]" % (Kobj, MAX_OBJECTS))
-    if centre:
+    if box:
+        need = _lib._fn("rtk_track_score_box_lds_bytes")(Kobj, K, N, 1 if track_memory else 0)
+    elif centre:
         need = _lib._fn("rtk_track_score_centre_lds_bytes")(Kobj, K, N, 1 if track_memory else 0)
     else:
         need = _lib._fn("rtk_track_score_memory_lds_bytes" if track_memory else "rtk_track_score_lds_bytes")(Kobj, K, N)
@@ -263,7 +296,8 @@ class GtObjects:
     (box slot as in `BoxBatch`, label id, number of points; -1 / -1 / 0 past count); members (B,K,ceil(N/32)) int32 holding uint32
     words, bit p & 31 of word p >> 5 = point p -- an object that received a rider keeps the FIRST column of each distinct coordinate
     triple (the host's torch.unique), so size is the number of set bits for every object; centre (B,K,3) float64, the mean of the
-    points of the object's own box; flags (B) int32; n_valid (B) int32 or None."""
+    points of the object's own box; boxes (B,K,16) float64, the frame-1 box table `gt_objects` was given (a reference, not a copy: entry
+    slot[b][j] is kept object j's label box); flags (B) int32; n_valid (B) int32 or None."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -307,8 +341,8 @@ def gt_objects(pc1, boxes, types, n_valid=None, min_obj_points=2):
     o = GtObjectsOut(slot.data_ptr(), label_id.data_ptr(), count.data_ptr(), size.data_ptr(), members.data_ptr(), centre.data_ptr(),
                      flags.data_ptr())
     _lib.call("rtk_gt_objects", ctypes.addressof(a), ctypes.addressof(o), _stream())
-    return GtObjects(slot=slot, label_id=label_id, count=count, size=size, members=members, centre=centre, flags=flags, n_valid=nv,
-                     max_boxes=K, points=N)
+    return GtObjects(slot=slot, label_id=label_id, count=count, size=size, members=members, centre=centre, boxes=boxes.boxes[0], flags=flags,
+                     n_valid=nv, max_boxes=K, points=N)
 
 
 # ---- launch 2 --------------------------------------------------------------------------------------------------------------
@@ -356,7 +390,7 @@ class SweepResult:
     (level, threshold, mota, moda, recall, precision, mt_fraction, pt_fraction, ml_fraction and the raw counts), None when no level
     was reached.  `unfiltered`: the pooled index-0 counts and iou_sum.  `counters` (L+1,B,11) int64 and `iou_sums` (L+1,B) float64 per
     stream; `flags` (B).  `matching` "greedy" or "optimal" and `min_iou` (None for greedy); `similarity` and `zero_distance` of the
-    scorer's pair log ("iou" and None, or "centre" and its distance scale: the IoU sums are then sums of s).  Under the optimal matching also `frag`
+    scorer's pair log ("iou" and None, "centre" and its distance scale, or "box" / "box_bev" and None: the IoU sums are then sums of s).  Under the optimal matching also `frag`
     (L+1) int64, the pooled fragmentations per level, and `iou_q` (L+1) int64, the pooled sums of the matches' IoUs quantised to
     1/65536 (both 0 past `reached`), with `frag_streams` and `iou_q_streams` (L+1,B) per stream; under the greedy rule they are
     None.  MOTP is iou_sum / tp under either."""
@@ -561,12 +595,19 @@ class TrackScorer:
     with centre-distance similarity s = 1 - |c - g| / zero_distance > 0 (module docstring; rtk_track_score_pairs_centre), pair_common
     may be 0, and pair_sim (B,Q) float64 holds s.  zero_distance: None (2.0 under "centre") or a finite number > 0; only with
     "centre".  `update` / `update_raw` then read `gobj.centre`; `sweep(matching="optimal")`, `clear_optimal`, `hota(matching="optimal")`
-    and `identity(pairs="all")` replay the log on s (min_iou: the minimum similarity)."""
+    and `identity(pairs="all")` replay the log on s (min_iou: the minimum similarity).  "box" / "box_bev", which need sweep_pairs as
+    well: the pair log holds every pair whose oriented-box IoU -- in three dimensions / in the bird's-eye view -- between the
+    detection's fitted box and the kept object's label box, read upright, is > 0 (module docstring; rtk_track_score_pairs_box);
+    pair_common may be 0 and pair_sim (B,Q) float64 holds the IoU.  `update` then reads `out.object_boxes` / `out.object_box_valid`
+    (`BatchedTracker(boxes=True)`), `update_raw` takes det_boxes= / det_box_valid=, both read `gobj.boxes`.  A DETECTION WITHOUT A BOX
+    HAS NO PAIRS: a cluster of two points, or of collinear points, fitted with min_extent = 0 has width 0 and therefore none -- build
+    the tracker with `BatchedTracker(box_min_extent=...)` above 0 (or give `object_boxes_raw` a positive min_extent)."""
 
     def __init__(self, streams, max_objects=128, max_boxes=32, max_gt_tracks=1024, device="cuda", sweep_frames=None, sweep_records=None,
                  track_memory=False, sweep_pairs=None, similarity="iou", zero_distance=None):
-        self.similarity, self.zero_distance = check_similarity(similarity, zero_distance, sweep_pairs)
+        self.similarity, self.zero_distance = check_pair_similarity(similarity, zero_distance, sweep_pairs)
         self.centre = self.similarity == "centre"
+        self.box = self.similarity in BOX_MODES
         self.B, self.Kobj, self.K, self.T = int(streams), int(max_objects), int(max_boxes), int(max_gt_tracks)
         if self.T < 1:
             raise ValueError("max_gt_tracks=%d must be at least 1" % self.T)
@@ -586,7 +627,7 @@ class TrackScorer:
             if self.Q < 1 or self.B * self.Q >= 2 ** 31:
                 raise ValueError("TrackScorer: sweep_pairs=%d must be at least 1 (and the pair log below 2^31 entries)" % self.Q)
         self.track_memory = bool(track_memory)
-        check_fit(self.K, 1, self.Kobj, self.track_memory, self.centre)
+        check_fit(self.K, 1, self.Kobj, self.track_memory, self.centre, self.box)
         B, z = self.B, lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)
         self.counters = torch.zeros(B, len(COUNTERS), dtype=torch.int64, device=device)
         self.iou_sum = torch.zeros(B, dtype=torch.float64, device=device)
@@ -606,8 +647,9 @@ class TrackScorer:
             self.pair_cursor, self.pair_frame = z(B), z(B, self.F, 2)
             self.pair_key, self.pair_common = z(B, self.Q), z(B, self.Q)
             self.log_size, self.log_label_size = z(B, self.R), z(B, self.R)
-        if self.centre:
+        if self.centre or self.box:          # a log that carries its similarity: the replays go to the *_sim entry points
             self.pair_sim = torch.zeros(B, self.Q, dtype=torch.float64, device=device)
+        self.has_sim = self.centre or self.box
 
     def _log_block(self, object_conf=None):
         return ScoreLog(self.F, self.R, object_conf, self.log_cursor.data_ptr(), self.log_frame.data_ptr(), self.log_label.data_ptr(),
@@ -619,8 +661,9 @@ class TrackScorer:
 
     def update(self, out, gobj, reset=None, active=None):
         """out: a `tracker.StepResult`; gobj: the GtObjects of the same frame (its n_valid is used).  active None: the mask the step
-        ran with.  With logging on, out.object_conf is logged; with track_memory, out.table_ids / out.table_count are the table.
-        One launch, no synchronisation.  -> MatchResult."""
+        ran with.  With logging on, out.object_conf is logged; with track_memory, out.table_ids / out.table_count are the table;
+        under similarity "box" / "box_bev", out.object_boxes / out.object_box_valid are the detections' boxes.  One launch, no
+        synchronisation.  -> MatchResult."""
         if out.max_objects != self.Kobj:
             raise ValueError("TrackScorer(max_objects=%d) against a step with max_objects=%d" % (self.Kobj, out.max_objects))
         table = {}
@@ -629,17 +672,24 @@ class TrackScorer:
                 raise ValueError("TrackScorer(track_memory=True) keeps its record by the tracker's table, and this step has none: "
                                  "build the tracker with max_age (0 or more)")
             table = dict(table_ids=out.table_ids, table_count=out.table_count)
+        if self.box:
+            if getattr(out, "object_boxes", None) is None or getattr(out, "object_box_valid", None) is None:
+                raise ValueError("TrackScorer(similarity=\"%s\") scores the detections' boxes, and this step has none: build the tracker with "
+                                 "BatchedTracker(boxes=True)" % self.similarity)
+            table.update(det_boxes=out.object_boxes, det_box_valid=out.object_box_valid)
         return self.update_raw(out.pc1, out.obj, out.num_objects, out.object_ids, gobj, gobj.n_valid, reset,
                                out.active if active is None else active, object_conf=out.object_conf if self.logging else None, **table)
 
     def update_raw(self, pc1, obj, num_objects, object_ids, gobj, n_valid=None, reset=None, active=None, object_conf=None, table_ids=None,
-                   table_count=None):
+                   table_count=None, det_boxes=None, det_box_valid=None):
         """pc1 (B,3,N) fp32 of any strides; obj (B,N) int32, the detection each point belongs to (-1 none; detections are numbered in
         association order); num_objects (B) int32; object_ids (B,Kobj) int32 track ids; gobj from `gt_objects` on the same cloud;
         n_valid (B) / (2,B) / None; reset, active (B) masks or None; object_conf (B,Kobj) fp32, the confidence of each detection:
         required when the scorer logs for `sweep`, ignored otherwise; table_ids (B,Kobj) int32 and table_count (B) int32: the
         tracker's NEW table (the one this frame's association wrote: its first num_objects rows are this frame's detections),
-        required with track_memory, ignored otherwise."""
+        required with track_memory, ignored otherwise; det_boxes (B,Kobj,8) float64 and det_box_valid (B,Kobj) int32: the detections'
+        boxes as `boxes.object_boxes` / `object_boxes_raw` return them (`.box`, `.valid`) for the same step, required under
+        similarity "box" / "box_bev" (with `gobj.boxes`, the frame-1 box table), ignored otherwise."""
         B, C, N = pc1.shape
         if B != self.B or C != 3 or tuple(obj.shape) != (B, N) or tuple(object_ids.shape) != (B, self.Kobj) or num_objects.numel() != B:
             raise ValueError("TrackScorer(streams=%d, max_objects=%d): got pc1 %s, obj %s, object_ids %s"
@@ -647,8 +697,22 @@ class TrackScorer:
         if gobj.max_boxes != self.K or gobj.points != N or gobj.count.numel() != B:
             raise ValueError("TrackScorer(max_boxes=%d): ground-truth objects of %d slots over %d points against %d points"
                              % (self.K, gobj.max_boxes, gobj.points, N))
-        check_fit(self.K, N, self.Kobj, self.track_memory, self.centre)
+        check_fit(self.K, N, self.Kobj, self.track_memory, self.centre, self.box)
         dev = pc1.device
+        gt_boxes = None
+        if self.box:
+            gt_boxes = getattr(gobj, "boxes", None)
+            if gt_boxes is None or tuple(gt_boxes.shape) != (B, self.K, 16) or gt_boxes.dtype != torch.float64:
+                raise ValueError("TrackScorer(similarity=\"%s\"): gobj.boxes must be the (%d,%d,16) float64 frame-1 box table, got %s"
+                                 % (self.similarity, B, self.K, None if gt_boxes is None else (tuple(gt_boxes.shape), gt_boxes.dtype)))
+            if det_boxes is None or det_box_valid is None or tuple(det_boxes.shape) != (B, self.Kobj, 8) or det_boxes.dtype != torch.float64 or \
+                    tuple(det_box_valid.shape) != (B, self.Kobj):
+                raise ValueError("TrackScorer(similarity=\"%s\"): update_raw needs the detections' boxes, det_boxes (%d,%d,8) float64 and "
+                                 "det_box_valid (%d,%d), got %s and %s"
+                                 % (self.similarity, B, self.Kobj, B, self.Kobj, None if det_boxes is None else (tuple(det_boxes.shape), det_boxes.dtype),
+                                    None if det_box_valid is None else tuple(det_box_valid.shape)))
+            gt_boxes, det_boxes = gt_boxes.to(dev).contiguous(), det_boxes.to(dev).contiguous()
+            det_box_valid = det_box_valid.to(device=dev, dtype=torch.int32).contiguous()
         gt_centre = None
         if self.centre:
             gt_centre = getattr(gobj, "centre", None)
@@ -687,7 +751,12 @@ class TrackScorer:
         if self.track_memory:
             table_ids, table_count = as32(table_ids), as32(table_count)
             mm = ScoreMemory(table_ids.data_ptr(), table_count.data_ptr(), self.row_track.data_ptr(), self.labelled_coasted.data_ptr())
-        if self.centre:
+        if self.box:
+            lg, pr = self._log_block(object_conf.data_ptr()), self._pair_block()
+            _lib.call("rtk_track_score_pairs_box", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), ctypes.addressof(lg),
+                      None if mm is None else ctypes.addressof(mm), ctypes.addressof(pr), self.pair_sim.data_ptr(), det_boxes.data_ptr(),
+                      det_box_valid.data_ptr(), gt_boxes.data_ptr(), BOX_MODES[self.similarity], _stream())
+        elif self.centre:
             lg, pr = self._log_block(object_conf.data_ptr()), self._pair_block()
             _lib.call("rtk_track_score_pairs_centre", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), ctypes.addressof(lg),
                       None if mm is None else ctypes.addressof(mm), ctypes.addressof(pr), self.pair_sim.data_ptr(), gt_centre.data_ptr(),
@@ -848,7 +917,7 @@ class TrackScorer:
         q = torch.empty(count, B, dtype=torch.float64, device=dev)
         tail = (score.data_ptr(), thr.data_ptr(), None if reached is None else reached.data_ptr(), count, min_iou, c.data_ptr(), iq.data_ptr(),
                 q.data_ptr(), None if mask is None else mask.data_ptr(), flags.data_ptr(), st)
-        if self.centre:
+        if self.has_sim:
             _lib.call("rtk_score_replay_optimal_sim", B, self.T, lgp, prp, self.pair_sim.data_ptr(), *tail)
         else:
             _lib.call("rtk_score_replay_optimal", B, self.T, lgp, prp, *tail)
@@ -936,7 +1005,7 @@ class TrackScorer:
             pair_a = torch.empty(B, self.Q, dtype=torch.float64, device=dev)
             pair_index, clip_cg, clip_ct = (torch.empty(B, self.Q, dtype=torch.int32, device=dev) for _ in range(3))
             tables = (pair_a.data_ptr(), pair_index.data_ptr(), clip_cg.data_ptr(), clip_ct.data_ptr())
-            if self.centre:
+            if self.has_sim:
                 sim = self.pair_sim.data_ptr()
                 _lib.call("rtk_score_alignment_sim", B, self.T, lgp, prp, sim, sp, tp, *tables, flags.data_ptr(), st)
                 _lib.call("rtk_score_hota_optimal_sim", B, lgp, prp, sim, sp, tp, A, *tables, c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
@@ -979,7 +1048,7 @@ class TrackScorer:
         sp, tp = None if score is None else score.data_ptr(), None if thr is None else thr.data_ptr()
         if pairs == "all":
             pr = self._pair_block()
-            if self.centre:
+            if self.has_sim:
                 _lib.call("rtk_score_identity_pairs_sim", B, self.T, lgp, ctypes.addressof(pr), self.pair_sim.data_ptr(), sp, tp, levels.data_ptr(), A,
                           c.data_ptr(), flags.data_ptr(), st)
             else:
