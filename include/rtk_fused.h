@@ -666,6 +666,87 @@ RTK_EXPORT int rtk_object_boxes(int B, int N, int K, const rtk_bcn_view_t *pc1, 
                                 const unsigned char *active, double min_extent, double *box, int *cand, int *valid, int *flags,
                                 rtk_stream_t stream);
 
+/* ---- Filtered boxes (csrc/track_box_filter.hip, csrc/box_filter.h, ratrack_amd/boxes.py): the boxes of a track, not of a frame -----------
+ * rtk_result_log_boxes gives every record the rectangle of that one frame's points.  This launch, run when the clip is over, links the
+ * records of every track and runs a constant-velocity Kalman filter over (x, y, z, yaw, l, w, h, vx, vy, vz) along each track, with
+ * an orientation correction before each update, optionally a backward (Rauch-Tung-Striebel) pass, and optionally a size taken from the
+ * whole track.  F, H, Q, R and P0 of that ten-state filter couple a coordinate with nothing but its own velocity, so it is computed as
+ * three two-state filters (x, y, z with their velocities) that share one covariance (P00, P01, P11) and four scalar filters: yaw with
+ * Pyaw, and l, w, h that share Psize.  With r_* = 1, q_pos = q_yaw = q_size, symmetry = 2 and no gaps this IS the dense ten-state
+ * filter (tests/test_box_filter_cpu.py holds the two together).
+ * THE RULE.  All arithmetic is float64; every sum, product and quotient is rounded on its own (no FMA); nothing is transcendental and
+ * every floor is exact, so every output word is a correctly rounded chain.  PI is the float64 nearest pi.
+ *   clips       those of rtk_result_log_select, walked the same way; a track is a (stream, clip, track id).
+ *   members     a record is ELIGIBLE if its input valid > 0, keep (where given) marks it and its id is not INT_MIN.  Of a frame's
+ *               eligible records with one track id the one with the smallest index is the track's MEMBER in that frame; the others are
+ *               not members and raise RTK_BOX_FLAG_DUPLICATE for their stream.  A member's frame number n is its frame's tag.index.
+ *   non-members come out empty: box, vel, state, aligned all zero, valid 0, the four link words -1.
+ *   segments    a track's members in log order.  The first starts a segment; a member whose k = n - n_prev (to the track's previous
+ *               member) is below 1 or above max_gap starts a new one.  Links never leave a segment.
+ *   measurement a member's input box read as z = (x, y, z, yaw, l, w, h).
+ *   start       (first member of a segment) mean = (z, 0, 0, 0); P00 = p0, P01 = 0, P11 = p0_vel; Pyaw = Psize = p0; the aligned reading
+ *               is the measurement as it is.
+ *   predict     k times: per coordinate c of x, y, z: m_c = m_c + v_c.  a = P00 + P01; b = P01 + P11; P00 = (a + b) + q_pos; P01 = b;
+ *               P11 = P11 + q_vel; Pyaw = Pyaw + q_yaw; Psize = Psize + q_size.
+ *   align       H = (2 PI) / symmetry; d = yaw_z - yaw; t = floor(d / H + 0.5); yaw_z' = yaw + (d - t H).  With symmetry = 4 and t
+ *               odd (t - 2 floor(t / 2) == 1) l_z and w_z are swapped.  symmetry 2: a rectangle without a front (a half turn changes
+ *               nothing); 4: without a front and without a labelled side (a quarter turn swaps l and w; what fitted boxes are).  yaw is
+ *               never wrapped inside the filter.
+ *   update      S = P00 + r_pos; K0 = P00 / S; K1 = P01 / S; per coordinate y = z_c - m_c; m_c = m_c + K0 y; v_c = v_c + K1 y.
+ *               P11 = P11 - K1 P01 (the old P01), then P01 = (1 - K0) P01, then P00 = (1 - K0) P00.
+ *               Ky = Pyaw / (Pyaw + r_yaw); yaw = yaw + Ky (yaw_z' - yaw); Pyaw = (1 - Ky) Pyaw.
+ *               Ks = Psize / (Psize + r_size); l, w, h each: m = m + Ks (z' - m), against the aligned reading; Psize = (1 - Ks) Psize.
+ *   smooth      (smooth = 1) inside a segment from its last member backwards; the last member's smoothed mean is its filtered one.
+ *               For member p whose successor lies k frames on: (m-, P-) = p's filtered state predicted k times;
+ *               C00 = P00 + k P01; C01 = P01; C10 = P01 + k P11; C11 = P11 (p's filtered P); det = P-00 P-11 - P-01 P-01;
+ *               G00 = (C00 P-11 - C01 P-01) / det; G01 = (C01 P-00 - C00 P-01) / det;
+ *               G10 = (C10 P-11 - C11 P-01) / det; G11 = (C11 P-00 - C10 P-01) / det;
+ *               per coordinate, e0 = the successor's smoothed m_c - m-_c, e1 = its smoothed v_c - v_c:
+ *               m_c = m_c + (G00 e0 + G01 e1); v_c = v_c + (G10 e0 + G11 e1).
+ *               yaw = yaw + (Pyaw / P-yaw) (yaw_successor - yaw); l, w, h likewise with Psize / P-size.  No smoothed covariance.
+ *   extent      (size_rule = 1) for each of l, w, h: of the segment's n aligned readings, ordered by (value, record index), the one
+ *               of 0-based rank (size_percent (n - 1)) / 100 (integer division) replaces that word of every member's final mean -- one
+ *               of the measured values.  A track of partial views reaches the object's size this way; a percentile below 100 guards
+ *               against a frame in which two clusters merged.  It looks at the whole segment: with smooth = 0 the result is then NOT
+ *               causal either.
+ *   output      from the final mean (smoothed if smooth, with the extent's sizes if size_rule): if w > l they are swapped and
+ *               yaw = yaw + PI / 2; yaw = yaw - floor((yaw + PI / 2) / PI) PI, then one corrective -PI (yaw >= PI / 2) or +PI
+ *               (yaw < -PI / 2).  out_box = (x, y, z, l, w, h, yaw, l w): rtk_result_log_boxes' layout.
+ *               vel = (vx, vy, vz, the final mean's yaw before any of that: unwrapped).
+ *               state = the FILTERED mean (x, y, z, yaw, l, w, h, vx, vy, vz), P00, P01, P11, Pyaw, Psize, 0.
+ *               aligned = (yaw_z', l', w', h').   out_valid = the input's valid.
+ *               link = previous member | gap k | next member | the segment's first member: record indices of the stream, -1 where
+ *               there is none (a segment's first member has no previous member and no gap).
+ * With smooth = 0 and size_rule = 0 a record's outputs depend on its track's earlier records only: the bits an in-step filter would
+ * produce.  The filter runs in each frame's own sensor frame (no ego-motion compensation). */
+#define RTK_BOX_FILTER_MAX_GAP 64    /* the largest max_gap: frames a segment may skip between two members */
+#define RTK_BOX_FLAG_DUPLICATE 4     /* rtk_result_log_filter_boxes: a track id twice among a frame's eligible records */
+#define RTK_BOX_FLAG_TRACKS 8        /* rtk_result_log_filter_boxes: more track ids in one clip than the track table holds (2048) */
+
+typedef struct {
+    double r_pos, r_yaw, r_size;            /* measurement variances: finite, > 0 */
+    double q_pos, q_vel, q_yaw, q_size;     /* process variances per frame: finite, >= 0 */
+    double p0, p0_vel;                      /* the initial variances: finite, > 0 */
+    int symmetry;                           /* 2 or 4 */
+    int max_gap;                            /* 1 ... RTK_BOX_FILTER_MAX_GAP */
+    int smooth;                             /* 0 or 1 */
+    int size_rule;                          /* 0: the filter's sizes, 1: the extent rule */
+    int size_percent;                       /* 0 ... 100 */
+} rtk_box_filter_t;
+
+/* rtk_result_log_filter_boxes: the rule above over every stream's log.  One workgroup per stream.  keep: NULL or (B,R) uint8.
+ * box (B,R,8) float64 and valid (B,R) int32 are rtk_result_log_boxes' outputs (or boxes from anywhere in that layout) and are only
+ * read; the outputs must not alias them.  out_box (B,R,8), vel (B,R,4), state (B,R,16), aligned (B,R,4) float64, out_valid (B,R)
+ * and link (B,R,4) int32 are written for the records below the stream's cursor only; nothing at or beyond it is touched.  flags (B) is
+ * WRITTEN: 0, RTK_BOX_FLAG_DUPLICATE, or RTK_BOX_FLAG_TRACKS for a stream with a clip of more track ids than the table holds (as
+ * rtk_result_log_select counts them, over all the clip's records): that clip and the stream's later clips come out empty, record for
+ * record -- a clip is never filtered wrongly.  Parameters outside the ranges above refuse the call.  No allocation, no
+ * synchronisation, one writer per word and plain stores: the same bits on every run, and the launch can be captured.  The log is
+ * walked with the scorer's clamps and every link read back is checked against the cursor.  Static LDS: 48 KiB. */
+RTK_EXPORT int rtk_result_log_filter_boxes(int B, const rtk_result_log_t *log, const unsigned char *keep, const double *box, const int *valid,
+                                           const rtk_box_filter_t *par, double *out_box, int *out_valid, double *vel, double *state,
+                                           double *aligned, int *link, int *flags, rtk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

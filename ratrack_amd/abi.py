@@ -54,6 +54,11 @@ class ResultLog(ctypes.Structure):
                                                                       "points", "flags")]
 
 
+class BoxFilter(ctypes.Structure):
+    _fields_ = [(n, _d) for n in ("r_pos", "r_yaw", "r_size", "q_pos", "q_vel", "q_yaw", "q_size", "p0", "p0_vel")] + \
+               [(n, _i) for n in ("symmetry", "max_gap", "smooth", "size_rule", "size_percent")]
+
+
 # ---- include/rtk_gt.h -----------------------------------------------------------------------------------------------------------
 
 class GtBoxes(ctypes.Structure):
@@ -147,7 +152,7 @@ class PwWgradJob(ctypes.Structure):
 STRUCTS = {
     "rtk_src_t": Src, "rtk_layer_t": Layer, "rtk_interp_t": Interp, "rtk_gterm_job_t": GtermJob, "rtk_copy_job_t": CopyJob,
     "rtk_layout_job_t": LayoutJob, "rtk_bcn_view_t": View, "rtk_track_frame_t": TrackFrame,
-    "rtk_result_log_t": ResultLog,
+    "rtk_result_log_t": ResultLog, "rtk_box_filter_t": BoxFilter,
     "rtk_gt_boxes_t": GtBoxes, "rtk_gt_in_t": GtIn, "rtk_gt_out_t": GtOut, "rtk_eval_in_t": EvalIn,
     "rtk_gt_objects_in_t": GtObjectsIn, "rtk_gt_objects_out_t": GtObjectsOut, "rtk_track_score_in_t": ScoreIn,
     "rtk_track_score_state_t": ScoreState, "rtk_track_score_out_t": ScoreOut, "rtk_score_log_t": ScoreLog,
@@ -157,7 +162,7 @@ STRUCTS = {
 }
 
 # name -> argtypes.  A struct pointer that callers pass as ctypes.addressof() is _p; one they pass as an array or byref() is typed.
-# The argument blocks of rtk_gt.h and rtk_score.h (GtIn, GtOut, EvalIn, GtObjectsIn, ..., ScoreOut, ScoreLog, ScoreMemory, ScorePairs), rtk_track_frame_t and rtk_result_log_t go by
+# The argument blocks of rtk_gt.h and rtk_score.h (GtIn, GtOut, EvalIn, GtObjectsIn, ..., ScoreOut, ScoreLog, ScoreMemory, ScorePairs), rtk_track_frame_t, rtk_result_log_t and rtk_box_filter_t go by
 # address; the *_lds_bytes are host functions that return a byte count.
 SIGNATURES = {
     # ---- include/rtk_pointnet2.h
@@ -225,6 +230,7 @@ SIGNATURES = {
     "rtk_result_log_select": [_i, _p, _p, _d, _i, _i, _p, _p, _p, _p, _p],
     "rtk_result_log_boxes": [_i, _p, _p, _d] + [_p] * 4 + [_p],
     "rtk_object_boxes": [_i] * 3 + [_p] * 4 + [_d] + [_p] * 4 + [_p],
+    "rtk_result_log_filter_boxes": [_i] + [_p] * 12 + [_p],
     # ---- include/rtk_gt.h
     "rtk_gt_labels": [_p, _p, _p],
     "rtk_eval_frame": [_p, _p, _p, _p],

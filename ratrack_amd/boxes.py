@@ -11,6 +11,15 @@ with the points' z range for its height: a search over the directions of all poi
 include/rtk_fused.h ("Oriented boxes"), implemented in csrc/box_fit.h, one HIP launch for a whole step (rtk_object_boxes) or a whole
 result log (rtk_result_log_boxes, `ResultLog.boxes` / `ResultLog.write_kitti`).  `BatchedTracker(boxes=True)` issues the launch
 inside the step.  An object of more than MAX_POINTS points is fitted axis-aligned; `axis_only` marks it and `check()` says so.
+
+    fb = log.filter_boxes(log.boxes(), filter=BoxFilter(smooth=1, size_rule=1))      # ResultLog; one launch, when the clip is over
+    fb.box, fb.valid                             # a box per record in the same layout, from its whole track
+    fb.vel[b, r]                                 # (vx, vy, vz, unwrapped yaw): the tracked object's velocity, metres per frame
+
+A box fitted from one frame's two to ten radar points is a fraction of the object and its heading jumps by a quarter turn.
+`BoxFilter` holds the parameters of a constant-velocity Kalman filter run along every track of a result log
+(rtk_result_log_filter_boxes, csrc/track_box_filter.hip; the rule is stated in include/rtk_fused.h, "Filtered boxes"), with an optional
+backward pass and an optional size from the whole track; `FilteredBoxes` is its result and goes wherever an `ObjectBoxes` goes.
 """
 import ctypes
 import math
@@ -24,7 +33,9 @@ from .gt_device import _flag_bytes
 
 MAX_POINTS = 128                       # RTK_BOX_MAX_POINTS
 MAX_OBJECTS = 256                      # RTK_RESULT_MAX_OBJECTS
-FLAG_AXIS, FLAG_OBJECTS = 1, 2         # RTK_BOX_FLAG_*
+FLAG_AXIS, FLAG_OBJECTS, FLAG_DUPLICATE, FLAG_TRACKS = 1, 2, 4, 8      # RTK_BOX_FLAG_*
+FILTER_MAX_GAP = 64                    # RTK_BOX_FILTER_MAX_GAP
+TRACKS = 2048                          # RTK_SCORE_SWEEP_TRACKS: track ids of one clip the filter can tell apart
 CX, CY, CZ, L, W, H, YAW, AREA = range(8)      # the words of a box
 
 
@@ -55,6 +66,10 @@ def flag_message(b, f, rows):
         return "boxes: stream %d has a num_objects outside [0, max_objects=%d]: nothing of it was fitted" % (b, rows)
     if f & FLAG_AXIS:
         return "boxes: stream %d has an object of more than %d points: it was fitted axis-aligned (axis_only marks it)" % (b, MAX_POINTS)
+    if f & FLAG_TRACKS:
+        return "boxes: stream %d has a clip with more than %d track ids: it and the later clips were not filtered" % (b, TRACKS)
+    if f & FLAG_DUPLICATE:
+        return "boxes: stream %d has a frame with one track id on two records: the first was filtered, the others have no box" % b
     return None
 
 
@@ -117,3 +132,100 @@ def object_boxes(out, min_extent=0.0, into=None):
     object `out.object_ids[b, j]`; rows past `out.num_objects[b]` and inactive streams hold no box (valid = 0).  into: an ObjectBoxes
     to write into (`ObjectBoxes.empty(B, out.max_objects, device)`): nothing is allocated, so the call can be captured in a graph."""
     return object_boxes_raw(out.pc1, out.obj, out.num_objects, out.max_objects, active=out.active, min_extent=min_extent, into=into)
+
+
+# ---- filtered boxes ---------------------------------------------------------------------------------------------------------------
+
+def _number(name, v, least, strict):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(float(v)) or \
+            float(v) < least or (strict and float(v) == least):
+        raise ValueError("BoxFilter: %s=%r must be a finite number %s %g" % (name, v, ">" if strict else ">=", least))
+    return float(v)
+
+
+def _integer(name, v, allowed, text):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in allowed:
+        raise ValueError("BoxFilter: %s=%r must be %s" % (name, v, text))
+    return int(v)
+
+
+class BoxFilter:
+    """The parameters of the track box filter (rtk_box_filter_t), checked on construction (ValueError; no device is touched).
+    r_pos, r_yaw, r_size: measurement variances (> 0); q_pos, q_vel, q_yaw, q_size: process variances per frame (>= 0); p0, p0_vel: the
+    initial variances (> 0).  symmetry: 2 (a box without a front) or 4 (without a front and a labelled side: fitted boxes).  max_gap:
+    the frames between two members of a track beyond which the filter starts again (1 ... 64).  smooth: 1 adds the backward pass.
+    size_rule: 0 the filter's sizes, 1 the reading of rank size_percent (0 ... 100) among each segment's readings.  The defaults are
+    the values of the filter the tracker was modelled on, for fitted boxes; `reference()` is that filter itself."""
+
+    def __init__(self, r_pos=1.0, r_yaw=1.0, r_size=1.0, q_pos=1.0, q_vel=0.01, q_yaw=1.0, q_size=1.0, p0=10.0, p0_vel=10000.0, symmetry=4,
+                 max_gap=2, smooth=0, size_rule=0, size_percent=90):
+        self.r_pos, self.r_yaw, self.r_size = (_number(n, v, 0.0, True) for n, v in (("r_pos", r_pos), ("r_yaw", r_yaw), ("r_size", r_size)))
+        self.q_pos, self.q_vel, self.q_yaw, self.q_size = (_number(n, v, 0.0, False) for n, v in (("q_pos", q_pos), ("q_vel", q_vel),
+                                                                                                  ("q_yaw", q_yaw), ("q_size", q_size)))
+        self.p0, self.p0_vel = _number("p0", p0, 0.0, True), _number("p0_vel", p0_vel, 0.0, True)
+        self.symmetry = _integer("symmetry", symmetry, (2, 4), "2 or 4")
+        self.max_gap = _integer("max_gap", max_gap, range(1, FILTER_MAX_GAP + 1), "an integer in [1, %d]" % FILTER_MAX_GAP)
+        self.smooth = _integer("smooth", smooth, (0, 1), "0 or 1")
+        self.size_rule = _integer("size_rule", size_rule, (0, 1), "0 (the filter's sizes) or 1 (the extent rule)")
+        self.size_percent = _integer("size_percent", size_percent, range(0, 101), "an integer in [0, 100]")
+
+    @classmethod
+    def reference(cls, **kw):
+        """The ten-state filter with its shipped parameters: a half-turn symmetry, no gaps bridged beyond one frame."""
+        return cls(**dict(dict(symmetry=2, max_gap=1), **kw))
+
+    FIELDS = ("r_pos", "r_yaw", "r_size", "q_pos", "q_vel", "q_yaw", "q_size", "p0", "p0_vel", "symmetry", "max_gap", "smooth", "size_rule",
+              "size_percent")
+
+    def block(self):
+        from .abi import BoxFilter as _Par
+        return _Par(*(getattr(self, n) for n in self.FIELDS))
+
+    def __repr__(self):
+        return "BoxFilter(%s)" % ", ".join("%s=%r" % (n, getattr(self, n)) for n in self.FIELDS)
+
+
+def check_filter(filter):
+    """-> filter; raises ValueError unless it is a BoxFilter whose fields still pass its checks."""
+    if not isinstance(filter, BoxFilter):
+        raise ValueError("filter=%r: a boxes.BoxFilter" % (filter,))
+    BoxFilter(**{n: getattr(filter, n) for n in BoxFilter.FIELDS})
+    return filter
+
+
+class FilteredBoxes(ObjectBoxes):
+    """`ResultLog.filter_boxes`' result: box (B,R,8) float64, valid (B,R), flags (B) as an ObjectBoxes has them (box from the record's
+    whole track; flags FLAG_DUPLICATE | FLAG_TRACKS), cand = the input boxes' cand tensor itself (the filter has no candidates of its
+    own: `filter_boxes` sets the reference, the launch does not write it), and vel (B,R,4) float64 = vx, vy, vz per frame and the
+    unwrapped yaw; state (B,R,16) float64 = the filtered mean (x, y, z, yaw, l, w, h, vx, vy, vz), P00, P01, P11, Pyaw, Psize, 0; aligned
+    (B,R,4) float64 = the reading's yaw, l, w, h as the filter took them; link (B,R,4) int32 = previous member | gap | next member |
+    the segment's first member (record indices, -1: none).  Written below each stream's records cursor only."""
+
+    def __init__(self, box, cand, valid, flags, vel, state, aligned, link):
+        ObjectBoxes.__init__(self, box, cand, valid, flags)
+        self.vel, self.state, self.aligned, self.link = vel, state, aligned, link
+
+    @classmethod
+    def empty(cls, B, rows, device):
+        """Uninitialised buffers (what `into=` takes)."""
+        f64 = lambda *s: torch.empty(*s, dtype=torch.float64, device=device)
+        i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=device)
+        return cls(f64(B, rows, 8), i32(B, rows), i32(B, rows), i32(B), f64(B, rows, 4), f64(B, rows, 16), f64(B, rows, 4), i32(B, rows, 4))
+
+    @classmethod
+    def zeros(cls, B, rows, device):
+        out = cls.empty(B, rows, device)
+        for t in (out.box, out.cand, out.valid, out.flags, out.vel, out.state, out.aligned, out.link):
+            t.zero_()
+        return out
+
+
+def check_filtered_into(into, B, rows, dev):
+    """`into` as a FilteredBoxes of B streams of `rows` records on `dev`; raises ValueError."""
+    check_into(into, B, rows, dev)
+    for name, shape, dtype in (("vel", (B, rows, 4), torch.float64), ("state", (B, rows, 16), torch.float64),
+                               ("aligned", (B, rows, 4), torch.float64), ("link", (B, rows, 4), torch.int32)):
+        t = getattr(into, name, None)
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != torch.device(dev):
+            raise ValueError("into.%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
+    return into

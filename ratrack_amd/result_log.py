@@ -22,6 +22,9 @@ score `TrackScorer.sweep` reports its operating point in, the same bits -- and t
 
 `boxes` (rtk_result_log_boxes, ratrack_amd/boxes.py) fits every record's oriented box in one launch, and `write_kitti` writes them, for
 the records a selection keeps, as KITTI tracking result files, one per sequence: the format the evaluators of the field read.
+`filter_boxes` (rtk_result_log_filter_boxes, `boxes.BoxFilter`) turns those per-frame boxes into the boxes of each track -- a Kalman
+filter along every (stream, clip, track id), optionally smoothed, optionally with a size from the whole track -- in one more launch, and
+`write_kitti(filter=...)` writes them instead.
 
 Only `write`, `write_kitti`, `frames`, `check`, `download` and `select(check=True)` synchronise.  `seq` / `index` given as host values cost one small
 host-to-device copy per append; given as (B,) int32 device tensors they are read at launch time and cost nothing.
@@ -355,7 +358,8 @@ class ResultLog:
         (B,records) uint8 or None, and the sticky flags or-ed with the selection's.  Two transfers whatever the frame count: the
         cursors and flags, then everything below the largest cursors in one concatenation.  boxes (`boxes()`'s result): its rows
         travel in the same two transfers and join host as box (B,records,8) float64, box_cand, box_valid (B,records) int32 and
-        box_flags (B) int32 (kept apart from `flags`: a box flag refuses no frame)."""
+        box_flags (B) int32 (kept apart from `flags`: a box flag refuses no frame); `filter_boxes()`'s result goes the same way and
+        adds box_vel (B,records,4) float64."""
         head = [self.cursor.reshape(-1), self.flags] + ([] if selection is None else [selection.flags]) + ([] if boxes is None else [boxes.flags])
         head = torch.cat(head).cpu().numpy()
         B = self.B
@@ -370,6 +374,8 @@ class ResultLog:
             parts.append(("keep", selection.keep[:, :r].to(torch.int32)))
         if boxes is not None:
             parts += [("box", boxes.box[:, :r].reshape(B, -1).view(torch.int32)), ("box_cand", boxes.cand[:, :r]), ("box_valid", boxes.valid[:, :r])]
+            if hasattr(boxes, "vel"):      # a FilteredBoxes: the velocity rows travel too
+                parts.append(("box_vel", boxes.vel[:, :r].reshape(B, -1).view(torch.int32)))
         flat = torch.cat([t.reshape(-1) for _, t in parts]).cpu().numpy()
         host, o = dict(cursor=cursor), 0
         for name, t in parts:
@@ -380,6 +386,8 @@ class ResultLog:
         keep = host.pop("keep").astype(np.uint8) if selection is not None else None
         if boxes is not None:
             host["box"] = host["box"].view(np.float64).reshape(B, r, 8)
+            if "box_vel" in host:
+                host["box_vel"] = host["box_vel"].view(np.float64).reshape(B, r, 4)
             host["box_flags"] = head[-B:].copy() if B else head[:0].copy()
         return host, keep, flags
 
@@ -423,8 +431,42 @@ class ResultLog:
                   out.box.data_ptr(), out.cand.data_ptr(), out.valid.data_ptr(), out.flags.data_ptr(), _stream())
         return out
 
+    def filter_boxes(self, boxes, keep=None, filter=None, into=None):
+        """The boxes of every track instead of every frame (ratrack_amd/boxes.py, `BoxFilter`; rtk_result_log_filter_boxes): one
+        launch over the log when the clip is over, no synchronisation, -> boxes.FilteredBoxes with one row per record slot, written
+        below each stream's records cursor only (zero elsewhere).  boxes: `boxes()`'s result, or an ObjectBoxes of (B,R) rows from
+        anywhere; it is only read.  keep: None, a `Selection` or its (B,R) uint8 `keep`: the records it does not mark belong to no
+        track and get no box.  filter: a boxes.BoxFilter (None: its defaults).  into: a FilteredBoxes of (B,R) rows to write into
+        (`FilteredBoxes.empty(B, R, device)`; nothing is allocated: the call can be captured)."""
+        from . import boxes as _boxes
+        flt = _boxes.check_filter(_boxes.BoxFilter() if filter is None else filter)
+        keep = getattr(keep, "keep", keep)
+        dev = self.cursor.device
+        if keep is not None:
+            if not torch.is_tensor(keep) or tuple(keep.shape) != (self.B, self.R) or keep.dtype not in (torch.uint8, torch.bool):
+                raise ValueError("ResultLog.filter_boxes: keep must be a (%d,%d) uint8 tensor (Selection.keep)" % (self.B, self.R))
+        try:
+            _boxes.check_into(boxes, self.B, self.R, dev)
+        except ValueError as e:
+            raise ValueError("ResultLog.filter_boxes: boxes: " + str(e).replace("into.", "")) from None
+        if into is not None:
+            out = _boxes.check_filtered_into(into, self.B, self.R, dev)
+            if out.box.data_ptr() == boxes.box.data_ptr() or out.valid.data_ptr() == boxes.valid.data_ptr():
+                raise ValueError("ResultLog.filter_boxes: into must not share box or valid with the input boxes")
+        else:
+            out = _boxes.FilteredBoxes.zeros(self.B, self.R, dev)
+        if keep is not None:
+            keep = keep.to(device=dev).contiguous()
+            keep = keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+        out.cand = boxes.cand
+        lg, par = self._block(), flt.block()
+        _lib.call("rtk_result_log_filter_boxes", self.B, ctypes.addressof(lg), None if keep is None else keep.data_ptr(), boxes.box.data_ptr(),
+                  boxes.valid.data_ptr(), ctypes.addressof(par), out.box.data_ptr(), out.valid.data_ptr(), out.vel.data_ptr(),
+                  out.state.data_ptr(), out.aligned.data_ptr(), out.link.data_ptr(), out.flags.data_ptr(), _stream())
+        return out
+
     def write_kitti(self, root, names, transforms=None, obj_type="Car", threshold=None, min_hits=1, min_track_frames=1, min_extent=0.0,
-                    check=True):
+                    check=True, filter=None):
         """KITTI tracking result files (vod_io.format_kitti_track_line), one per sequence: <root>/<names[seq]>.txt with one line per
         kept record that has a box, in (index, record) order; the frame number is the frame's index, the score the record's confidence.
         `select` runs with the given filters (when one is given), `boxes` on what it keeps, then everything is downloaded once.
@@ -432,12 +474,21 @@ class ResultLog:
         label fields of the camera frame (vod_io.box_label_fields); a logged frame without an entry raises ValueError before any file
         is written.  check=True raises RuntimeError naming the stream for any flag of the log or of the selection before anything is
         written; check=False writes the streams without one.  A stream with an object above boxes.MAX_POINTS points is written, its
-        box axis-aligned, with a warning.  Returns the paths."""
+        box axis-aligned, with a warning.  filter: None, or a boxes.BoxFilter: the files hold `filter_boxes`' boxes of the kept
+        records instead of the per-frame ones (one more launch; the fit's warning still comes from the per-frame boxes, and a stream
+        whose filter raised a flag is written with a warning too).  Returns the paths."""
         import warnings
         from . import boxes as _boxes, vod_io
         _boxes.check_min_extent(min_extent)
+        if filter is not None:
+            _boxes.check_filter(filter)
         sel = self._selected(threshold, min_hits, min_track_frames)
-        host, keep, flags = self.download(sel, boxes=self.boxes(sel, min_extent))
+        fitted = self.boxes(sel, min_extent)
+        if filter is not None:
+            filtered = self.filter_boxes(fitted, sel, filter)
+            filtered.flags = filtered.flags | fitted.flags
+            fitted = filtered
+        host, keep, flags = self.download(sel, boxes=fitted)
         if check:
             raise_on_flags(flags.tolist(), self.K)
         streams = [b for b in range(self.B) if not flags[b]]
