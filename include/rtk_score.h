@@ -324,7 +324,7 @@ RTK_EXPORT int rtk_score_identity(int B, int T, const rtk_score_log_t *log, cons
                                   const double *threshold /* device scalar, or NULL: nothing removed */, const double *alphas /* device, (count) */,
                                   int count, long long *counters /* (count,B,6) */, int *flags /* (B) */, rtk_stream_t stream);
 
-/* ---- Per-frame optimal matching at an IoU threshold (csrc/track_score_pairs.hip, csrc/track_optimal.hip, csrc/lds_assignment.h,
+/* ---- Per-frame optimal matching at an IoU threshold (csrc/track_score.hip, csrc/track_optimal.hip, csrc/lds_assignment.h,
  *      TrackScorer(sweep_pairs=...), TrackScorer.sweep(matching="optimal"), TrackScorer.clear_optimal) ------------------------------
  *
  * Everything above rests on rtk_track_score's matching rule: each detection takes its single best object, first come first served,
@@ -498,7 +498,7 @@ RTK_EXPORT int rtk_score_identity_pairs(int B, int T, const rtk_score_log_t *log
                                         const double *alphas /* device, (count) */, int count, long long *counters /* (count,B,6) */,
                                         int *flags /* (B) */, rtk_stream_t stream);
 
-/* ---- TrackEval's centre-distance similarity on the pair log (csrc/track_score_centre.hip, csrc/track_replay_sim.hip,
+/* ---- TrackEval's centre-distance similarity on the pair log (csrc/track_score.hip, csrc/track_optimal.hip and its siblings,
  *      TrackScorer(similarity="centre")) ----------------------------------------------------------------------------------------------
  *
  * The two sections above say that what still does not agree with TrackEval is the similarity: a point IoU where TrackEval has a box IoU.
@@ -569,7 +569,7 @@ RTK_EXPORT int rtk_score_identity_pairs_sim(int B, int T, const rtk_score_log_t 
                                             const double *alphas /* device, (count) */, int count, long long *counters /* (count,B,6) */,
                                             int *flags /* (B) */, rtk_stream_t stream);
 
-/* ---- The oriented-box IoU on the pair log, in three dimensions and in the bird's-eye view (csrc/track_score_box.hip,
+/* ---- The oriented-box IoU on the pair log, in three dimensions and in the bird's-eye view (csrc/track_score.hip,
  *      TrackScorer(similarity="box") / TrackScorer(similarity="box_bev")) --------------------------------------------------------------
  *
  * The evaluators the result files are written for (the KITTI devkit, AB3DMOT, TrackEval's loaders, the VoD devkit) match detections to

@@ -132,6 +132,22 @@ __device__ __forceinline__ bool lw_valid_pair(const rtk_score_pairs_t &pr, const
     return true;
 }
 
+// The pair log as a replay kernel's argument: the pair block and, with SIM, pair_sim right behind it.  One kernel template then has, for
+// either value of SIM, exactly the argument segment of a kernel written for that value alone: a kernel without SIM carries no unused word.
+template <bool SIM>
+struct lw_pairs_arg_t {
+    rtk_score_pairs_t pr;
+    lw_pairs_arg_t(const rtk_score_pairs_t &p, const double *) : pr(p) {}
+    __device__ const double *sim() const { return nullptr; }
+};
+template <>
+struct lw_pairs_arg_t<true> {
+    rtk_score_pairs_t pr;
+    const double *pair_sim;
+    lw_pairs_arg_t(const rtk_score_pairs_t &p, const double *s) : pr(p), pair_sim(s) {}
+    __device__ const double *sim() const { return pair_sim; }
+};
+
 // host side: a log argument with every table present
 static inline bool lw_log_ok(const rtk_score_log_t *lg) {
     return lg && lg->F >= 1 && lg->R >= 1 && lg->cursor && lg->frame && lg->label && lg->rec_track && lg->rec_best && lg->rec_conf && lg->rec_iou;

@@ -16,22 +16,26 @@
 // solve the assignment together.  Integers and fixed-order float64 sums only: the same bits on every run, and the bits of a host loop
 // written from the definitions.  Every level re-solves the same assignment: the grid fills the device with it (DESIGN.md section 4.9
 // has the measured cost).  The frame decode, the track table, the pair list and the valid-pair test are score_log_walk.h's.
-// The LDS layouts and the bodies are track_hota_optimal_body.h's, instantiated here on the point IoU of the logged integers.
+// The LDS layouts and the bodies are track_hota_optimal_body.h's, instantiated here twice: on the point IoU of the logged integers
+// (rtk_score_alignment, rtk_score_hota_optimal) and, SIM, on the similarity the pair log itself carries (rtk_score_alignment_sim,
+// rtk_score_hota_optimal_sim; track_optimal.hip's header has the rule).  The same LDS tables, grids and arithmetic either way.
 #include "track_hota_optimal_body.h"
 
-template <int TCAP>
-__global__ __launch_bounds__(RTK_WAVE) void alignment_kernel(int T, const rtk_score_log_t lg, const rtk_score_pairs_t pr, const double *rec_score,
-                                                             const double *threshold, double *pair_a, int *pair_index, int *clip_cg, int *clip_ct,
-                                                             int *flags) {
+template <int TCAP, bool SIM>
+__global__ __launch_bounds__(RTK_WAVE) void alignment_kernel(int T, const rtk_score_log_t lg, const lw_pairs_arg_t<SIM> pa,
+                                                             const double *rec_score, const double *threshold, double *pair_a, int *pair_index,
+                                                             int *clip_cg, int *clip_ct, int *flags) {
     __shared__ __attribute__((aligned(16))) int al_smem[al_words(TCAP)];
-    alignment_body<TCAP, false>(al_smem, T, lg, pr, rec_score, threshold, pair_a, pair_index, clip_cg, clip_ct, flags, nullptr);
+    alignment_body<TCAP, SIM>(al_smem, T, lg, pa.pr, rec_score, threshold, pair_a, pair_index, clip_cg, clip_ct, flags, pa.sim());
 }
 
-__global__ __launch_bounds__(RTK_WAVE) void hota_optimal_kernel(const rtk_score_log_t lg, const rtk_score_pairs_t pr, const double *rec_score,
-                                                                const double *threshold, const double *pair_a, const int *pair_index,
-                                                                const int *clip_cg, const int *clip_ct, long long *counters, double *sums, int *flags) {
+template <bool SIM>
+__global__ __launch_bounds__(RTK_WAVE) void hota_optimal_kernel(const rtk_score_log_t lg, const lw_pairs_arg_t<SIM> pa,
+                                                                const double *rec_score, const double *threshold, const double *pair_a,
+                                                                const int *pair_index, const int *clip_cg, const int *clip_ct, long long *counters,
+                                                                double *sums, int *flags) {
     __shared__ __attribute__((aligned(16))) int ho_smem[ho_words()];
-    hota_optimal_body<false>(ho_smem, lg, pr, rec_score, threshold, pair_a, pair_index, clip_cg, clip_ct, counters, sums, flags, nullptr);
+    hota_optimal_body<SIM>(ho_smem, lg, pa.pr, rec_score, threshold, pair_a, pair_index, clip_cg, clip_ct, counters, sums, flags, pa.sim());
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -42,28 +46,56 @@ extern "C" int rtk_score_alignment_lds_bytes(int T) {
     return (int)al_lds(T);
 }
 
+// name: the entry point's, for its messages; SIM: the pass on pair_sim, refused when that is NULL
+template <bool SIM>
+static int al_launch(const char *name, int B, int T, const rtk_score_log_t *lg, const rtk_score_pairs_t *pr, const double *pair_sim,
+                     const double *rec_score, const double *threshold, double *pair_a, int *pair_index, int *clip_cg, int *clip_ct, int *flags,
+                     rtk_stream_t stream) {
+    const int status = al_validate(name, B, T, lg, pr, pair_a, pair_index, clip_cg, clip_ct, flags);
+    if (status != RTK_OK) return status;
+    if (SIM) RTK_REQUIRE(pair_sim, "%s: null pair_sim", name);
+    const auto kernel = T <= AL_TCAP_SMALL ? alignment_kernel<AL_TCAP_SMALL, SIM> : alignment_kernel<AL_TCAP_LARGE, SIM>;
+    kernel<<<B, RTK_WAVE, 0, (hipStream_t)stream>>>(T, *lg, lw_pairs_arg_t<SIM>(*pr, pair_sim), rec_score, threshold, pair_a, pair_index, clip_cg, clip_ct,
+                                                    flags);
+    RTK_CHECK_LAUNCH(name);
+    return RTK_OK;
+}
+
+template <bool SIM>
+static int ho_launch(const char *name, int B, const rtk_score_log_t *lg, const rtk_score_pairs_t *pr, const double *pair_sim, const double *rec_score,
+                     const double *threshold, int alphas, const double *pair_a, const int *pair_index, const int *clip_cg, const int *clip_ct,
+                     long long *counters, double *sums, int *flags, rtk_stream_t stream) {
+    const int status = ho_validate(name, B, lg, pr, alphas, pair_a, pair_index, clip_cg, clip_ct, counters, sums, flags);
+    if (status != RTK_OK) return status;
+    if (SIM) RTK_REQUIRE(pair_sim, "%s: null pair_sim", name);
+    hota_optimal_kernel<SIM><<<dim3(B, alphas), RTK_WAVE, 0, (hipStream_t)stream>>>(*lg, lw_pairs_arg_t<SIM>(*pr, pair_sim), rec_score, threshold, pair_a,
+                                                                                     pair_index, clip_cg, clip_ct, counters, sums, flags);
+    RTK_CHECK_LAUNCH(name);
+    return RTK_OK;
+}
+
 extern "C" int rtk_score_alignment(int B, int T, const rtk_score_log_t *lg, const rtk_score_pairs_t *pr, const double *rec_score,
                                    const double *threshold, double *pair_a, int *pair_index, int *clip_cg, int *clip_ct, int *flags,
                                    rtk_stream_t stream) {
-    const int status = al_validate("score_alignment", B, T, lg, pr, pair_a, pair_index, clip_cg, clip_ct, flags);
-    if (status != RTK_OK) return status;
-    if (T <= AL_TCAP_SMALL)
-        alignment_kernel<AL_TCAP_SMALL><<<B, RTK_WAVE, 0, (hipStream_t)stream>>>(T, *lg, *pr, rec_score, threshold, pair_a, pair_index, clip_cg, clip_ct,
-                                                                                  flags);
-    else
-        alignment_kernel<AL_TCAP_LARGE><<<B, RTK_WAVE, 0, (hipStream_t)stream>>>(T, *lg, *pr, rec_score, threshold, pair_a, pair_index, clip_cg, clip_ct,
-                                                                                  flags);
-    RTK_CHECK_LAUNCH("score_alignment");
-    return RTK_OK;
+    return al_launch<false>("score_alignment", B, T, lg, pr, nullptr, rec_score, threshold, pair_a, pair_index, clip_cg, clip_ct, flags, stream);
+}
+
+extern "C" int rtk_score_alignment_sim(int B, int T, const rtk_score_log_t *lg, const rtk_score_pairs_t *pr, const double *pair_sim,
+                                       const double *rec_score, const double *threshold, double *pair_a, int *pair_index, int *clip_cg, int *clip_ct,
+                                       int *flags, rtk_stream_t stream) {
+    return al_launch<true>("score_alignment_sim", B, T, lg, pr, pair_sim, rec_score, threshold, pair_a, pair_index, clip_cg, clip_ct, flags, stream);
 }
 
 extern "C" int rtk_score_hota_optimal(int B, const rtk_score_log_t *lg, const rtk_score_pairs_t *pr, const double *rec_score, const double *threshold,
                                       int alphas, const double *pair_a, const int *pair_index, const int *clip_cg, const int *clip_ct,
                                       long long *counters, double *sums, int *flags, rtk_stream_t stream) {
-    const int status = ho_validate("score_hota_optimal", B, lg, pr, alphas, pair_a, pair_index, clip_cg, clip_ct, counters, sums, flags);
-    if (status != RTK_OK) return status;
-    hota_optimal_kernel<<<dim3(B, alphas), RTK_WAVE, 0, (hipStream_t)stream>>>(*lg, *pr, rec_score, threshold, pair_a, pair_index, clip_cg, clip_ct,
-                                                                                counters, sums, flags);
-    RTK_CHECK_LAUNCH("score_hota_optimal");
-    return RTK_OK;
+    return ho_launch<false>("score_hota_optimal", B, lg, pr, nullptr, rec_score, threshold, alphas, pair_a, pair_index, clip_cg, clip_ct, counters, sums,
+                            flags, stream);
+}
+
+extern "C" int rtk_score_hota_optimal_sim(int B, const rtk_score_log_t *lg, const rtk_score_pairs_t *pr, const double *pair_sim, const double *rec_score,
+                                          const double *threshold, int alphas, const double *pair_a, const int *pair_index, const int *clip_cg,
+                                          const int *clip_ct, long long *counters, double *sums, int *flags, rtk_stream_t stream) {
+    return ho_launch<true>("score_hota_optimal_sim", B, lg, pr, pair_sim, rec_score, threshold, alphas, pair_a, pair_index, clip_cg, clip_ct, counters,
+                           sums, flags, stream);
 }

@@ -1,8 +1,7 @@
 // track_hota_optimal_body.h -- the LDS layouts, the bodies and the argument checks of HOTA under TrackEval's matching (include/rtk_score.h,
-// "HOTA under the optimal matching"): rtk_score_alignment and rtk_score_hota_optimal (track_hota_optimal.hip) instantiate the bodies on
-// the point IoU of the logged integers, rtk_score_alignment_sim and rtk_score_hota_optimal_sim (track_replay_sim.hip) on the similarity
-// the pair log carries, each kernel behind a __global__ wrapper of its own in the file of its entry point.  The two walks are described
-// in track_hota_optimal.hip.
+// "HOTA under the optimal matching"): track_hota_optimal.hip's kernel templates instantiate the bodies on the point IoU of the logged
+// integers for rtk_score_alignment and rtk_score_hota_optimal, and on the similarity the pair log carries for rtk_score_alignment_sim and
+// rtk_score_hota_optimal_sim.  The two walks are described in track_hota_optimal.hip.
 #pragma once
 #include <math.h>
 

@@ -1,7 +1,7 @@
 // track_identity_pairs_body.h -- the LDS layout, the body and the argument checks of the identity metrics over every pair
-// (include/rtk_score.h, "Identity over every pair"): rtk_score_identity_pairs (track_identity_pairs.hip) instantiates the body on the point
-// IoU of the logged integers, rtk_score_identity_pairs_sim (track_replay_sim.hip) on the similarity the pair log carries, each kernel
-// behind a __global__ wrapper of its own in the file of its entry point.  The walk is described in track_identity_pairs.hip.
+// (include/rtk_score.h, "Identity over every pair"): track_identity_pairs.hip's kernel template instantiates the body on the point IoU of the
+// logged integers for rtk_score_identity_pairs and on the similarity the pair log carries for rtk_score_identity_pairs_sim.  The walk is
+// described in track_identity_pairs.hip.
 #pragma once
 #include "lds_assignment.h"
 #include "score_log_walk.h"

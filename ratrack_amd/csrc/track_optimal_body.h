@@ -1,7 +1,7 @@
 // track_optimal_body.h -- the LDS layout, the body and the argument checks of the replay under a per-frame OPTIMAL matching at a
-// similarity threshold (include/rtk_score.h): rtk_score_replay_optimal (track_optimal.hip) instantiates the body on the point IoU of the
-// logged integers, rtk_score_replay_optimal_sim (track_replay_sim.hip) on the similarity the pair log carries, each kernel behind a
-// __global__ wrapper of its own in the file of its entry point.  The walk is described in track_optimal.hip.
+// similarity threshold (include/rtk_score.h): track_optimal.hip's kernel template instantiates the body on the point IoU of the logged
+// integers for rtk_score_replay_optimal and on the similarity the pair log carries for rtk_score_replay_optimal_sim.  The walk is
+// described in track_optimal.hip.
 #pragma once
 #include <math.h>
 

@@ -6,8 +6,8 @@
 //   rtk_track_score   one workgroup per stream: vod_gt.map_gt_objects (track4d_utils.py:50-102), the 0/1 target of
 //                     loss.affinity_loss against the stream's previous frame, and the running CLEAR-MOT counts with the per-stream
 //                     table of ground-truth tracks; rtk_track_score_logged is the same launch that also appends the frame to the
-//                     stream's log for the confidence sweep (track_sweep.hip); rtk_track_score_memory
-//                     (track_score_memory.hip) is the same body with a record as tall as the table of a tracker that keeps lost tracks
+//                     stream's log for the confidence sweep (track_sweep.hip); rtk_track_score_memory, rtk_track_score_pairs,
+//                     rtk_track_score_pairs_centre and rtk_track_score_pairs_box are further variants of that launch (listed below)
 //
 // Layout of both: 256 threads = 4 waves of 64, one stream's tables in LDS (the byte counts are ts_gto_lds / ts_score_lds below).
 //
@@ -220,48 +220,143 @@ extern "C" int rtk_gt_objects(const rtk_gt_objects_in_t *in, const rtk_gt_object
 // ------------------------------------------------------------------------------------------------
 // rtk_track_score
 // ------------------------------------------------------------------------------------------------
-// The LDS layout and the body of the scoring kernels: track_score_body.h (shared with track_score_memory.hip).
-__global__ __launch_bounds__(TS_THREADS) void track_score_kernel(const rtk_track_score_in_t in, const rtk_track_score_state_t st,
-                                                                 const rtk_track_score_out_t out) {
-    track_score_body<false, false>(in, st, out, rtk_score_log_t{}, rtk_score_memory_t{});
+// The LDS layouts and the one body of the scoring kernels are track_score_body.h's; this is everything around the body: the one kernel
+// template, the LDS figure, the launcher and the six entry points.  The ten instantiations, each one workgroup of 256 threads per
+// stream with the stream's tables in dynamic LDS:
+//   plain, logged             rtk_track_score, rtk_track_score_logged: the same LDS, the log goes straight to memory
+//   memory (with any other)   rtk_track_score_memory, or a memory block given to the pair-logging entry points: a record as tall as the
+//                             table of a tracker that keeps lost tracks (BatchedTracker(max_age=...), rtk_track_memory), so that the 0/1
+//                             target of the tracking loss has a row for every coasted track; Kobj words of LDS more
+//   pairs                     rtk_track_score_pairs: every (detection, kept object) pair with common > 0 also goes to the pair log, the
+//                             input of the per-frame optimal matching (track_optimal.hip); the same LDS
+//   centre                    rtk_track_score_pairs_centre: the pair log under s = max(0, 1 - |c_i - g_j| / zero_distance) in place of the
+//                             point IoU; 24 K + 16 bytes of LDS more
+//   box                       rtk_track_score_pairs_box: the pair log under the IoU of each detection's fitted box (rtk_object_boxes) and
+//                             each kept object's label box read upright, in three dimensions or in the bird's-eye view; 64 K + 16 bytes more
+// Under centre and box a pair is logged iff s > 0, whatever its common count, and the similarity's arguments are staged in LDS once, so
+// that none rides in scalar registers through the body.  Everything but the pair log is bit for bit what the plain launch writes, and
+// the main log is the same in every logging variant.  One writer per word or row, plain stores, no floating-point atomics: the same
+// bits on every run.  A block an instantiation has no switch for is not read by it.
+struct ts_sim_args_t {      // the similarity of the pair log: pair_sim with CENTRE or BOX, the next two with CENTRE, the last four with BOX
+    double *pair_sim;
+    const double *gt_centre;
+    double zero_distance;
+    const double *det_box;
+    const int *det_valid;
+    const double *gt_boxes;
+    int mode;
+};
+
+template <bool LOG, bool MEM, bool PAIRS, bool CENTRE, bool BOX>
+__global__ __launch_bounds__(TS_THREADS) void ts_kernel(const rtk_track_score_in_t in, const rtk_track_score_state_t st,
+                                                        const rtk_track_score_out_t out, const rtk_score_log_t lg, const rtk_score_memory_t mm,
+                                                        const rtk_score_pairs_t pr, const ts_sim_args_t sa) {
+    track_score_body<LOG, MEM, PAIRS, CENTRE, BOX>(in, st, out, lg, mm, pr, sa.pair_sim, sa.gt_centre, sa.zero_distance, sa.det_box, sa.det_valid,
+                                                   sa.gt_boxes, sa.mode);
 }
 
-// the logged variant: the same body (and the same LDS: the log goes straight to memory)
-__global__ __launch_bounds__(TS_THREADS) void ts_logged_kernel(const rtk_track_score_in_t in, const rtk_track_score_state_t st,
-                                                               const rtk_track_score_out_t out, const rtk_score_log_t lg) {
-    track_score_body<true, false>(in, st, out, lg, rtk_score_memory_t{});
+typedef void (*ts_kernel_t)(const rtk_track_score_in_t, const rtk_track_score_state_t, const rtk_track_score_out_t, const rtk_score_log_t,
+                            const rtk_score_memory_t, const rtk_score_pairs_t, const ts_sim_args_t);
+enum ts_variant_t { TS_PLAIN, TS_LOGGED, TS_PAIRS, TS_CENTRE, TS_BOX };
+static const ts_kernel_t ts_kernels[5][2] = {      // [variant][without | with the memory block]: the ten instantiations there are
+    {ts_kernel<false, false, false, false, false>, ts_kernel<false, true, false, false, false>},
+    {ts_kernel<true, false, false, false, false>, ts_kernel<true, true, false, false, false>},
+    {ts_kernel<true, false, true, false, false>, ts_kernel<true, true, true, false, false>},
+    {ts_kernel<true, false, true, true, false>, ts_kernel<true, true, true, true, false>},
+    {ts_kernel<true, false, true, false, true>, ts_kernel<true, true, true, false, true>},
+};
+
+// the dynamic LDS of a variant: the log and the pair log take none
+static size_t ts_lds(int Kobj, int K, int N, bool memory, ts_variant_t variant) {
+    if (variant == TS_CENTRE) return ts_score_centre_lds(Kobj, K, N, memory);
+    if (variant == TS_BOX) return ts_score_box_lds(Kobj, K, N, memory);
+    return memory ? ts_score_memory_lds(Kobj, K, N) : ts_score_lds(Kobj, K, N);
 }
 
-extern "C" int rtk_track_score_lds_bytes(int Kobj, int K, int N) {
+// what the exported functions answer: -1 outside the sizes any variant takes
+static int ts_lds_bytes(int Kobj, int K, int N, bool memory, ts_variant_t variant) {
     if (Kobj < 1 || K < 1 || N < 1 || Kobj > RTK_SCORE_MAX_OBJECTS || K > RTK_SCORE_MAX_BOXES || N > RTK_SCORE_MAX_POINTS) return -1;
-    return (int)ts_score_lds(Kobj, K, N);
+    return (int)ts_lds(Kobj, K, N, memory, variant);
 }
 
-static int ts_score_launch(const rtk_track_score_in_t *in, const rtk_track_score_state_t *st, const rtk_track_score_out_t *out,
-                           const rtk_score_log_t *lg, rtk_stream_t stream) {
-    RTK_REQUIRE(in && st && out, "track_score: null argument block");
-    const size_t lds = ts_score_lds(in->Kobj, in->K, in->N);
+extern "C" int rtk_track_score_lds_bytes(int Kobj, int K, int N) { return ts_lds_bytes(Kobj, K, N, false, TS_PLAIN); }
+extern "C" int rtk_track_score_memory_lds_bytes(int Kobj, int K, int N) { return ts_lds_bytes(Kobj, K, N, true, TS_PLAIN); }
+extern "C" int rtk_track_score_centre_lds_bytes(int Kobj, int K, int N, int memory) { return ts_lds_bytes(Kobj, K, N, memory != 0, TS_CENTRE); }
+extern "C" int rtk_track_score_box_lds_bytes(int Kobj, int K, int N, int memory) { return ts_lds_bytes(Kobj, K, N, memory != 0, TS_BOX); }
+
+#define TS_NEED_LOG 1
+#define TS_NEED_MEMORY 2
+#define TS_NEED_PAIRS 4
+
+// The one scoring launch.  name: the entry point's name in the refusals; launched: its name in the report of a failed launch; need: the
+// blocks it cannot do without (lg, mm and pr may each be NULL otherwise); sim: TS_CENTRE or TS_BOX with the arguments in sa, which the
+// caller has checked, or TS_PLAIN for the point IoU, where the blocks given choose the variant.
+static int ts_launch(const char *name, const char *launched, unsigned need, const rtk_track_score_in_t *in,
+                     const rtk_track_score_state_t *st, const rtk_track_score_out_t *out, const rtk_score_log_t *lg,
+                     const rtk_score_memory_t *mm, const rtk_score_pairs_t *pr, ts_variant_t sim, const ts_sim_args_t &sa, rtk_stream_t stream) {
+    RTK_REQUIRE(in && st && out, "%s: null argument block", name);
+    RTK_REQUIRE(mm || !(need & TS_NEED_MEMORY), "%s: null memory block", name);
+    RTK_REQUIRE(lg || !(need & TS_NEED_LOG), "%s: null log block", name);
+    RTK_REQUIRE(pr || !(need & TS_NEED_PAIRS), "%s: null pair-log block", name);
+    const ts_variant_t variant = sim != TS_PLAIN ? sim : pr ? TS_PAIRS : lg ? TS_LOGGED : TS_PLAIN;
+    const size_t lds = ts_lds(in->Kobj, in->K, in->N, mm != nullptr, variant);
     const int status = ts_score_validate(in, st, out, lg, lds);
     if (status != RTK_OK) return status;
-    if (lg) {
-        (void)hipFuncSetAttribute((const void *)ts_logged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RTK_SCORE_LDS_LIMIT);
-        ts_logged_kernel<<<in->B, TS_THREADS, lds, (hipStream_t)stream>>>(*in, *st, *out, *lg);
-        RTK_CHECK_LAUNCH("track_score_logged");
-        return RTK_OK;
+    if (pr) {
+        RTK_REQUIRE(pr->Q >= 1, "%s: a pair log of Q=%d pairs per stream", name, pr->Q);
+        RTK_REQUIRE(pr->cursor && pr->frame_pair && pr->pair_key && pr->pair_common && pr->rec_size && pr->label_size, "%s: null pair log", name);
     }
-    (void)hipFuncSetAttribute((const void *)track_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RTK_SCORE_LDS_LIMIT);
-    track_score_kernel<<<in->B, TS_THREADS, lds, (hipStream_t)stream>>>(*in, *st, *out);
-    RTK_CHECK_LAUNCH("track_score");
+    if (mm) RTK_REQUIRE(mm->table_ids && mm->table_count && mm->row_track && mm->labelled_coasted, "%s: null table or state", name);
+    const ts_kernel_t kernel = ts_kernels[variant][mm ? 1 : 0];
+    (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RTK_SCORE_LDS_LIMIT);
+    kernel<<<in->B, TS_THREADS, lds, (hipStream_t)stream>>>(*in, *st, *out, lg ? *lg : rtk_score_log_t{}, mm ? *mm : rtk_score_memory_t{},
+                                                           pr ? *pr : rtk_score_pairs_t{}, sa);
+    RTK_CHECK_LAUNCH(launched);
     return RTK_OK;
 }
 
 extern "C" int rtk_track_score(const rtk_track_score_in_t *in, const rtk_track_score_state_t *st, const rtk_track_score_out_t *out,
                                rtk_stream_t stream) {
-    return ts_score_launch(in, st, out, nullptr, stream);
+    return ts_launch("track_score", "track_score", 0, in, st, out, nullptr, nullptr, nullptr, TS_PLAIN, ts_sim_args_t{}, stream);
 }
 
 extern "C" int rtk_track_score_logged(const rtk_track_score_in_t *in, const rtk_track_score_state_t *st, const rtk_track_score_out_t *out,
                                       const rtk_score_log_t *lg, rtk_stream_t stream) {
     RTK_REQUIRE(lg, "track_score_logged: null log block");
-    return ts_score_launch(in, st, out, lg, stream);
+    return ts_launch("track_score", "track_score_logged", 0, in, st, out, lg, nullptr, nullptr, TS_PLAIN, ts_sim_args_t{}, stream);
+}
+
+extern "C" int rtk_track_score_memory(const rtk_track_score_in_t *in, const rtk_track_score_state_t *st, const rtk_track_score_out_t *out,
+                                      const rtk_score_log_t *lg, const rtk_score_memory_t *mm, rtk_stream_t stream) {
+    return ts_launch("track_score_memory", "track_score_memory", TS_NEED_MEMORY, in, st, out, lg, mm, nullptr, TS_PLAIN, ts_sim_args_t{},
+                     stream);
+}
+
+extern "C" int rtk_track_score_pairs(const rtk_track_score_in_t *in, const rtk_track_score_state_t *st, const rtk_track_score_out_t *out,
+                                     const rtk_score_log_t *lg, const rtk_score_memory_t *mm, const rtk_score_pairs_t *pr,
+                                     rtk_stream_t stream) {
+    return ts_launch("track_score_pairs", "track_score_pairs", TS_NEED_LOG | TS_NEED_PAIRS, in, st, out, lg, mm, pr, TS_PLAIN, ts_sim_args_t{},
+                     stream);
+}
+
+extern "C" int rtk_track_score_pairs_centre(const rtk_track_score_in_t *in, const rtk_track_score_state_t *st, const rtk_track_score_out_t *out,
+                                            const rtk_score_log_t *lg, const rtk_score_memory_t *mm, const rtk_score_pairs_t *pr,
+                                            double *pair_sim, const double *gt_centre, double zero_distance, rtk_stream_t stream) {
+    RTK_REQUIRE(pair_sim, "track_score_pairs_centre: null pair_sim (the similarity of every logged pair)");
+    RTK_REQUIRE(gt_centre, "track_score_pairs_centre: null gt_centre (the kept objects' positions)");
+    RTK_REQUIRE(zero_distance > 0.0 && zero_distance < INFINITY, "track_score_pairs_centre: zero_distance=%g must be finite and above 0", zero_distance);
+    return ts_launch("track_score_pairs_centre", "track_score_pairs_centre", TS_NEED_LOG | TS_NEED_PAIRS, in, st, out, lg, mm, pr, TS_CENTRE,
+                     ts_sim_args_t{pair_sim, gt_centre, zero_distance, nullptr, nullptr, nullptr, 0}, stream);
+}
+
+extern "C" int rtk_track_score_pairs_box(const rtk_track_score_in_t *in, const rtk_track_score_state_t *st, const rtk_track_score_out_t *out,
+                                         const rtk_score_log_t *lg, const rtk_score_memory_t *mm, const rtk_score_pairs_t *pr, double *pair_sim,
+                                         const double *det_box, const int *det_valid, const double *gt_boxes, int mode, rtk_stream_t stream) {
+    RTK_REQUIRE(pair_sim, "track_score_pairs_box: null pair_sim (the similarity of every logged pair)");
+    RTK_REQUIRE(det_box && det_valid, "track_score_pairs_box: null det_box or det_valid (the detections' boxes, rtk_object_boxes' output)");
+    RTK_REQUIRE(gt_boxes, "track_score_pairs_box: null gt_boxes (the frame-1 box table)");
+    RTK_REQUIRE(mode == RTK_SCORE_BOX_3D || mode == RTK_SCORE_BOX_BEV, "track_score_pairs_box: mode=%d is neither RTK_SCORE_BOX_3D nor RTK_SCORE_BOX_BEV",
+                mode);
+    return ts_launch("track_score_pairs_box", "track_score_pairs_box", TS_NEED_LOG | TS_NEED_PAIRS, in, st, out, lg, mm, pr, TS_BOX,
+                     ts_sim_args_t{pair_sim, nullptr, 0.0, det_box, det_valid, gt_boxes, mode}, stream);
 }

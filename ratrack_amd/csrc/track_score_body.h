@@ -1,7 +1,6 @@
-// track_score_body.h -- the LDS layout, the body and the argument checks of the scoring kernels: rtk_track_score and
-// rtk_track_score_logged (track_score.hip), rtk_track_score_memory (track_score_memory.hip), rtk_track_score_pairs
-// (track_score_pairs.hip), rtk_track_score_pairs_centre (track_score_centre.hip) and rtk_track_score_pairs_box (track_score_box.hip)
-// instantiate the one body, each kernel behind a __global__ wrapper of its own in the file of its entry point.
+// track_score_body.h -- the LDS layout, the body and the argument checks of the scoring kernels: rtk_track_score,
+// rtk_track_score_logged, rtk_track_score_memory, rtk_track_score_pairs, rtk_track_score_pairs_centre and rtk_track_score_pairs_box
+// launch instantiations of the one body through the one kernel template and the one launcher of track_score.hip.
 #pragma once
 #include <math.h>
 
@@ -159,13 +158,12 @@ __device__ __forceinline__ double ts_box_similarity(double dcx, double dcy, doub
     return s < 1.0 ? s : (s >= 1.0 ? 1.0 : s);      // min(s, 1.0); a NaN stays one
 }
 
-template <bool LOG, bool MEM, bool PAIRS = false, bool CENTRE = false, bool BOX = false>
+template <bool LOG, bool MEM, bool PAIRS, bool CENTRE, bool BOX>
 __device__ __forceinline__ void track_score_body(const rtk_track_score_in_t &in, const rtk_track_score_state_t &st,
                                                  const rtk_track_score_out_t &out, const rtk_score_log_t &lg,
-                                                 const rtk_score_memory_t &mm, const rtk_score_pairs_t &pr = rtk_score_pairs_t{},
-                                                 double *pair_sim = nullptr, const double *gt_centre = nullptr, double zero_distance = 0.0,
-                                                 const double *det_box = nullptr, const int *det_valid = nullptr,
-                                                 const double *gt_boxes = nullptr, int mode = 0) {
+                                                 const rtk_score_memory_t &mm, const rtk_score_pairs_t &pr, double *pair_sim,
+                                                 const double *gt_centre, double zero_distance, const double *det_box, const int *det_valid,
+                                                 const double *gt_boxes, int mode) {
     static_assert(LOG || !PAIRS, "the pair log goes with the main log");
     static_assert(PAIRS || !CENTRE, "the centre similarity is the pair log's");
     static_assert((PAIRS && !CENTRE) || !BOX, "the box similarity is the pair log's, and a log has one similarity");

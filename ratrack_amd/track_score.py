@@ -261,12 +261,16 @@ def check_fit(max_boxes, points, max_objects=None, track_memory=False, centre=Fa
     Kobj = int(max_objects)
     if not 1 <= Kobj <= MAX_OBJECTS:
         raise ValueError("max_objects=%d outside [1, %d]" % (Kobj, MAX_OBJECTS))
+    memory = 1 if track_memory else 0
     if box:
-        need = _lib._fn("rtk_track_score_box_lds_bytes")(Kobj, K, N, 1 if track_memory else 0)
+        name, args = "rtk_track_score_box_lds_bytes", (Kobj, K, N, memory)
     elif centre:
-        need = _lib._fn("rtk_track_score_centre_lds_bytes")(Kobj, K, N, 1 if track_memory else 0)
+        name, args = "rtk_track_score_centre_lds_bytes", (Kobj, K, N, memory)
+    elif track_memory:
+        name, args = "rtk_track_score_memory_lds_bytes", (Kobj, K, N)
     else:
-        need = _lib._fn("rtk_track_score_memory_lds_bytes" if track_memory else "rtk_track_score_lds_bytes")(Kobj, K, N)
+        name, args = "rtk_track_score_lds_bytes", (Kobj, K, N)
+    need = _lib._fn(name)(*args)
     if need < 0 or need > LDS_LIMIT:
         raise ValueError("TrackScorer: max_objects=%d, max_boxes=%d and N=%d need %d bytes of LDS per stream, the limit is %d"
                          % (Kobj, K, N, need, LDS_LIMIT))
@@ -747,33 +751,28 @@ class TrackScorer:
                        self.prev_count.data_ptr(), self.prev_gt.data_ptr(), self.flags.data_ptr())
         o = ScoreOut(pred_gt_slot.data_ptr(), pred_gt_id.data_ptr(), gt_pred.data_ptr(), iou.data_ptr(), aff_target.data_ptr(),
                      aff_defined.data_ptr())
+        lg = self._log_block(object_conf.data_ptr()) if self.logging else None
+        pr = self._pair_block() if self.pairs else None
         mm = None
         if self.track_memory:
             table_ids, table_count = as32(table_ids), as32(table_count)
             mm = ScoreMemory(table_ids.data_ptr(), table_count.data_ptr(), self.row_track.data_ptr(), self.labelled_coasted.data_ptr())
+        lgp, prp, mmp = (None if x is None else ctypes.addressof(x) for x in (lg, pr, mm))
+        # the one launch: the entry point of the scorer's mode and what it takes behind the in, state and out blocks
         if self.box:
-            lg, pr = self._log_block(object_conf.data_ptr()), self._pair_block()
-            _lib.call("rtk_track_score_pairs_box", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), ctypes.addressof(lg),
-                      None if mm is None else ctypes.addressof(mm), ctypes.addressof(pr), self.pair_sim.data_ptr(), det_boxes.data_ptr(),
-                      det_box_valid.data_ptr(), gt_boxes.data_ptr(), BOX_MODES[self.similarity], _stream())
+            name, extra = "rtk_track_score_pairs_box", (lgp, mmp, prp, self.pair_sim.data_ptr(), det_boxes.data_ptr(), det_box_valid.data_ptr(),
+                                                        gt_boxes.data_ptr(), BOX_MODES[self.similarity])
         elif self.centre:
-            lg, pr = self._log_block(object_conf.data_ptr()), self._pair_block()
-            _lib.call("rtk_track_score_pairs_centre", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), ctypes.addressof(lg),
-                      None if mm is None else ctypes.addressof(mm), ctypes.addressof(pr), self.pair_sim.data_ptr(), gt_centre.data_ptr(),
-                      self.zero_distance, _stream())
+            name, extra = "rtk_track_score_pairs_centre", (lgp, mmp, prp, self.pair_sim.data_ptr(), gt_centre.data_ptr(), self.zero_distance)
         elif self.pairs:
-            lg, pr = self._log_block(object_conf.data_ptr()), self._pair_block()
-            _lib.call("rtk_track_score_pairs", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), ctypes.addressof(lg),
-                      None if mm is None else ctypes.addressof(mm), ctypes.addressof(pr), _stream())
+            name, extra = "rtk_track_score_pairs", (lgp, mmp, prp)
         elif self.track_memory:
-            lg = self._log_block(object_conf.data_ptr()) if self.logging else None
-            _lib.call("rtk_track_score_memory", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o),
-                      None if lg is None else ctypes.addressof(lg), ctypes.addressof(mm), _stream())
+            name, extra = "rtk_track_score_memory", (lgp, mmp)
         elif self.logging:
-            lg = self._log_block(object_conf.data_ptr())
-            _lib.call("rtk_track_score_logged", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), ctypes.addressof(lg), _stream())
+            name, extra = "rtk_track_score_logged", (lgp,)
         else:
-            _lib.call("rtk_track_score", ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), _stream())
+            name, extra = "rtk_track_score", ()
+        _lib.call(name, ctypes.addressof(a), ctypes.addressof(s), ctypes.addressof(o), *extra, _stream())
         return MatchResult(pred_gt_slot=pred_gt_slot, pred_gt_id=pred_gt_id, gt_pred=gt_pred, iou=iou, aff_target=aff_target,
                            aff_defined=aff_defined)
 
@@ -917,11 +916,16 @@ class TrackScorer:
         q = torch.empty(count, B, dtype=torch.float64, device=dev)
         tail = (score.data_ptr(), thr.data_ptr(), None if reached is None else reached.data_ptr(), count, min_iou, c.data_ptr(), iq.data_ptr(),
                 q.data_ptr(), None if mask is None else mask.data_ptr(), flags.data_ptr(), st)
-        if self.has_sim:
-            _lib.call("rtk_score_replay_optimal_sim", B, self.T, lgp, prp, self.pair_sim.data_ptr(), *tail)
-        else:
-            _lib.call("rtk_score_replay_optimal", B, self.T, lgp, prp, *tail)
+        self._call_on_pairs("rtk_score_replay_optimal", (B, self.T, lgp, prp), *tail)
         return c, iq, q
+
+    def _call_on_pairs(self, name, head, *tail):
+        """A replay of the pair log: `name(*head, *tail)`, head ending in the pair block -- or, where the log carries its similarity,
+        the `_sim` twin with pair_sim right behind the pair block."""
+        if self.has_sim:
+            _lib.call(name + "_sim", *head, self.pair_sim.data_ptr(), *tail)
+        else:
+            _lib.call(name, *head, *tail)
 
     def _threshold_scores(self, threshold, lgp, flags, st):
         """The prologue of a call that may filter by track score.  threshold None: (None, None), no launch.  A float or a 0-dim
@@ -1005,13 +1009,8 @@ class TrackScorer:
             pair_a = torch.empty(B, self.Q, dtype=torch.float64, device=dev)
             pair_index, clip_cg, clip_ct = (torch.empty(B, self.Q, dtype=torch.int32, device=dev) for _ in range(3))
             tables = (pair_a.data_ptr(), pair_index.data_ptr(), clip_cg.data_ptr(), clip_ct.data_ptr())
-            if self.has_sim:
-                sim = self.pair_sim.data_ptr()
-                _lib.call("rtk_score_alignment_sim", B, self.T, lgp, prp, sim, sp, tp, *tables, flags.data_ptr(), st)
-                _lib.call("rtk_score_hota_optimal_sim", B, lgp, prp, sim, sp, tp, A, *tables, c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
-            else:
-                _lib.call("rtk_score_alignment", B, self.T, lgp, prp, sp, tp, *tables, flags.data_ptr(), st)
-                _lib.call("rtk_score_hota_optimal", B, lgp, prp, sp, tp, A, *tables, c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
+            self._call_on_pairs("rtk_score_alignment", (B, self.T, lgp, prp), sp, tp, *tables, flags.data_ptr(), st)
+            self._call_on_pairs("rtk_score_hota_optimal", (B, lgp, prp), sp, tp, A, *tables, c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
         else:
             _lib.call("rtk_score_hota", B, self.T, lgp, sp, tp, A, c.data_ptr(), q.data_ptr(), flags.data_ptr(), st)
         counters, sums, fl, *tau = _download([c, q, flags.long()] + ([] if thr is None else [thr]))
@@ -1048,11 +1047,8 @@ class TrackScorer:
         sp, tp = None if score is None else score.data_ptr(), None if thr is None else thr.data_ptr()
         if pairs == "all":
             pr = self._pair_block()
-            if self.has_sim:
-                _lib.call("rtk_score_identity_pairs_sim", B, self.T, lgp, ctypes.addressof(pr), self.pair_sim.data_ptr(), sp, tp, levels.data_ptr(), A,
-                          c.data_ptr(), flags.data_ptr(), st)
-            else:
-                _lib.call("rtk_score_identity_pairs", B, self.T, lgp, ctypes.addressof(pr), sp, tp, levels.data_ptr(), A, c.data_ptr(), flags.data_ptr(), st)
+            self._call_on_pairs("rtk_score_identity_pairs", (B, self.T, lgp, ctypes.addressof(pr)), sp, tp, levels.data_ptr(), A, c.data_ptr(),
+                                flags.data_ptr(), st)
         else:
             _lib.call("rtk_score_identity", B, self.T, lgp, sp, tp, levels.data_ptr(), A, c.data_ptr(), flags.data_ptr(), st)
         counters, fl, *tau = _download([c, flags.long()] + ([] if thr is None else [thr]))

@@ -117,13 +117,55 @@ def grad_report(case, grads, prefix=""):
 
 
 # ---- what a kernel file's gfx950 code object states ------------------------------------------------------------------------------
-KernelNotes = collections.namedtuple("KernelNotes", "private lds wavefront max_threads")
+class KernelNotes(collections.namedtuple("KernelNotes", "private lds wavefront max_threads")):
+    """The four fields, and beside them .vgpr (the .vgpr_count): an attribute, so that the tuple compares as it always did."""
+
+    def __new__(cls, private, lds, wavefront, max_threads, vgpr):
+        self = super().__new__(cls, private, lds, wavefront, max_threads)
+        self.vgpr = vgpr
+        return self
+
+
+_NOTES = {}
 
 
 def kernel_notes(src, tmp_path):
     """Compiles `src` for the device with the flags it is built with -> ({kernel symbol: KernelNotes}, the assembly text): the
-    .private_segment_fixed_size (scratch), .group_segment_fixed_size (static LDS), .wavefront_size and .max_flat_workgroup_size of
-    every kernel in the notes of the assembly.  Skips where there is no hipcc."""
+    .private_segment_fixed_size (scratch), .group_segment_fixed_size (static LDS), .wavefront_size, .max_flat_workgroup_size and
+    .vgpr_count of every kernel in the notes of the assembly.  A file is compiled once per test run.  Skips where there is no hipcc."""
+    if src not in _NOTES:
+        _NOTES[src] = _kernel_notes(src, tmp_path)
+    return dict(_NOTES[src][0]), _NOTES[src][1]
+
+
+def template_flags(symbol):
+    """The bool template arguments of a mangled kernel symbol, in order: "_Z9ts_kernelILb1ELb0E...EEv..." -> (True, False, ...)."""
+    return tuple(c == "1" for c in re.findall(r"Lb([01])E", symbol[:symbol.index("EEv") + 1]))
+
+
+# the ten instantiations of csrc/track_score.hip's ts_kernel<LOG, MEM, PAIRS, CENTRE, BOX>, by the name of their variant
+SCORE_VARIANTS = {"plain": (False, False, False, False, False), "memory": (False, True, False, False, False),
+                  "logged": (True, False, False, False, False), "memory_logged": (True, True, False, False, False),
+                  "pairs": (True, False, True, False, False), "pairs_memory": (True, True, True, False, False),
+                  "centre": (True, False, True, True, False), "centre_memory": (True, True, True, True, False),
+                  "box": (True, False, True, False, True), "box_memory": (True, True, True, False, True)}
+
+
+def score_kernel_notes(tmp_path):
+    """The scoring launch's one translation unit -> {variant name of SCORE_VARIANTS: KernelNotes}, after asserting that its code object
+    holds exactly those ten ts_kernel instantiations and gt_objects_kernel, each a workgroup of 256 threads in waves of 64 without
+    scratch and without static LDS."""
+    from ratrack_amd import build as B
+    found, _ = kernel_notes(os.path.join(B.CSRC, "track_score.hip"), tmp_path)
+    ours = [n for n in found if re.match(r"_Z\d+ts_kernelI", n)]
+    assert len(found) == 11 and [n for n in found if n not in ours] == ["_Z17gt_objects_kernel19rtk_gt_objects_in_t20rtk_gt_objects_out_t"], sorted(found)
+    assert all((v.private, v.lds, v.wavefront, v.max_threads) == (0, 0, 64, 256) for v in found.values()), found
+    by_flags = {template_flags(n): found[n] for n in ours}
+    assert sorted(by_flags) == sorted(SCORE_VARIANTS.values()), sorted(by_flags)
+    return {name: by_flags[flags] for name, flags in SCORE_VARIANTS.items()}
+
+
+def _kernel_notes(src, tmp_path):
     from ratrack_amd import build as B
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
@@ -138,7 +180,7 @@ def kernel_notes(src, tmp_path):
     for e in re.split(r"\n\s+- \.", notes):
         m = re.search(r"\.name:\s+(\S+)", e)
         v = [re.search(r"\.%s:\s+(\d+)" % k, e)
-             for k in ("private_segment_fixed_size", "group_segment_fixed_size", "wavefront_size", "max_flat_workgroup_size")]
+             for k in ("private_segment_fixed_size", "group_segment_fixed_size", "wavefront_size", "max_flat_workgroup_size", "vgpr_count")]
         if m and all(v):
             found[m.group(1)] = KernelNotes(*(int(x.group(1)) for x in v))
     return found, asm

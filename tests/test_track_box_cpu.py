@@ -1,5 +1,5 @@
 """CPU: the native surface and the host half of the oriented-box IoU on the pair log (include/rtk_score.h, the last section;
-csrc/track_score_box.hip; ratrack_amd/track_score.py: `TrackScorer(similarity="box")` / `"box_bev"`) -- the host statement of
+csrc/track_score.hip; ratrack_amd/track_score.py: `TrackScorer(similarity="box")` / `"box_bev"`) -- the host statement of
 tests/_track_box_util.py against exact rational arithmetic; the keywords and the host-side refusals; header, abi.py and exports; the
 producer's code object; the replays on a constructed similarity log against their dense twins; and the bound on pair_sim, measured
 again."""
@@ -15,7 +15,7 @@ import pytest
 import _track_box_util as X
 import _track_hota_optimal_util as HO
 import _track_optimal_util as O
-from _util import kernel_notes
+from _util import SCORE_VARIANTS, score_kernel_notes
 from ratrack_amd import _lib, abi, build as B
 from ratrack_amd import track_score as TS
 
@@ -248,20 +248,21 @@ def test_header_declares_binding_mirrors_and_library_exports_the_entry_points():
                  "DEPARTURES FROM\n * TrackEval AFTER THIS", "arccos(R[2][2])"):
         assert word in last, word
     assert "A box IoU is not built here" not in text
-    for name in ("track_score_box.hip", "track_score_body.h"):
+    for name in ("track_score.hip", "track_score_body.h"):
         code = re.sub(r"//[^\n]*", "", open(os.path.join(B.CSRC, name)).read())
         assert "asm" not in code and not re.search(r"atomic\w*\s*\(\s*&?\s*\w*(pair_sim|gpos|sim)\b", code), name
-    # the four existing wrappers instantiate the body as they did: none names the new switch or its arguments
-    for name in ("track_score.hip", "track_score_memory.hip", "track_score_pairs.hip", "track_score_centre.hip"):
-        code = open(os.path.join(B.CSRC, name)).read()
-        assert "det_box" not in code and "gt_boxes" not in code and not re.search(r"track_score_body<[^>]*,[^>]*,[^>]*,[^>]*,", code), name
 
 
 def test_the_producer_builds_as_two_kernels_without_scratch_and_without_static_lds(tmp_path):
-    found, _ = kernel_notes(os.path.join(B.CSRC, "track_score_box.hip"), tmp_path)
-    assert sorted(found) == sorted(n for n in found if "ts_box" in n) and len(found) == 2, found
-    assert any("ts_box_memory_kernel" in n for n in found) and any("ts_box_kernel" in n for n in found)
-    assert all((v.private, v.lds, v.wavefront, v.max_threads) == (0, 0, 64, 256) for v in found.values()), found
+    ts = score_kernel_notes(tmp_path)                # the ten instantiations of the one scoring kernel, each (0, 0, 64, 256), and no other
+    box = [k for k, flags in SCORE_VARIANTS.items() if flags[4]]
+    centre = [k for k, flags in SCORE_VARIANTS.items() if flags[3]]
+    assert box == ["box", "box_memory"] and centre == ["centre", "centre_memory"]       # each without and with the memory block
+    assert all((ts[k].private, ts[k].lds, ts[k].wavefront, ts[k].max_threads) == (0, 0, 64, 256) for k in box), ts
+    # the box code stays in the instantiations with BOX, the centre code in those with CENTRE: every other instantiation of the one
+    # body needs strictly fewer registers than either of them (at most 75 against 143 and 144; at most 44 against 73 and 75)
+    assert max(ts[k].vgpr for k in ts if k not in box) < min(ts[k].vgpr for k in box), ts
+    assert max(ts[k].vgpr for k in ts if k not in box + centre) < min(ts[k].vgpr for k in centre), ts
     # dynamic LDS: the plain figure rounded up to 8 bytes, plus eight float64 per kept object, the mode and one address
     plain, memory, box = (_lib._fn(n) for n in ("rtk_track_score_lds_bytes", "rtk_track_score_memory_lds_bytes", "rtk_track_score_box_lds_bytes"))
     for Kobj, K, N in ((16, 8, 96), (7, 5, 33), (64, 40, 128), (128, 32, 256), (256, 64, 1)):

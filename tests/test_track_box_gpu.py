@@ -1,4 +1,4 @@
-"""GPU: the oriented-box IoU on the pair log (csrc/track_score_box.hip `rtk_track_score_pairs_box`, `TrackScorer(similarity="box")` /
+"""GPU: the oriented-box IoU on the pair log (csrc/track_score.hip `rtk_track_score_pairs_box`, `TrackScorer(similarity="box")` /
 `"box_bev"`) against the host statement of tests/_track_box_util.py.  The producer's integers and decisions exactly and its similarities
 within SIM_BOUND (exact cases: bit for bit); everything but the pair log equal to the "iou" scorer's; the four replays on produced logs
 against the existing host statements with their two similarity functions substituted.  The ground-truth objects are built by hand where

@@ -1,5 +1,5 @@
 """CPU: the native surface and the host half of TrackEval's centre-distance similarity on the pair log (include/rtk_score.h, the last
-section; csrc/track_score_centre.hip, csrc/track_replay_sim.hip; ratrack_amd/track_score.py: `TrackScorer(similarity="centre")`) -- the
+section; csrc/track_score.hip and the three replay files; ratrack_amd/track_score.py: `TrackScorer(similarity="centre")`) -- the
 entry points are declared, mirrored in abi.py, built for gfx950 and exported; the producer builds as exactly two kernels without scratch
 and without static LDS; the similarity replays build without scratch, as one wave of 64 threads, with the static LDS of their plain
 counterparts; the entry points refuse before any launch; `check_similarity` validates the keywords; the host statement of
@@ -15,7 +15,7 @@ import pytest
 import _track_centre_util as C
 import _track_hota_optimal_util as HO
 import _track_optimal_util as O
-from _util import kernel_notes
+from _util import SCORE_VARIANTS, kernel_notes, score_kernel_notes, template_flags
 from ratrack_amd import _lib, abi, build as B
 from ratrack_amd import track_score as TS
 
@@ -51,17 +51,16 @@ def test_header_declares_binding_mirrors_and_library_exports_the_entry_points():
                  "a NaN is not logged", "may now be 0", "DEPARTURES FROM TrackEval AFTER THIS", "point\n * centroids rather than label-box centres",
                  "(1 << 23) + min(floor(s * 65536), 65536)", "ONE similarity"):
         assert word in text, word
-    for name in ("track_score_centre.hip", "track_replay_sim.hip", "track_score_body.h", "track_optimal_body.h", "track_hota_optimal_body.h",
-                 "track_identity_pairs_body.h"):
+    for name in ("track_score.hip", "track_optimal.hip", "track_hota_optimal.hip", "track_identity_pairs.hip", "track_score_body.h",
+                 "track_optimal_body.h", "track_hota_optimal_body.h", "track_identity_pairs_body.h"):
         code = re.sub(r"//[^\n]*", "", open(os.path.join(B.CSRC, name)).read())
         assert "asm" not in code and not re.search(r"atomic\w*\s*\(\s*&?\s*\w*(pair_sim|gpos|pmc|rsum|ksum|quot|miou|cq)\b", code), name
 
 
 def test_the_producer_builds_as_two_kernels_without_scratch_and_without_static_lds(tmp_path):
-    found, _ = kernel_notes(os.path.join(B.CSRC, "track_score_centre.hip"), tmp_path)
-    assert sorted(found) == sorted(n for n in found if "ts_centre" in n) and len(found) == 2, found
-    assert any("ts_centre_memory_kernel" in n for n in found) and any("ts_centre_kernel" in n for n in found)
-    assert all((v.private, v.lds) == (0, 0) for v in found.values()), found
+    ts = score_kernel_notes(tmp_path)                # the ten instantiations of the one scoring kernel, and no other
+    assert [k for k, flags in SCORE_VARIANTS.items() if flags[3]] == ["centre", "centre_memory"]       # CENTRE: without and with the memory block
+    assert all((ts[k].private, ts[k].lds) == (0, 0) for k in ("centre", "centre_memory")), ts
     # dynamic LDS: the plain figure rounded up to 8 bytes, plus the kept objects' positions, zero_distance and one address
     plain, memory, centre = (_lib._fn(n) for n in ("rtk_track_score_lds_bytes", "rtk_track_score_memory_lds_bytes", "rtk_track_score_centre_lds_bytes"))
     for Kobj, K, N in ((16, 8, 96), (7, 5, 33), (64, 40, 128), (128, 32, 256), (256, 64, 1)):
@@ -71,18 +70,17 @@ def test_the_producer_builds_as_two_kernels_without_scratch_and_without_static_l
 
 
 def test_the_similarity_replays_build_without_scratch_as_one_wave_with_their_counterparts_lds(tmp_path):
-    sim, _ = kernel_notes(os.path.join(B.CSRC, "track_replay_sim.hip"), tmp_path)
-    assert len(sim) == 7 and all("_sim_kernel" in n for n in sim), sorted(sim)
-    assert all(v.private == 0 and (v.wavefront, v.max_threads) == (64, 64) and 0 < v.lds <= LIMIT for v in sim.values()), sim
-    plain = {}
+    found = {}
     for name in ("track_optimal.hip", "track_hota_optimal.hip", "track_identity_pairs.hip"):
-        plain.update(kernel_notes(os.path.join(B.CSRC, name), tmp_path)[0])
-    assert len(plain) == 7
-    # a similarity kernel is named after its counterpart (optimal_replay_sim_kernel<1024> for optimal_replay_kernel<1024>, ...)
-    key = lambda n: re.search(r"_Z\d+(\w+?)(?:_sim)?_kernel(?:ILi(\d+)E)?", n).groups()
-    twins = {key(n): v for n, v in plain.items()}
-    assert len(twins) == 7 and sorted(twins) == sorted(key(n) for n in sim)
-    assert all(twins[key(n)].lds == v.lds for n, v in sim.items()), (sim, plain)
+        found.update(kernel_notes(os.path.join(B.CSRC, name), tmp_path)[0])
+    assert len(found) == 14, sorted(found)
+    assert all(v.private == 0 and (v.wavefront, v.max_threads) == (64, 64) and 0 < v.lds <= LIMIT for v in found.values()), found
+    # a similarity kernel is its counterpart's template with the switch on (optimal_replay_kernel<1024, true> for <1024, false>, ...)
+    key = lambda n: re.search(r"_Z\d+(\w+?)_kernelI(?:Li(\d+)E)?Lb[01]EEv", n).groups()
+    sim = {key(n): v for n, v in found.items() if template_flags(n) == (True,)}
+    plain = {key(n): v for n, v in found.items() if template_flags(n) == (False,)}
+    assert len(sim) == 7 and sorted(sim) == sorted(plain)
+    assert all(plain[k].lds == v.lds for k, v in sim.items()), found
 
 
 def test_entry_points_refuse_before_any_launch():

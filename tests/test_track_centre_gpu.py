@@ -1,5 +1,5 @@
-"""GPU: TrackEval's centre-distance similarity on the pair log (csrc/track_score_centre.hip `rtk_track_score_pairs_centre`,
-csrc/track_replay_sim.hip, `TrackScorer(similarity="centre")`) against the host statement of tests/_track_centre_util.py.  The producer's
+"""GPU: TrackEval's centre-distance similarity on the pair log (csrc/track_score.hip `rtk_track_score_pairs_centre`,
+the replays' `_sim` entry points, `TrackScorer(similarity="centre")`) against the host statement of tests/_track_centre_util.py.  The producer's
 integers, decisions and -- bit for bit -- similarities; everything but the pair log equal to the "iou" scorer's; the four replays on
 constructed and on produced logs against the existing host statements with their two similarity functions substituted.  The ground-truth
 objects are built by hand where that is simpler (`GtObjects` is a plain holder of tensors)."""

@@ -17,7 +17,7 @@ import _track_hota_util as H
 import _track_identity_util as I
 import _track_optimal_util as O
 import _track_sweep_util as W
-from _util import kernel_notes
+from _util import kernel_notes, template_flags
 from ratrack_amd import _lib, abi, build as B
 from ratrack_amd import track_score as TS
 
@@ -61,22 +61,25 @@ def test_header_declares_and_library_exports_the_new_entry_points():
 
 def test_the_new_kernels_build_for_gfx950_without_scratch_and_within_the_lds_limit(tmp_path):
     found, _ = kernel_notes(os.path.join(B.CSRC, "track_hota_optimal.hip"), tmp_path)
-    assert len(found) == 3 and all(v.private == 0 and 0 < v.lds <= LIMIT and (v.wavefront, v.max_threads) == (64, 64) for v in found.values()), found
+    # every kernel twice: on the point IoU and with the similarity switch on
+    assert len(found) == 6 and all(v.private == 0 and 0 < v.lds <= LIMIT and (v.wavefront, v.max_threads) == (64, 64) for v in found.values()), found
+    assert sorted(template_flags(name) for name in found) == [(False,)] * 3 + [(True,)] * 3, sorted(found)
     lds = _lib._fn("rtk_score_alignment_lds_bytes")
     small = [v.lds for name, v in found.items() if "alignment_kernelILi1024E" in name]
     large = [v.lds for name, v in found.items() if "alignment_kernel" in name and "ILi1024E" not in name]
-    assert small == [lds(1024)] and lds(1) == lds(1024) and large == [lds(1025)] and lds(1024) < lds(1025) <= LIMIT
+    assert small == [lds(1024)] * 2 and lds(1) == lds(1024) and large == [lds(1025)] * 2 and lds(1024) < lds(1025) <= LIMIT
     assert lds(1404) == lds(1025) and lds(1405) > LIMIT and lds(0) == -1
     # the figures, from their parts (ints): r, k, a chunk's q, pmc as float64 | chunk key, index | pair list key, n | pair lookup | track
     # table key, ct | label table key, cg | rslot | glabel, entry | scalars
     assert lds(1024) == 4 * (2 * (256 + 64 + 64 + 1024) + 2 * 64 + 2 * 1024 + 2048 + 2 * 3072 + 2 * 1024 + 256 + 2 * 64 + 8) == 62496
     la_words = (256 + 1) + 2 * 2048 + 256 + 5 * 64
     match = [v.lds for name, v in found.items() if "hota_optimal_kernel" in name]
-    assert match == [4 * (2 * (64 + 3 * 64) + 2 * 2048 + la_words + 1024 + 256 + 2 * 64 + 64 + 8)] == [44068]
+    assert match == [4 * (2 * (64 + 3 * 64) + 2 * 2048 + la_words + 1024 + 256 + 2 * 64 + 64 + 8)] * 2 == [44068] * 2
     found, _ = kernel_notes(os.path.join(B.CSRC, "track_identity_pairs.hip"), tmp_path)
-    assert len(found) == 2 and all("identity_pairs_kernel" in name and v.private == 0 and v.lds <= LIMIT for name, v in found.items()), found
+    assert len(found) == 4 and all("identity_pairs_kernel" in name and v.private == 0 and v.lds <= LIMIT for name, v in found.items()), found
+    assert sorted(template_flags(name) for name in found) == [(False,)] * 2 + [(True,)] * 2, sorted(found)
     ilds, plds = _lib._fn("rtk_score_identity_lds_bytes"), _lib._fn("rtk_score_identity_pairs_lds_bytes")
-    assert sorted(v.lds for v in found.values()) == [plds(1024), plds(1025)] and all(plds(T) == ilds(T) for T in (0, 1, 1024, 1025, 3583, 3584, 100000))
+    assert sorted(v.lds for v in found.values()) == [plds(1024)] * 2 + [plds(1025)] * 2 and all(plds(T) == ilds(T) for T in (0, 1, 1024, 1025, 3583, 3584, 100000))
 
 
 def test_entry_points_refuse_before_any_launch():

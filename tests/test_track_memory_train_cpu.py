@@ -1,17 +1,16 @@
-"""CPU: training the re-acquisition -- rtk_track_score_memory (csrc/track_score_memory.hip), TrackScorer(track_memory=True) and
+"""CPU: training the re-acquisition -- rtk_track_score_memory (csrc/track_score.hip), TrackScorer(track_memory=True) and
 SequenceTrainer(reacquire=...): declared, exported, built without scratch; the host statement of the record on hand-written cases;
 arguments refused before any device is touched."""
 import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 import torch
 
 import _track_memory_train_util as M
+from _util import SCORE_VARIANTS, score_kernel_notes
 from ratrack_amd import _lib, abi, build as B, track_score as TS, track_train as TT, tracker as T
 from ratrack_amd.track4d import Args, Track4D
 
@@ -46,25 +45,10 @@ def test_header_declares_and_library_exports_the_entry_point():
 
 
 def test_memory_kernels_build_for_gfx950_without_scratch(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(B.CSRC, "track_score_memory.hip")
-    out = str(tmp_path / "track_score_memory.s")
-    cmd = [hipcc] + [f for f in B.flags_for(src) if f != "-fPIC"] + ["-I", os.path.join(ROOT, "include"), "-I", B.CSRC, "-S",
-                                                                    "--cuda-device-only", "-o", out, src]
-    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    notes = asm[asm.index("amdhsa.kernels"):]
-    found = {}
-    for e in re.split(r"\n\s+- \.", notes):
-        m = re.search(r"\.name:\s+(\S+)", e)
-        p = re.search(r"\.private_segment_fixed_size:\s+(\d+)", e)
-        if m and p:
-            found[m.group(1)] = int(p.group(1))
-    assert len(found) == 2, found                    # one __global__ wrapper per variant: without and with the log
-    for k in ("ts_memory_kernel", "ts_memory_logged_kernel"):
-        assert [v for name, v in found.items() if k in name] == [0], (k, found)
+    ts = score_kernel_notes(tmp_path)                # the ten instantiations of the one scoring kernel, and no other
+    for k in ("memory", "memory_logged"):            # one instantiation per variant: without and with the log
+        assert SCORE_VARIANTS[k][1] and not any(SCORE_VARIANTS[k][2:]), k
+        assert (ts[k].private, ts[k].lds, ts[k].wavefront, ts[k].max_threads) == (0, 0, 64, 256), (k, ts[k])
 
 
 # ---- 2. the host statement on hand-written cases ----------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""GPU: training the re-acquisition -- rtk_track_score_memory (csrc/track_score_memory.hip), TrackScorer(track_memory=True) behind
+"""GPU: training the re-acquisition -- rtk_track_score_memory (csrc/track_score.hip), TrackScorer(track_memory=True) behind
 BatchedTracker(max_age=...) and SequenceTrainer(reacquire=...).
 
 Every comparison is exact (== on integers, bit views on floats) except the gradient test, whose bound is the project's own

@@ -1,5 +1,5 @@
 """CPU: the native surface and the host half of the per-frame optimal matching at an IoU threshold (include/rtk_score.h,
-csrc/track_score_pairs.hip, csrc/track_optimal.hip, ratrack_amd/track_score.py: `TrackScorer(sweep_pairs=...)`,
+csrc/track_score.hip, csrc/track_optimal.hip, ratrack_amd/track_score.py: `TrackScorer(sweep_pairs=...)`,
 `sweep(matching="optimal")`, `clear_optimal`) -- the entry points and their constants are declared, built for gfx950 without scratch
 and exported; the LDS the code object states is the figure the host function reports; the two host forms of
 tests/_track_optimal_util.py agree with each other; the constructed frames have their known answers (greedy 1, optimal 2); the keywords are
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import _track_optimal_util as O
-from _util import kernel_notes
+from _util import SCORE_VARIANTS, kernel_notes, score_kernel_notes, template_flags
 from ratrack_amd import _lib, abi, build as B
 from ratrack_amd import track_score as TS
 
@@ -40,19 +40,20 @@ def test_header_declares_and_library_exports_the_pair_log_and_the_optimal_replay
     for word in ("ONE ASSIGNMENT", "THE CALLER CHOOSES", "still NOT a reproduction", "(1 << 23) + min(floor(iou * 65536), 65536)",
                  "tp * 2^23 + iou_q", "seen but unmatched in its previous seen frame", "logged whole or not at\n * all"):
         assert word in text, word
-    for name in ("track_optimal.hip", "score_log_walk.h", "track_score_pairs.hip"):
+    for name in ("track_optimal.hip", "score_log_walk.h", "track_score.hip"):
         assert "asm" not in re.sub(r"//[^\n]*", "", open(os.path.join(B.CSRC, name)).read()), name
 
 
 def test_optimal_replay_builds_for_gfx950_without_scratch_and_states_its_lds(tmp_path):
     found, _ = kernel_notes(os.path.join(B.CSRC, "track_optimal.hip"), tmp_path)
-    # one instance per track-table capacity: no scratch, and the static LDS is the figure the host function reports
-    assert len(found) == 2 and all("optimal_replay_kernel" in name and v.private == 0 for name, v in found.items()), found
+    # one instance per track-table capacity and similarity switch: no scratch, and the static LDS is the figure the host function reports
+    assert len(found) == 4 and all("optimal_replay_kernel" in name and v.private == 0 for name, v in found.items()), found
+    assert sorted(template_flags(name) for name in found) == [(False,), (False,), (True,), (True,)], sorted(found)
     lds = _lib._fn("rtk_score_optimal_lds_bytes")
     small = [v.lds for name, v in found.items() if "optimal_replay_kernelILi1024E" in name]
-    assert small == [lds(1024)] and lds(1024) <= 65536 and lds(1) == lds(1024), (found, lds(1024))
+    assert small == [lds(1024)] * 2 and lds(1024) <= 65536 and lds(1) == lds(1024), (found, lds(1024))
     large = [v.lds for name, v in found.items() if "optimal_replay_kernelILi1024E" not in name]
-    assert large == [lds(1025)] and lds(1024) < lds(1025) <= 65536
+    assert large == [lds(1025)] * 2 and lds(1024) < lds(1025) <= 65536
     assert lds(100000) > 65536 and lds(0) == -1
     # the figure, from its parts (ints): IoUs of the matches | edge list | solver tables at 256 x 64 x 2048 | track table 5 T | frame rows | scalars
     la_words = (256 + 1) + 2 * 2048 + 256 + 5 * 64
@@ -60,9 +61,10 @@ def test_optimal_replay_builds_for_gfx950_without_scratch_and_states_its_lds(tmp
 
 
 def test_pair_logging_kernels_build_without_scratch_and_with_no_static_lds(tmp_path):
-    found, _ = kernel_notes(os.path.join(B.CSRC, "track_score_pairs.hip"), tmp_path)
-    assert sorted(n for n in found) == sorted(n for n in found if "ts_pairs" in n) and len(found) == 2, found
-    assert all((v.private, v.lds) == (0, 0) for v in found.values()), found          # dynamic LDS only: rtk_track_score_lds_bytes / _memory_lds_bytes
+    ts = score_kernel_notes(tmp_path)                # the ten instantiations of the one scoring kernel, and no other
+    for k in ("pairs", "pairs_memory"):              # PAIRS with LOG, on the point IoU: without and with the memory block
+        assert SCORE_VARIANTS[k][0] and SCORE_VARIANTS[k][2] and not any(SCORE_VARIANTS[k][3:]), k
+        assert (ts[k].private, ts[k].lds) == (0, 0), (k, ts[k])          # dynamic LDS only: rtk_track_score_lds_bytes / _memory_lds_bytes
 
 
 def test_entry_points_refuse_before_any_launch():

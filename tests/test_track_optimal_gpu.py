@@ -1,4 +1,4 @@
-"""GPU: the pair log (csrc/track_score_pairs.hip `rtk_track_score_pairs`, `TrackScorer(sweep_pairs=...)`) and the replay under the
+"""GPU: the pair log (csrc/track_score.hip `rtk_track_score_pairs`, `TrackScorer(sweep_pairs=...)`) and the replay under the
 per-frame optimal matching (csrc/track_optimal.hip `rtk_score_replay_optimal`, `TrackScorer.sweep(matching="optimal")`,
 `clear_optimal`) against the host statement of tests/_track_optimal_util.py.  The device delivers integers and fixed-order float64
 sums, so everything is compared with == / bit for bit."""

@@ -5,14 +5,13 @@ tests/test_track_score_gpu.py meets its input conditions and holds every situati
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import _gt_util as U
 import _track_score_util as S
+from _util import kernel_notes, score_kernel_notes
 from ratrack_amd import build as B
 from ratrack_amd import gt_device as G
 from ratrack_amd import track_score as TS
@@ -40,24 +39,11 @@ def test_header_declares_and_library_exports_the_entry_points():
 
 
 def test_kernels_build_for_gfx950_without_scratch(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(B.CSRC, "track_score.hip")
-    out = str(tmp_path / "track_score.s")
-    cmd = [hipcc] + [f for f in B.flags_for(src) if f != "-fPIC"] + ["-I", os.path.join(ROOT, "include"), "-I", B.CSRC, "-S",
-                                                                    "--cuda-device-only", "-o", out, src]
-    subprocess.check_call(cmd, stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    notes = asm[asm.index("amdhsa.kernels"):]
-    found = {}
-    for e in re.split(r"\n\s+- \.", notes):
-        m = re.search(r"\.name:\s+(\S+)", e)
-        p = re.search(r"\.private_segment_fixed_size:\s+(\d+)", e)
-        if m and p:
-            found[m.group(1)] = int(p.group(1))
-    for k in ("gt_objects_kernel", "track_score_kernel"):
-        assert [v for name, v in found.items() if k in name] == [0], (k, found)
+    found, _ = kernel_notes(os.path.join(B.CSRC, "track_score.hip"), tmp_path)
+    assert [v.private for name, v in found.items() if "gt_objects_kernel" in name] == [0], found
+    # the scoring launch: gt_objects_kernel aside, the file holds exactly the ten instantiations of the one kernel template
+    ts = score_kernel_notes(tmp_path)
+    assert (ts["plain"].private, ts["plain"].lds, ts["plain"].wavefront, ts["plain"].max_threads) == (0, 0, 64, 256), ts["plain"]
 
 
 def test_pack_box_types_follows_pack_boxes_slot_order_on_the_shipped_frames():

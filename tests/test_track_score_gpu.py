@@ -339,3 +339,109 @@ def test_affinity_target_gives_the_host_tracking_loss(tracked):
             assert torch.equal(ours, theirs), (f, b, float(ours), float(theirs))
     print("tracking loss compared on %d stream-frames" % defined)
     assert defined > 0
+
+
+# ---- 8: the ten variants of the one scoring launch -------------------------------------------------------------------------------------
+STATE = ("counters", "iou_sum", "table_key", "table_last", "table_seen", "table_matched", "table_used", "prev_gt_id", "prev_count", "prev_gt",
+         "flags")
+LOG = ("log_cursor", "log_frame", "log_label", "log_track", "log_best", "log_conf", "log_iou")
+
+
+def _tail_frames():
+    """Three frames of B = 2 streams at sizes that are no multiple of anything: N = 33 columns with n_valid = (33, 20), Kobj = 7
+    detection slots, K = 5 box slots.  Four 2 m cars per stream, their points (multiples of 1/64) shuffled among clutter; detections:
+    one exact, one with a point exchanged for clutter, one split in two, one that appears from the second frame on, one of clutter
+    alone; a track id that changes; a reset of stream 0 on the second frame; stream 1 inactive in the third."""
+    B, N, Kobj, K, q = 2, 33, 7, 5, 1.0 / 64
+    rng = np.random.default_rng(20250921)
+    sizes, n_valid = ((5, 4, 4, 3), (4, 4, 3, 2)), (33, 20)
+    local = [[rng.integers(-40, 41, (k, 3)).astype(np.float64) * q for k in sizes[b]] for b in range(B)]
+    clutter = [(rng.integers(-64, 65, (N, 3)) + np.array([-3000, 0, 0])).astype(np.float64) * q for b in range(B)]
+    frames = []
+    for f in range(3):
+        pc1 = np.zeros((B, 3, N), dtype=np.float32)
+        obj, num, ids = np.full((B, N), -1, dtype=np.int32), np.zeros(B, dtype=np.int32), np.full((B, Kobj), -1, dtype=np.int32)
+        det_box, det_valid, per_stream = np.zeros((B, Kobj, 8)), np.zeros((B, Kobj), dtype=np.int32), []
+        for b in range(B):
+            centres = [np.array([6.0 * j + 0.25 * f, 2.0 * b, 0.0]) for j in range(4)]
+            labels = {20 + j: vod_gt.Label("Car", 20 + j, 0, 0, 0, 0, 0, 0, 2.0, 2.0, 2.0, *(float(v) for v in c), -(0.2 * j + np.pi / 2))
+                      for j, c in enumerate(centres)}
+            per_stream.append((labels, U.IDENTITY_TF, labels, U.IDENTITY_TF))
+            pts = np.concatenate([c + l for c, l in zip(centres, local[b])] + [clutter[b]])[:n_valid[b]]
+            perm = rng.permutation(len(pts))
+            where = np.empty(len(pts), dtype=np.int64)
+            where[perm] = np.arange(len(pts))
+            pc1[b, :, :len(pts)] = pts[perm].T.astype(np.float32)
+            pc1[b, :, len(pts):] = pc1[b, :, :1]
+            start = np.cumsum((0,) + sizes[b])
+            own = [[int(where[i]) for i in range(start[j], start[j + 1])] for j in range(4)]
+            spare = [int(where[i]) for i in range(start[4], len(pts))]
+            preds = [(30 + 100 * (f == 1 and b == 1), own[0]), (31, own[1][:-1] + spare[:1]), (32, own[2][:1]), (532, own[2][1:])]
+            if f > 0:
+                preds.append((33, own[3]))
+            preds.append((900 + f, spare[1:4]))
+            if f == 1:
+                preds.reverse()
+            for i, (tid, cols) in enumerate(preds):
+                obj[b, cols], ids[b, i] = i, tid
+                c = pc1[b][:, cols].astype(np.float64).mean(axis=1)
+                det_box[b, i], det_valid[b, i] = (c[0], c[1], c[2], 2.0, 1.5, 2.0, 0.1 * i, 0.0), 3
+            num[b] = len(preds)
+        frames.append(dict(per_stream=per_stream, pc1=pc1, obj=obj, num=num, ids=ids, det_box=det_box, det_valid=det_valid,
+                           conf=rng.random((B, Kobj)).astype(np.float32), n_valid=np.array(n_valid, dtype=np.int32),
+                           reset=np.array([f == 1, 0], dtype=np.uint8), active=np.array([1, f != 2], dtype=np.uint8)))
+    return frames, B, N, Kobj, K
+
+
+def _bytes(t):
+    return t.cpu().numpy().tobytes()
+
+
+def test_all_ten_variants_of_the_scoring_launch_agree_outside_the_pair_log():
+    """The same frames through the ten instantiations the one launcher chooses among: whatever a variant adds, everything but the pair
+    log is the plain launch's bit for bit, and the main log is the same in the eight variants that keep one.  The memory variants get
+    the detections themselves as the table (table_ids = object_ids, table_count = num_objects), so nothing coasts."""
+    frames, B, N, Kobj, K = _tail_frames()
+    log, pairs = dict(sweep_frames=4, sweep_records=32), dict(sweep_frames=4, sweep_records=32, sweep_pairs=64)
+    variants = dict(plain={}, logged=log, pairs=pairs, centre=dict(pairs, similarity="centre"), box=dict(pairs, similarity="box"))
+    variants.update({k + "_memory": dict(v, track_memory=True) for k, v in list(variants.items())})
+    variants["box_memory"]["similarity"] = "box_bev"                    # (the same instantiation: the mode is an argument)
+    assert len(variants) == 10
+    scorers = {k: TS.TrackScorer(streams=B, max_objects=Kobj, max_boxes=K, max_gt_tracks=8, **kw) for k, kw in variants.items()}
+    matches = {k: [] for k in variants}
+    for fr in frames:
+        pc1, nv = _dev(fr["pc1"]), _dev(fr["n_valid"])
+        gobj = TS.gt_objects(pc1, G.pack_boxes(fr["per_stream"], K, DEV), TS.pack_box_types(fr["per_stream"], K, DEV), n_valid=nv,
+                             min_obj_points=S.MIN_PTS)
+        args = [_dev(fr[k]) for k in ("obj", "num", "ids")]
+        kw = dict(reset=_dev(fr["reset"]), active=_dev(fr["active"]), object_conf=_dev(fr["conf"]), table_ids=args[2], table_count=args[1],
+                  det_boxes=_dev(fr["det_box"]), det_box_valid=_dev(fr["det_valid"]))
+        for k, s in scorers.items():
+            matches[k].append(s.update_raw(pc1, *args, gobj, nv, **kw))
+    plain = scorers["plain"]
+    res = plain.result()["overall"]
+    assert not plain.flags.any() and res["frames"] == 5 and res["tp"] > 0 and res["fp"] > 0 and res["fn"] > 0 and res["idsw"] > 0, res
+    assert sum(int(m.aff_defined.sum()) for m in matches["plain"]) > 0 and int(matches["plain"][2].pred_gt_id[1].max()) == -1
+    for k, s in scorers.items():
+        for f, (m, m0) in enumerate(zip(matches[k], matches["plain"])):
+            for name in MATCH:
+                assert _bytes(getattr(m, name)) == _bytes(getattr(m0, name)), (k, f, name)
+        for name in STATE:
+            assert _bytes(getattr(s, name)) == _bytes(getattr(plain, name)), (k, name)
+        # each scorer really ran its own variant: the record of the table, the logs, the similarity
+        assert s.track_memory == k.endswith("_memory") and s.logging == (not k.startswith("plain"))
+        if s.track_memory:
+            assert s.row_track[0].tolist() == frames[2]["ids"][0].tolist() and s.row_track[1].tolist() == frames[1]["ids"][1].tolist(), k
+            assert not s.labelled_coasted.any(), k
+        if s.logging:
+            for name in LOG:
+                assert _bytes(getattr(s, name)) == _bytes(getattr(scorers["logged"], name)), (k, name)
+            assert s.log_cursor[:, 0].tolist() == [3, 2] and s.log_cursor[:, 1].tolist() == [int(sum(fr["num"][0] for fr in frames)),
+                                                                                            int(sum(fr["num"][1] for fr in frames[:2]))], k
+        if s.pairs:
+            assert s.pair_cursor.min() > 0 and s.pair_frame[0, :3, 1].sum() == s.pair_cursor[0], k
+            assert (s.pair_sim[:, 0] > 0).all() if s.has_sim else not hasattr(s, "pair_sim"), k
+    # the pair logs differ where they should: the point IoU, the centre distance and the two box IoUs are four different similarities
+    assert _bytes(scorers["centre"].pair_sim) != _bytes(scorers["box"].pair_sim) != _bytes(scorers["box_memory"].pair_sim)
+    assert _bytes(scorers["centre"].pair_sim) == _bytes(scorers["centre_memory"].pair_sim)
+    assert _bytes(scorers["pairs"].pair_key) == _bytes(scorers["pairs_memory"].pair_key)

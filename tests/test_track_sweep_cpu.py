@@ -11,7 +11,7 @@ import pytest
 
 import _track_score_util as S
 import _track_sweep_util as W
-from _util import kernel_notes
+from _util import SCORE_VARIANTS, kernel_notes, score_kernel_notes
 from ratrack_amd import _lib, abi, build as B
 from ratrack_amd import track_score as TS
 
@@ -44,11 +44,10 @@ def test_sweep_kernels_and_the_logged_wrapper_build_for_gfx950_without_scratch(t
     for k in ("sweep_means_kernel", "sweep_thresholds_kernel", "sweep_replay_kernel"):
         assert [v for name, v in found.items() if k in name] == [0], (k, found)
     assert len(found) == 3, found
-    found = {k: v.private for k, v in kernel_notes(os.path.join(B.CSRC, "track_score.hip"), tmp_path)[0].items()}
-    logged = [name for name in found if "ts_logged_kernel" in name]
-    assert len(logged) == 1 and found[logged[0]] == 0, found
-    assert "track_score_kernel" not in logged[0] and "gt_objects_kernel" not in logged[0]
-    assert len(found) == 3, found                     # gt_objects_kernel, track_score_kernel and the logged wrapper: no template instances
+    # the logged variant is an instantiation of its own among the ten of the one scoring kernel (and gt_objects_kernel: nothing else)
+    ts = score_kernel_notes(tmp_path)
+    assert SCORE_VARIANTS["logged"] == (True, False, False, False, False) != SCORE_VARIANTS["plain"]
+    assert (ts["logged"].private, ts["logged"].lds, ts["logged"].wavefront, ts["logged"].max_threads) == (0, 0, 64, 256), ts["logged"]
 
 
 # ---- sweep_values ------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """The pair log under the oriented-box IoU (ratrack_amd/track_score.py `TrackScorer(similarity="box")` / `"box_bev"`;
-csrc/track_score_box.hip): what the box launch costs per frame against `rtk_track_score_pairs_centre` and `rtk_track_score_pairs`, and
+csrc/track_score.hip): what the box launch costs per frame against `rtk_track_score_pairs_centre` and `rtk_track_score_pairs`, and
 how many pairs each similarity logs.
 
     python tools/time_track_box.py [--streams 64] [--points 256] [--boxes 32] [--max-objects 128] [--iters 200] [--warmup 5] [--rounds 3]

@@ -1,5 +1,5 @@
 """The pair log under TrackEval's centre-distance similarity (ratrack_amd/track_score.py `TrackScorer(similarity="centre")`;
-csrc/track_score_centre.hip, csrc/track_replay_sim.hip): what the centre launch costs per frame against `rtk_track_score_pairs`, what the
+csrc/track_score.hip and the replays' files): what the centre launch costs per frame against `rtk_track_score_pairs`, what the
 four replays cost on a centre log against an IoU log of the same frames, and how many pairs each similarity logs.
 
     python tools/time_track_centre.py [--streams 64] [--points 256] [--boxes 32] [--max-objects 128] [--iters 200] [--replay-iters 50]

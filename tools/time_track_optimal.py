@@ -1,5 +1,5 @@
 """The pair log and the replay under the per-frame optimal matching (ratrack_amd/track_score.py `TrackScorer(sweep_pairs=...)`,
-`sweep(matching="optimal")`; csrc/track_score_pairs.hip, csrc/track_optimal.hip): what logging the pairs costs per frame, and what the
+`sweep(matching="optimal")`; csrc/track_score.hip, csrc/track_optimal.hip): what logging the pairs costs per frame, and what the
 optimal replay costs against the greedy one.
 
     python tools/time_track_optimal.py [--streams 64] [--points 256] [--boxes 32] [--max-objects 128] [--iters 50] [--warmup 5]
