@@ -747,6 +747,42 @@ RTK_EXPORT int rtk_result_log_filter_boxes(int B, const rtk_result_log_t *log, c
                                            const rtk_box_filter_t *par, double *out_box, int *out_valid, double *vel, double *state,
                                            double *aligned, int *link, int *flags, rtk_stream_t stream);
 
+/* ---- Filtered boxes inside the step (csrc/track_box_step.hip, csrc/box_filter.h, ratrack_amd/boxes.py) ------------------------------------
+ * The filter above, a frame at a time: the state of every track travels with the tracker's table, one launch per step after the
+ * association and the box fit advances it IN PLACE and hands out, for every row of the table, the track's box and velocity now.
+ * smooth and size_rule must be 0 (neither is causal); with them 0 a measured row gets the bits rtk_result_log_filter_boxes gives the
+ * record the step would log, when every stream's frame index advances by one per active step.
+ *   state (B,K,16) float64   a row has the layout of the offline launch's state: mean (x, y, z, yaw, l, w, h, vx, vy, vz), P00, P01, P11,
+ *                            Pyaw, Psize, 0.
+ *   since (B,K) int32        -1: the row has no filter; 0: the filter took a measurement this frame; s > 0: frames since its last one.
+ * THE RULE, per stream b.  All arithmetic is box_filter.h's, called in the order given: float64, every operation rounded on its own.
+ *   counts      count_prev, count_new and num_objects (n_b) are clamped to [0, K].
+ *   inactive    (active[b] == 0) state and since keep every bit; all K output rows are empty: zeros, out_valid 0, gap -1.
+ *   reset       (reset[b] and active[b]) the previous table is ignored: no row below has a previous row.
+ *   previous    the previous row of new-table row r < count_new is the smallest i < count_prev with ids_prev[i] == ids_new[r]; an
+ *               id < 0 matches nothing.  Ids are unique within a table, so this is a lookup; nothing of rtk_track_memory is needed.
+ *   measured    r < min(n_b, count_new) and valid[b][r] > 0.  The reading is z = (box[0], box[1], box[2], box[6], box[3], box[4], box[5]).
+ *               It CONTINUES if it has a previous row with since_prev >= 0 and k = since_prev + 1 <= max_gap: that state is loaded,
+ *               predict k times, align, update; gap = k.  Otherwise it STARTS: start, the aligned reading is the measurement as it is,
+ *               gap = -1.  Either way since = 0, out_valid = valid[b][r], aligned = (yaw_z', l', w', h').
+ *   carried     r < count_new, not measured, a previous row with since_prev >= 0 (a coasted survivor; a detection without a valid
+ *               box): the state is copied bit for bit, since = min(since_prev + 1, RTK_BOX_FILTER_MAX_GAP) (saturated, such a row can
+ *               only start again), out_valid = 0, gap = -1, aligned = zeros.
+ *   no filter   every other row below count_new and every row at or past it: state zeros, since = -1, the outputs empty.
+ *   outputs     for a row with since >= 0, (out_box, vel) = output of a COPY of the state's mean after `since` position predictions
+ *               (m_c = m_c + v_c, since times): a measured row's filtered box, a carried row's predicted one.  The stored state is never
+ *               predicted eagerly, so the bits of a later update are those of the offline chain.
+ * par outside the ranges above, smooth != 0, size_rule != 0 or K > RTK_RESULT_MAX_OBJECTS refuses the call.  active and reset may be NULL
+ * (all active, none reset).  box (B,K,8) and valid (B,K) are rtk_object_boxes' outputs, or boxes from anywhere; the outputs must not
+ * alias them.  out_box (B,K,8), out_valid (B,K), vel (B,K,4), aligned (B,K,4), gap (B,K): all K rows of every stream are written.
+ * One workgroup of 256 lanes per stream, a lane per row; a lane reads its previous row's 16 words before a barrier and stores after
+ * it.  No allocation, no synchronisation, one writer per word and plain stores: the same bits on every run, and the launch can be
+ * captured.  Static LDS: 1 KiB. */
+RTK_EXPORT int rtk_track_box_filter_step(int B, int K, const unsigned char *active, const unsigned char *reset, const int *ids_prev,
+                                         const int *count_prev, const int *ids_new, const int *count_new, const int *num_objects,
+                                         const double *box, const int *valid, const rtk_box_filter_t *par, double *state, int *since,
+                                         double *out_box, int *out_valid, double *vel, double *aligned, int *gap, rtk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

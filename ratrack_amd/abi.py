@@ -231,6 +231,7 @@ SIGNATURES = {
     "rtk_result_log_boxes": [_i, _p, _p, _d] + [_p] * 4 + [_p],
     "rtk_object_boxes": [_i] * 3 + [_p] * 4 + [_d] + [_p] * 4 + [_p],
     "rtk_result_log_filter_boxes": [_i] + [_p] * 12 + [_p],
+    "rtk_track_box_filter_step": [_i] * 2 + [_p] * 17 + [_p],
     # ---- include/rtk_gt.h
     "rtk_gt_labels": [_p, _p, _p],
     "rtk_eval_frame": [_p, _p, _p, _p],

@@ -20,6 +20,13 @@ A box fitted from one frame's two to ten radar points is a fraction of the objec
 `BoxFilter` holds the parameters of a constant-velocity Kalman filter run along every track of a result log
 (rtk_result_log_filter_boxes, csrc/track_box_filter.hip; the rule is stated in include/rtk_fused.h, "Filtered boxes"), with an optional
 backward pass and an optional size from the whole track; `FilteredBoxes` is its result and goes wherever an `ObjectBoxes` goes.
+
+    trk = BatchedTracker(net, streams=B, boxes=True, box_filter=BoxFilter(max_gap=3))      # the same filter, a frame at a time
+    out.filtered_boxes[b, j], out.filtered_velocity[b, j]      # the track's box and velocity now, inside the step
+
+`filter_step_raw` is that launch (rtk_track_box_filter_step, csrc/track_box_step.hip; the rule: include/rtk_fused.h, "Filtered boxes
+inside the step"): the filter's state travels with the tracker's table and is advanced in place once per step; the forward pass with
+the filter's own sizes only (`check_step_filter`), and for a measured object the bits `ResultLog.filter_boxes` gives its record.
 """
 import ctypes
 import math
@@ -229,3 +236,78 @@ def check_filtered_into(into, B, rows, dev):
         if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != torch.device(dev):
             raise ValueError("into.%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
     return into
+
+
+# ---- filtered boxes inside the step -------------------------------------------------------------------------------------------------
+
+def check_step_filter(filter):
+    """`check_filter` for the filter a tracker runs inside its step (rtk_track_box_filter_step): -> filter; raises ValueError also
+    for smooth=1 or size_rule=1."""
+    check_filter(filter)
+    if filter.smooth or filter.size_rule:
+        raise ValueError("box_filter: smooth=%d, size_rule=%d: neither is causal -- the backward pass and the extent rule look at a "
+                         "track's later frames, which a step does not have; run them over the log when the clip is over "
+                         "(ResultLog.filter_boxes)" % (filter.smooth, filter.size_rule))
+    return filter
+
+
+class StepBoxes:
+    """`filter_step_raw`'s outputs (device tensors): box (B,K,8) float64 and valid (B,K) int32 in the layout of an ObjectBoxes' (the
+    track's box now: filtered where the row was measured, predicted where it was carried; zeros, valid 0 elsewhere); vel (B,K,4) float64
+    = vx, vy, vz per frame and the unwrapped yaw; aligned (B,K,4) float64 = the reading's yaw, l, w, h as the filter took them (zeros
+    unless measured); gap (B,K) int32 = the frames since the track's previous measurement where the row continued it, else -1."""
+
+    NAMES = (("box", 8, torch.float64), ("valid", 0, torch.int32), ("vel", 4, torch.float64), ("aligned", 4, torch.float64),
+             ("gap", 0, torch.int32))
+
+    def __init__(self, box, valid, vel, aligned, gap):
+        self.box, self.valid, self.vel, self.aligned, self.gap = box, valid, vel, aligned, gap
+
+    @classmethod
+    def empty(cls, B, K, device):
+        """Uninitialised buffers (what `into=` takes)."""
+        return cls(*(torch.empty((B, K) + ((w,) if w else ()), dtype=dt, device=device) for _, w, dt in cls.NAMES))
+
+
+def _check_tensor(what, t, shape, dtype, dev):
+    if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != torch.device(dev):
+        raise ValueError("filter_step: %s must be a contiguous %s tensor of shape %s on %s, got %s" % (
+            what, dtype, shape, dev, "%s %s on %s" % (t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__))
+    return t
+
+
+def filter_step_raw(ids_prev, count_prev, ids_new, count_new, num_objects, box, valid, state, since, filter=None, active=None, reset=None,
+                    into=None):
+    """rtk_track_box_filter_step (include/rtk_fused.h, "Filtered boxes inside the step") for tables from anywhere: one launch on the
+    current stream, no synchronisation.  ids_prev / ids_new (B,K) int32 and count_prev / count_new (B) int32: the previous table and
+    the one this step wrote; num_objects (B) int32: the first rows of the new table that are this frame's detections; box (B,K,8)
+    float64 and valid (B,K) int32: their boxes (an ObjectBoxes' fields); state (B,K,16) float64 and since (B,K) int32: the filter's
+    state, ADVANCED IN PLACE (start from zeros and -1); active / reset (B) or None.  filter: a BoxFilter with smooth = size_rule = 0
+    (None: its defaults).  -> StepBoxes; into: a StepBoxes to write into (`StepBoxes.empty(B, K, device)`) -- with it and device
+    tensors for active and reset nothing is allocated and the call can be captured in a graph."""
+    flt = check_step_filter(BoxFilter() if filter is None else filter)
+    if not torch.is_tensor(ids_new) or ids_new.dim() != 2:
+        raise ValueError("filter_step: ids_new must be a (B,K) int32 tensor")
+    B, K = ids_new.shape
+    if not 1 <= K <= MAX_OBJECTS:
+        raise ValueError("filter_step: K=%d rows outside [1, %d]" % (K, MAX_OBJECTS))
+    dev = ids_new.device
+    for what, t, shape, dtype in (("ids_prev", ids_prev, (B, K), torch.int32), ("ids_new", ids_new, (B, K), torch.int32),
+                                  ("count_prev", count_prev, (B,), torch.int32), ("count_new", count_new, (B,), torch.int32),
+                                  ("num_objects", num_objects, (B,), torch.int32), ("box", box, (B, K, 8), torch.float64),
+                                  ("valid", valid, (B, K), torch.int32), ("state", state, (B, K, 16), torch.float64),
+                                  ("since", since, (B, K), torch.int32)):
+        _check_tensor(what, t, shape, dtype, dev)
+    if into is not None:
+        for name, w, dt in StepBoxes.NAMES:
+            _check_tensor("into." + name, getattr(into, name, None), (B, K) + ((w,) if w else ()), dt, dev)
+        if into.box.data_ptr() == box.data_ptr() or into.valid.data_ptr() == valid.data_ptr():
+            raise ValueError("filter_step: into must not share box or valid with the input boxes")
+    out = into if into is not None else StepBoxes.empty(B, K, dev)
+    act, rst = _flag_bytes(active, B, dev), _flag_bytes(reset, B, dev)
+    par = flt.block()
+    _lib.call("rtk_track_box_filter_step", B, K, None if act is None else act.data_ptr(), None if rst is None else rst.data_ptr(),
+              ids_prev.data_ptr(), count_prev.data_ptr(), ids_new.data_ptr(), count_new.data_ptr(), num_objects.data_ptr(), box.data_ptr(),
+              valid.data_ptr(), ctypes.addressof(par), state.data_ptr(), since.data_ptr(), out.box.data_ptr(), out.valid.data_ptr(),
+              out.vel.data_ptr(), out.aligned.data_ptr(), out.gap.data_ptr(), _stream())
+    return out

@@ -6,6 +6,7 @@
 #include <math.h>
 
 #include "box_fit.h"      // BF_PI
+#include "rtk_common.h"
 #include "rtk_fused.h"
 
 struct bxf_state_t {
@@ -104,4 +105,24 @@ __device__ __forceinline__ void bxf_output(const double *m, const double *v, dou
     else if (yaw < -(BF_PI / 2.0)) yaw = yaw + BF_PI;
     box[0] = m[0]; box[1] = m[1]; box[2] = m[2]; box[3] = l; box[4] = w; box[5] = m[6]; box[6] = yaw; box[7] = l * w;
     vel[0] = v[0]; vel[1] = v[1]; vel[2] = v[2]; vel[3] = m[3];
+}
+
+// host side: the ranges of rtk_box_filter_t outside which both launches refuse the call (who: the entry point, for the message)
+static inline bool bxf_positive(double x) { return isfinite(x) && x > 0.0; }
+static inline bool bxf_not_negative(double x) { return isfinite(x) && x >= 0.0; }
+
+static inline int bxf_check_ranges(const char *who, const rtk_box_filter_t *par) {
+    RTK_REQUIRE(par, "%s: null parameters", who);
+    RTK_REQUIRE(bxf_positive(par->r_pos) && bxf_positive(par->r_yaw) && bxf_positive(par->r_size),
+                "%s: r_pos=%g, r_yaw=%g, r_size=%g: finite numbers > 0", who, par->r_pos, par->r_yaw, par->r_size);
+    RTK_REQUIRE(bxf_not_negative(par->q_pos) && bxf_not_negative(par->q_vel) && bxf_not_negative(par->q_yaw) && bxf_not_negative(par->q_size),
+                "%s: q_pos=%g, q_vel=%g, q_yaw=%g, q_size=%g: finite numbers >= 0", who, par->q_pos, par->q_vel, par->q_yaw, par->q_size);
+    RTK_REQUIRE(bxf_positive(par->p0) && bxf_positive(par->p0_vel), "%s: p0=%g, p0_vel=%g: finite numbers > 0", who, par->p0, par->p0_vel);
+    RTK_REQUIRE(par->symmetry == 2 || par->symmetry == 4, "%s: symmetry=%d is neither 2 nor 4", who, par->symmetry);
+    RTK_REQUIRE(par->max_gap >= 1 && par->max_gap <= RTK_BOX_FILTER_MAX_GAP, "%s: max_gap=%d outside [1, %d]", who, par->max_gap,
+                RTK_BOX_FILTER_MAX_GAP);
+    RTK_REQUIRE((par->smooth == 0 || par->smooth == 1) && (par->size_rule == 0 || par->size_rule == 1) && par->size_percent >= 0 &&
+                    par->size_percent <= 100,
+                "%s: smooth=%d, size_rule=%d (0 or 1 each), size_percent=%d (0 ... 100)", who, par->smooth, par->size_rule, par->size_percent);
+    return RTK_OK;
 }

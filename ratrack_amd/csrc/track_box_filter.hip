@@ -271,9 +271,6 @@ __global__ __launch_bounds__(BXF_THREADS) void filter_boxes_kernel(const rtk_res
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static bool bxf_positive(double x) { return isfinite(x) && x > 0.0; }
-static bool bxf_not_negative(double x) { return isfinite(x) && x >= 0.0; }
-
 extern "C" int rtk_result_log_filter_boxes(int B, const rtk_result_log_t *lg, const unsigned char *keep, const double *box, const int *valid,
                                            const rtk_box_filter_t *par, double *out_box, int *out_valid, double *vel, double *state,
                                            double *aligned, int *link, int *flags, rtk_stream_t stream) {
@@ -281,21 +278,7 @@ extern "C" int rtk_result_log_filter_boxes(int B, const rtk_result_log_t *lg, co
     RTK_REQUIRE(lg && lg->F >= 1 && lg->R >= 1 && lg->cursor && lg->frame && lg->tag && lg->rec_track, "result_log_filter_boxes: null or empty log");
     RTK_REQUIRE((long long)B * 4 * lg->F < (1ll << 31) && (long long)B * 16 * lg->R < (1ll << 31),
                 "result_log_filter_boxes: a log of B=%d x (F=%d, R=%d): a table of 2^31 words or more", B, lg->F, lg->R);
-    RTK_REQUIRE(par, "result_log_filter_boxes: null parameters");
-    RTK_REQUIRE(bxf_positive(par->r_pos) && bxf_positive(par->r_yaw) && bxf_positive(par->r_size),
-                "result_log_filter_boxes: r_pos=%g, r_yaw=%g, r_size=%g: finite numbers > 0", par->r_pos, par->r_yaw, par->r_size);
-    RTK_REQUIRE(bxf_not_negative(par->q_pos) && bxf_not_negative(par->q_vel) && bxf_not_negative(par->q_yaw) && bxf_not_negative(par->q_size),
-                "result_log_filter_boxes: q_pos=%g, q_vel=%g, q_yaw=%g, q_size=%g: finite numbers >= 0", par->q_pos, par->q_vel, par->q_yaw,
-                par->q_size);
-    RTK_REQUIRE(bxf_positive(par->p0) && bxf_positive(par->p0_vel), "result_log_filter_boxes: p0=%g, p0_vel=%g: finite numbers > 0", par->p0,
-                par->p0_vel);
-    RTK_REQUIRE(par->symmetry == 2 || par->symmetry == 4, "result_log_filter_boxes: symmetry=%d is neither 2 nor 4", par->symmetry);
-    RTK_REQUIRE(par->max_gap >= 1 && par->max_gap <= RTK_BOX_FILTER_MAX_GAP, "result_log_filter_boxes: max_gap=%d outside [1, %d]", par->max_gap,
-                RTK_BOX_FILTER_MAX_GAP);
-    RTK_REQUIRE((par->smooth == 0 || par->smooth == 1) && (par->size_rule == 0 || par->size_rule == 1) && par->size_percent >= 0 &&
-                    par->size_percent <= 100,
-                "result_log_filter_boxes: smooth=%d, size_rule=%d (0 or 1 each), size_percent=%d (0 ... 100)", par->smooth, par->size_rule,
-                par->size_percent);
+    if (const int e = bxf_check_ranges("result_log_filter_boxes", par)) return e;
     RTK_REQUIRE(box && valid, "result_log_filter_boxes: null input boxes");
     RTK_REQUIRE(out_box && out_valid && vel && state && aligned && link && flags, "result_log_filter_boxes: null output");
     RTK_REQUIRE(out_box != box && out_valid != valid, "result_log_filter_boxes: the outputs must not alias the input boxes");

@@ -130,7 +130,18 @@ class StepResult:
     yaw, area) in the sensor frame (ratrack_amd/boxes.py; zeros past num_objects and on an inactive stream); object_box_valid (B,K)
     int32: the object's point count (0: no object, -1: a coordinate that is not finite); object_box_cand (B,K) int32: the winning
     candidate of the search (-1: no box); object_box_flags (B) int32: boxes.FLAG_AXIS where an object above boxes.MAX_POINTS points was
-    fitted axis-aligned."""
+    fitted axis-aligned.
+    With `BatchedTracker(box_filter=BoxFilter(...))` (else None): the boxes of the TRACKS in the table this step wrote, from a Kalman
+    filter advanced inside the step (include/rtk_fused.h, "Filtered boxes inside the step").  Rows j < num_objects[b] are the objects,
+    in the order of `object_ids`; with `max_age` the rows up to table_count[b] are the coasted tracks, aligned with `table_ids`.
+    filtered_boxes (B,K,8) float64 and filtered_valid (B,K) int32 in the layout of object_boxes / object_box_valid (they go to
+    `TrackScorer.update_raw(det_boxes=, det_box_valid=)` as they are): the filtered box where the row was measured this frame, the
+    predicted box (filtered_valid 0) where its track was carried, zeros where the row has no filter; filtered_velocity (B,K,4) float64:
+    vx, vy, vz in metres per frame and the unwrapped yaw; filtered_aligned (B,K,4) float64: the reading's yaw, l, w, h as the filter
+    took them; filtered_gap (B,K) int32: k where the row continued a track measured k frames ago, else -1; filtered_since (B,K) int32
+    (-1: no filter, 0: measured this frame, s: frames since the last measurement) and filtered_state (B,K,16) float64 (the mean x, y,
+    z, yaw, l, w, h, vx, vy, vz, then P00, P01, P11, Pyaw, Psize, 0): the tracker's own buffers `box_since` / `box_state`, advanced in
+    place -- valid until the next step, as `desc_prev` is under static_state."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -240,7 +251,7 @@ class BatchedTracker:
 
     def __init__(self, net, streams, max_objects=128, iters=500, alpha=0.9, eps=1.5, threshold=0.5, train_mode=False,
                  static_state=False, graph=False, graph_warmup=2, engine=None, max_age=None, motion=None, motion_beta=1.0,
-                 assign="sinkhorn", min_affinity=0.01, boxes=False, box_min_extent=0.0):
+                 assign="sinkhorn", min_affinity=0.01, boxes=False, box_min_extent=0.0, box_filter=None):
         """train_mode: accept a train-mode net -- for a caller that runs the backbone itself and uses `associate` and the state only
         (track_train.SequenceTrainer); `step()` stays the eval-mode path.
         static_state: this frame's objects are always written to slot 0 of `desc` / `ids` / `count` and the previous objects read
@@ -279,11 +290,22 @@ class BatchedTracker:
         `object_box_valid`, `object_box_cand` and `object_box_flags` are None.  True: one more launch after the association
         (rtk_object_boxes, ratrack_amd/boxes.py; inside the captured graph under `graph=True`) fits every object's oriented box:
         `StepResult.object_boxes` (B,K,8) float64, `boxes.object_boxes(out)`'s.  box_min_extent: the least length, width and height
-        of a box, a finite number >= 0 (needs boxes=True to be anything but 0).  A launch constant, like max_age."""
-        from .boxes import check_min_extent
+        of a box, a finite number >= 0 (needs boxes=True to be anything but 0).  A launch constant, like max_age.
+        box_filter: None (default): the tracker as it is without the keyword, the same launches, buffers and bits; the `filtered_*`
+        fields of `StepResult` are None.  A boxes.BoxFilter with smooth = 0 and size_rule = 0 (needs boxes=True): one more launch after
+        rtk_object_boxes (rtk_track_box_filter_step; inside the captured graph under `graph=True`) runs the constant-velocity Kalman
+        filter of `ResultLog.filter_boxes` along every track, a frame at a time: its state lives in `box_state` (B,K,16) float64 and
+        `box_since` (B,K) int32, single buffers advanced in place, and follows a track's id through the table -- through coasting
+        with `max_age`, both association modes, reset and inactive streams.  A measured object's `filtered_boxes` row holds the bits
+        `ResultLog.filter_boxes` gives its record with the same filter.  The association does not use the prediction.  Launch
+        constants, like max_age."""
+        from .boxes import check_min_extent, check_step_filter
         self.boxes, self.box_min_extent = bool(boxes), check_min_extent(box_min_extent)
         if not self.boxes and self.box_min_extent != 0.0:
             raise ValueError("box_min_extent=%r without boxes=True: there is no box to pad" % (box_min_extent,))
+        self.box_filter = None if box_filter is None else check_step_filter(box_filter)
+        if self.box_filter is not None and not self.boxes:
+            raise ValueError("box_filter=%r without boxes=True: there is no box to filter" % (box_filter,))
         if max_age is not None and (isinstance(max_age, bool) or not isinstance(max_age, int) or max_age < 0):
             raise ValueError("max_age=%r: None (no track memory) or an integer >= 0 (frames a lost track is kept)" % (max_age,))
         check_motion(motion, motion_beta, max_age, "max_age")
@@ -320,6 +342,10 @@ class BatchedTracker:
             self.vel = torch.zeros(2, B, K, 3, device=dev)
         # the weight of every stream's matching (assign="optimal"): the kernel leaves an inactive stream's word as it is
         self.assign_total = torch.zeros(B, dtype=torch.int64, device=dev) if assign == "optimal" else None
+        self.box_state = self.box_since = None
+        if self.box_filter is not None:      # the filter of every row of the table: ONE buffer each, advanced in place by its launch
+            self.box_state = torch.zeros(B, K, 16, dtype=torch.float64, device=dev)
+            self.box_since = torch.full((B, K), -1, dtype=torch.int32, device=dev)
         self.cur = 0
         self._work = None
         self.last = None
@@ -399,7 +425,8 @@ class BatchedTracker:
 
     def associate(self, pc1, feature1, flow, cls, prop, n_valid, reset, active):
         """The post-backbone half of step(): four launches, the state swap (static_state: the state advance first, five launches);
-        with max_age one more, rtk_track_memory (with motion: rtk_track_memory_motion in its place); no host synchronisation.  reset / active (B,) uint8 and n_valid (2,B) int32 (or
+        with max_age one more, rtk_track_memory (with motion: rtk_track_memory_motion in its place); with boxes rtk_object_boxes and with
+        box_filter rtk_track_box_filter_step behind it; no host synchronisation.  reset / active (B,) uint8 and n_valid (2,B) int32 (or
         None) are device tensors."""
         B, K = self.B, self.K
         N = pc1.shape[2]
@@ -470,6 +497,14 @@ class BatchedTracker:
             from .boxes import object_boxes_raw
             bx = object_boxes_raw(pc1, obj, num, K, active=active, min_extent=self.box_min_extent)
             fitted.update(object_boxes=bx.box, object_box_valid=bx.valid, object_box_cand=bx.cand, object_box_flags=bx.flags)
+        fitted.update(filtered_boxes=None, filtered_valid=None, filtered_velocity=None, filtered_aligned=None, filtered_gap=None,
+                      filtered_since=None, filtered_state=None)
+        if self.box_filter is not None:
+            from .boxes import filter_step_raw
+            fb = filter_step_raw(self.ids[prev], self.count[prev], self.ids[cur], self.count[cur], num, bx.box, bx.valid, self.box_state,
+                                 self.box_since, filter=self.box_filter, active=active, reset=reset)
+            fitted.update(filtered_boxes=fb.box, filtered_valid=fb.valid, filtered_velocity=fb.vel, filtered_aligned=fb.aligned,
+                          filtered_gap=fb.gap, filtered_since=self.box_since, filtered_state=self.box_state)
         if not self.static_state:
             self.cur = prev                # this frame's objects are the next frame's previous objects: a swap, not a copy
         out = StepResult(flow=flow, cls=cls, h=self.h, point_track_id=point_track_id, num_objects=num, object_ids=object_ids,
@@ -554,6 +589,7 @@ class TrackerPipeline:
     sequential within a group: concurrency comes from different groups only.  Every group has its own copy of the backbone engine
     (packed weights shared, per-engine state separate); beyond two groups the engines run their geometry kernels on their own
     stream and the cost volume on a share of the CUs, as in `GraphPipeline`.  The weights are those at construction.
+    Every other keyword of `BatchedTracker` (max_age, motion, assign, boxes, box_filter, ...) is forwarded to every group's tracker.
     `submit` returns group g's `StepResult`, enqueued on group g's stream: its tensors and host accessors (`objects`, `aff_mat`,
     `indices1(b)`, `check`, `write_results`) are valid after `drain()` or under `pipe.streams[g]`, and until group g's next submit.
     Inputs are read on group g's stream after everything the current stream held at the time of the submit."""
